@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- ray-samples/sec of a train step of the Contrastive-Lift render hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes outputs with --dump-outputs DIR and prints the line.  The dump is the timed step
+run once more, untimed, from the set-up state with the last timed step's batch (rendered rgb / semantics of the main pass, the four losses,
+the gradient arena, the parameter arena after Adam): its inputs are the same in every run, whereas the state the timed steps reach is
+not -- their gradients are sums through floating-point atomics, and Adam carries the last-bit differences into the parameters.  --full
+adds, after the timed region, what the headline does not need: the roofline replays, the per-pass split, the other arithmetics and shapes, the frame
+render, the CPU baseline, and with N > 1 the exchange timed alone and the data-parallel self-check.
 
 Step = one full ``training_step`` of the reference (trainer/train_panopli_tensorf.py:148-228) at steady state:
 main pass over 4096 rays (forward of all heads, MSE + TV + confidence-weighted CE + dist-reg, backward, Adam)
@@ -65,10 +72,22 @@ def parse():
                     help="after the timed region: K replays of one full training step from the timed region's snapshot with the asynchronous "
                          "gradient exchange ON (RCCL kernels beside the persistent MFMA kernels), every replay's rendered outputs bit-compared "
                          "with the first one's and its gradients compared within the noise of the floating-point atomics; counts in `soak`")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bf16-mode and frame-render extras measured after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline, after the timed region: the roofline replays of the timed steps, "
+                         "the per-pass split, the extras (unless --no-extras), the CPU baseline (unless --no-cpu-baseline), with N > 1 the exchange "
+                         "timed alone and the data-parallel self-check, with --inference-sharded the frame's roofline.  Without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more from the set-up state with the last timed step's batch (the same "
+                         "inputs in every run) and write what it computed as float32 DIR/<name>.npy (at most 64 MB in all: a larger array is cut "
+                         "to a fixed, seeded sample of its rows); with --inference-sharded, the last timed frame")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the bf16-mode and frame-render extras measured after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=30.0)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def self_launch(a):
@@ -173,9 +192,15 @@ def main():
     _ = tr._rng_state()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     ev[0].record(); torch.zeros(8, device=dev).cpu(); ev[1].record(); torch.cuda.synchronize(); _ = ev[0].elapsed_time(ev[1])
-    # ... and so are the buffers of the state snapshot and the per-step events of the timed loop: allocated / created (and recorded once) HERE, so
-    # that the caching allocator and the runtime's event pool are in the same state during the warm-up as during the timed steps
-    snap_bufs = [torch.empty_like(model.param_flat) for _ in range(5)]
+    # ... and so are the buffers of the state snapshot (only the replays after the timed region use it: --full, --soak) and the per-step events of
+    # the timed loop: allocated / created (and recorded once) HERE, so that the caching allocator and the runtime's event pool are in the same
+    # state during the warm-up as during the timed steps
+    need_snap = a.full or a.soak > 0
+    snap_bufs = [torch.empty_like(model.param_flat) for _ in range(5)] if need_snap else None
+    # --dump-outputs: the set-up state, taken before any step -- the only training state that is the same in every run (every step sums
+    # gradients through floating-point atomics, and Adam carries their last-bit differences into the parameters, so the state after the
+    # warm-up and the timed steps differs between runs)
+    init = state_snapshot(model, tr, [torch.empty_like(model.param_flat) for _ in range(5)]) if a.dump_outputs else None
     # ... and so is the interpreter's first FULL garbage collection: it traverses everything the imports and the set-up created (35 - 60 ms) and
     # fell at a fixed position of the run -- timed step 19 of 20 in seven runs out of eight once this round's edits had shifted the allocation
     # count.  Collected once here and frozen (gc.freeze: the set-up's objects are not traversed again); the step itself allocates little.
@@ -196,10 +221,7 @@ def main():
         tr.training_step(batches[i % n_batches], lean=a.lean)
     # snapshot of the training state at the start of the timed region (parameters + both Adam states): the roofline pass below
     # replays exactly these steps with per-launch events
-    for buf, src in zip(snap_bufs, (model.param_flat, tr.opt_main.m, tr.opt_main.v, tr.opt_inst.m, tr.opt_inst.v)):
-        buf.copy_(src)
-    snap = (snap_bufs[0], {"m": snap_bufs[1], "v": snap_bufs[2], "t": dict(tr.opt_main.t), "lr_scale": tr.opt_main.lr_scale},
-            {"m": snap_bufs[3], "v": snap_bufs[4], "t": dict(tr.opt_inst.t), "lr_scale": tr.opt_inst.lr_scale}, tr._rng_state())
+    snap = state_snapshot(model, tr, snap_bufs) if need_snap else None
     sync_all()
     # one event per step boundary (recorded, never waited on inside the loop): the per-step GPU times afterwards show whether the K steps were
     # uniform or whether one of them carried a one-off stall (seen: ~40 ms once in the first GPU process on a fresh box)
@@ -213,7 +235,162 @@ def main():
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
     if os.environ.get("CLIFT_BENCH_DUMP"):
         print("[steps] " + " ".join(f"{x:.2f}" for x in step_ms), file=sys.stderr)
+    step_ms_timed = list(step_ms)
     step_ms.sort()
+    if a.dump_outputs:
+        # the timed path's step once more, untimed, on inputs that are the same in every run: the set-up state and generators, the batch of
+        # the last timed step (every rank takes part: the step all-reduces its gradients)
+        restore_state(model, tr, init)
+        tr.training_step(batches[(a.steps - 1) % n_batches], lean=a.lean)
+        if rank == 0:
+            lo = tr.last_outputs
+            dump_outputs(a.dump_outputs, {"rgb": lo[0], "semantics": lo[1], "losses": tr.losses, "grads": model.grad_flat,
+                                          "params": model.param_flat})
+    rec_mean, rec, rec_all = roofline_replays(a, tr, batches, snap, sync_all) if a.full else (None, None, None)
+    ar_ms, rank_ms, dp_check = None, None, None
+    if world > 1:
+        cdev = dev if backend == "nccl" else "cpu"
+        t = torch.tensor([dt, -dt], device=cdev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        rank_ms = [-float(t[1]) / a.steps * 1e3, float(t[0]) / a.steps * 1e3]       # fastest / slowest rank's wall time per step
+        dt = float(t[0])
+    if world > 1 and a.full:
+        # the exchange by itself: the main pass's gradient range (what every backward all-reduces), 5 times, event-bracketed on this stream
+        r0, r1 = tr.main_range
+        gbuf = model.grad_flat[r0:r1]
+        dist.all_reduce(gbuf); sync_all()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            dist.all_reduce(gbuf)
+        e1.record(); sync_all()
+        ar_ms = {"main_range_bytes": 4 * (r1 - r0), "ms": e0.elapsed_time(e1) / 5, "backend": backend,
+                 "note": "one all-reduce of the main pass's gradient range alone (no compute beside it), mean of 5"}
+        dp_check = data_parallel_self_check(tr, model, batches[0], snap, a.lean, cdev, sync_all)
+    soak = None
+    if a.soak > 0:
+        soak = soak_replays(tr, model, batches[0], snap, a.soak, a.lean, (dev if backend == "nccl" else "cpu") if world > 1 else None, sync_all)
+    ms_step = dt / a.steps * 1e3
+    samples_step = world * (a.rays + a.inst_rays) * S
+    value = samples_step / (dt / a.steps)
+
+    extra = {}
+    roof = None
+    cpu = None
+    if a.full and rank == 0:
+        roof = roofline(rec_mean, rec_all, a.steps, engine, a.dtype, ms_step, rec_min=rec)
+    if a.full and rank == 0 and world == 1:
+        # ---- per-pass split and sample statistics (outside the timed region)
+        def timed(fn, n=n_batches):          # cycles through the same batches as the timed loop
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for i in range(n):
+                fn(batches[i % n_batches])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / n
+        t_main = timed(lambda b: tr.main_pass(b[0], lean=a.lean))
+        t_inst = timed(lambda b: tr.instance_pass(b[1]))
+        ctxs = tr.main_pass(batches[0][0], lean=a.lean)
+        M = sum((int(c.ray_start[-1]) if getattr(c, "capped", False) else c.M) for c in ctxs)
+        inbox = sum(int((c.alpha > 0).sum()) for c in ctxs)
+        extra = dict(main_pass_ms=round(t_main * 1e3, 3), instance_pass_ms=round(t_inst * 1e3, 3),
+                     main_pass_samples_per_s=a.rays * S / t_main, instance_pass_samples_per_s=a.inst_rays * S / t_inst,
+                     f_active=M / (a.rays * S), f_inbox_alpha_gt0=inbox / (a.rays * S), samples_per_ray=S)
+        extra["active_samples_per_s_main_pass"] = M / t_main            # cost follows the ACTIVE samples; comparable across scenes
+        if not a.no_extras and a.dtype in ("fp32", "fp32x6"):
+            # the reference's main pass computes the instance heads and discards their output (T:155); without that dead work:
+            t_lean = timed(lambda b: tr.main_pass(b[0], lean=True))
+            extra["lean_main_pass_ms"] = round(t_lean * 1e3, 3)
+            extra["lean_step_ms_estimate"] = round((t_lean + t_inst) * 1e3, 3)
+            # The other arithmetics and shapes on the same scene, AFTER the timed region, so that the driver-run record carries them: the other
+            # fp32 arithmetic (exact fp32 MFMA when the run is the default fp32x6, and vice versa) with its own roofline, BASELINE configs[2]
+            # (bf16 MLP operands), configs[3]'s per-GPU shape with the strong-scaling projection, configs[4] (frame render): same step
+            # definition, 10 steps after 3 warm-up steps / one 262144-ray tile
+            extra.update(inference_probe(cl, model, renderer, pool))
+            extra.update(bf16_probe(a, dev, batches, S))
+            extra.update(other_fp32_probe(a, dev, batches, S, "fp32" if a.dtype == "fp32x6" else "fp32x6"))
+            extra.update(small_batch_probe(a, dev, pool, S, tr.model.arena.range_of("grid_density", "grid_app", "net_app", "net_sem")))
+        if "bf16_ms_per_step" in extra:
+            extra["bf16"] = {"mlp_arithmetic": MLP_ARITHMETIC["bf16"], "ms_per_step": extra["bf16_ms_per_step"], "ray_samples_per_s": extra["bf16_ray_samples_per_s"],
+                             "roofline": {k: v for k, v in (extra.get("bf16_roofline") or {}).items() if k != "families"}}
+        if roof is not None:
+            # (the driver's record keeps `roofline`, `config` and `cpu_baseline` whole and only the NAMES of other keys: what a reader of that
+            # record should see of the extras rides inside `roofline`)
+            if "rays1024_ms_per_step" in extra:
+                extra["rays1024"] = {"ms_per_step": extra["rays1024_ms_per_step"], "nosync_ms_per_step": extra.get("rays1024_nosync_ms_per_step"),
+                                     "shape": "1024 main-pass rays + 1024 instance rays (configs[3] per-GPU shape)"}
+            for k in ("exact_fp32", "fp32x6", "bf16", "rays1024", "configs3_strong_scaling_projection", "inference_roofline"):
+                if k in extra:
+                    roof.setdefault("other_measurements", {})[k] = extra[k]
+    rccl_ranks = dist.get_world_size() if (world > 1 and backend == "nccl") else 0
+    if world > 1:
+        # every rank has left the timed region, the replays and the collectives: the group is done with.  Rank 0 then times the CPU path ALONE
+        # (the other ranks have exited; `cores` = what this process may use) and prints the line.
+        dist.barrier()
+        dist.destroy_process_group()
+    if a.full and rank == 0 and not a.no_cpu_baseline:
+        cpu = cpu_baseline(model, renderer, batches[0], a, S)
+    if rank == 0:
+        line = {"metric": "ray-samples/sec (train step) at 4096 rays", "value": value, "unit": "ray-samples/s",
+                "main_pass_samples_per_s": extra.get("main_pass_samples_per_s"), "n_gpus": world,
+                "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": ("strong" if a.global_rays else "weak"),
+                "vs_baseline": None, "full": a.full,
+                "value_definition": "nominal ray-samples of one full training_step = (main-pass rays + instance-pass rays) x S, over all ranks, / step time; the "
+                                    "main pass alone (the 4096 rays of the metric's name) is `main_pass_samples_per_s`, and because cost follows the ACTIVE "
+                                    "samples (f_active of the nominal ones) `active_samples_per_s_main_pass` is the scene-independent figure",
+                "dtype": {"fp32": "f32", "bf16": "bf16", "fp32x6": "f32"}[a.dtype],
+                "data": "synthetic",
+                "config": {"workload": ("BASELINE configs[1] stand-in: ScanNet-shaped scene (C=22, E=3/D=6, grid 128^3, S=440), "
+                                        "full training_step = main pass 4096 rays + slow-fast instance pass 1024 rays, fp32") if a.dtype != "bf16" else
+                                       (f"BASELINE configs[2]-style bf16 mode on the configs[1] shapes (C={a.classes}, E=3/D=6, grid {a.grid}^3): MLP "
+                                        "operands bf16 (weights rounded in-kernel, hidden activations / gradients bf16-stored), fp32 accumulate; everything else fp32"),
+                           "mlp_arithmetic": MLP_ARITHMETIC[a.dtype],
+                           "main_pass_samples_per_s": extra.get("main_pass_samples_per_s"),
+                           "rays_per_gpu": a.rays, "instance_rays_per_gpu": a.inst_rays, "grid": a.grid, "classes": a.classes,
+                           "samples_per_ray": S, "chunk": a.chunk or a.rays, "lean_main_pass": bool(a.lean), "sync_free": bool(a.nosync),
+                           "parallelism": f"dp{world} (rays sharded, 1 all-reduce per backward)"},
+                "roofline": roof, "cpu_baseline": cpu,
+                "dist_backend": backend, "rccl_ranks": rccl_ranks,
+                "devices_visible": torch.cuda.device_count(),
+                "allreduce_overlap": (tr.overlap_decision or {"overlap": tr.overlap_allreduce}) if world > 1 else None,
+                "allreduce_cu_reserve": tr.allreduce_cu_reserve if world > 1 else None,
+                "allreduce_ms": ar_ms, "rank_ms_per_step_min_max": rank_ms, "data_parallel_self_check": dp_check, "soak": soak,
+                "scaling_note": ("`value` is BASELINE's metric (ray-samples/s of the whole job: every rank renders its own 4096 + 1024 rays -- N ranks "
+                                 "render N instance images per step where one rank renders one); the driver's efficiency = value(N) / (N value(1)), and "
+                                 "north_star's '>= 6x at 8 GPUs' is read against THIS ratio.  The step-TIME ratio of a fixed global batch "
+                                 "(--global-rays, configs[3]) is the other reading: see configs3_strong_scaling_projection")}
+        line.update(extra)
+        # (ADVICE r4) the arithmetic of the headline number at the top level, with the exact-fp32 step of the same run beside it when it was measured
+        line["arithmetic"] = {"fp32x6": "fp32x6 (fp32-faithful: six bf16 MFMA products of exactly three-way-split fp32 operands, fp32 accumulate)",
+                              "fp32": "exact fp32 (fp32 MFMA)", "bf16": "bf16 operands, fp32 accumulate"}[a.dtype]
+        if a.dtype == "fp32x6" and isinstance(extra.get("exact_fp32"), dict):
+            line["exact_fp32_ms_per_step"] = extra["exact_fp32"].get("ms_per_step")
+        line["step_ms_median"] = step_ms[len(step_ms) // 2]
+        line["step_ms_min_max"] = [step_ms[0], step_ms[-1]]
+        line["step_ms"] = step_ms_timed                 # GPU time of every timed step, in order (events at the step boundaries)
+        print(json.dumps(line))
+
+
+def state_snapshot(model, tr, bufs):
+    """Training state (parameters, both Adam states, the step's generators) copied into five arena-sized buffers."""
+    for buf, src in zip(bufs, (model.param_flat, tr.opt_main.m, tr.opt_main.v, tr.opt_inst.m, tr.opt_inst.v)):
+        buf.copy_(src)
+    return (bufs[0], {"m": bufs[1], "v": bufs[2], "t": dict(tr.opt_main.t), "lr_scale": tr.opt_main.lr_scale},
+            {"m": bufs[3], "v": bufs[4], "t": dict(tr.opt_inst.t), "lr_scale": tr.opt_inst.lr_scale}, tr._rng_state())
+
+
+def restore_state(model, tr, snap):
+    model.param_flat.copy_(snap[0])
+    tr.opt_main.load_state_dict(snap[1])
+    tr.opt_inst.load_state_dict(snap[2])
+    tr.load_rng_state(snap[3])
+
+
+def roofline_replays(a, tr, batches, snap, sync_all):
+    """--full: replays of the timed steps from their snapshot with matrix-core launches bracketed by HIP events; returns the records
+    ``roofline`` is built from (dominant family: per-launch median and minimum of the replays; every launch: one replay)."""
+    from contrastive_lift_amd import engine
+    model, n_batches = tr.model, len(batches)
     # ---- roofline pass: the SAME steps again from the same state (the active-sample count drifts while the field trains, so
     # any other step would see a different launch mix), every clift_gemm launch bracketed by two HIP events on its launch
     # stream (torch's current stream; the side-stream mode is off by default).  Kept out of the timed region because creating
@@ -226,12 +403,7 @@ def main():
         """Re-run the timed steps from the snapshot with the selected matrix-core launches bracketed by HIP events.  Two launch sites:
         engine.gemm (clift_gemm) and engine.first2 (clift_xyz_head_first2_fwd: the K = 3 layer generated inside the persistent kernel
         of the first 256 x 256 layer -- kind "fwd_gen", FLOPs of both layers)."""
-        def restore():
-            model.param_flat.copy_(snap[0])
-            tr.opt_main.load_state_dict(snap[1])
-            tr.opt_inst.load_state_dict(snap[2])
-            tr.load_rng_state(snap[3])          # the per-ray jitter: same samples, same launch sizes
-        restore()
+        restore_state(model, tr, snap)          # (the generators too: the per-ray jitter -- same samples, same launch sizes)
         out = []
 
         def bracket(kind, M, N, K, extra_flops, nbytes, fn):
@@ -318,126 +490,7 @@ def main():
     sub = [x for x in rec_all if dom_sel(x[0], x[2])]
     if len(sub) == len(rec) and all(same(x, y) for x, y in zip(rec, sub)):
         rec = [x[:4] + (min(x[4], y[4]),) + x[5:] for x, y in zip(rec, sub)]
-    ar_ms, rank_ms, dp_check = None, None, None
-    if world > 1:
-        cdev = dev if backend == "nccl" else "cpu"
-        t = torch.tensor([dt, -dt], device=cdev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        rank_ms = [-float(t[1]) / a.steps * 1e3, float(t[0]) / a.steps * 1e3]       # fastest / slowest rank's wall time per step
-        dt = float(t[0])
-        # the exchange by itself: the main pass's gradient range (what every backward all-reduces), 5 times, event-bracketed on this stream
-        r0, r1 = tr.main_range
-        gbuf = model.grad_flat[r0:r1]
-        dist.all_reduce(gbuf); sync_all()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            dist.all_reduce(gbuf)
-        e1.record(); sync_all()
-        ar_ms = {"main_range_bytes": 4 * (r1 - r0), "ms": e0.elapsed_time(e1) / 5, "backend": backend,
-                 "note": "one all-reduce of the main pass's gradient range alone (no compute beside it), mean of 5"}
-        dp_check = data_parallel_self_check(tr, model, batches[0], snap, a.lean, cdev, sync_all)
-    soak = None
-    if a.soak > 0:
-        soak = soak_replays(tr, model, batches[0], snap, a.soak, a.lean, (dev if backend == "nccl" else "cpu") if world > 1 else None, sync_all)
-    ms_step = dt / a.steps * 1e3
-    samples_step = world * (a.rays + a.inst_rays) * S
-    value = samples_step / (dt / a.steps)
-
-    extra = {}
-    roof = None
-    cpu = None
-    if rank == 0:
-        roof = roofline(rec_mean, rec_all, a.steps, engine, a.dtype, ms_step, rec_min=rec)
-    if rank == 0 and world == 1:
-        # ---- per-pass split and sample statistics (outside the timed region)
-        def timed(fn, n=n_batches):          # cycles through the same batches as the timed loop
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for i in range(n):
-                fn(batches[i % n_batches])
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t) / n
-        t_main = timed(lambda b: tr.main_pass(b[0], lean=a.lean))
-        t_inst = timed(lambda b: tr.instance_pass(b[1]))
-        ctxs = tr.main_pass(batches[0][0], lean=a.lean)
-        M = sum((int(c.ray_start[-1]) if getattr(c, "capped", False) else c.M) for c in ctxs)
-        inbox = sum(int((c.alpha > 0).sum()) for c in ctxs)
-        extra = dict(main_pass_ms=round(t_main * 1e3, 3), instance_pass_ms=round(t_inst * 1e3, 3),
-                     main_pass_samples_per_s=a.rays * S / t_main, instance_pass_samples_per_s=a.inst_rays * S / t_inst,
-                     f_active=M / (a.rays * S), f_inbox_alpha_gt0=inbox / (a.rays * S), samples_per_ray=S)
-        extra["active_samples_per_s_main_pass"] = M / t_main            # cost follows the ACTIVE samples; comparable across scenes
-        if not a.no_extras and a.dtype in ("fp32", "fp32x6"):
-            # the reference's main pass computes the instance heads and discards their output (T:155); without that dead work:
-            t_lean = timed(lambda b: tr.main_pass(b[0], lean=True))
-            extra["lean_main_pass_ms"] = round(t_lean * 1e3, 3)
-            extra["lean_step_ms_estimate"] = round((t_lean + t_inst) * 1e3, 3)
-            # The other arithmetics and shapes on the same scene, AFTER the timed region, so that the driver-run record carries them: the other
-            # fp32 arithmetic (exact fp32 MFMA when the run is the default fp32x6, and vice versa) with its own roofline, BASELINE configs[2]
-            # (bf16 MLP operands), configs[3]'s per-GPU shape with the strong-scaling projection, configs[4] (frame render): same step
-            # definition, 10 steps after 3 warm-up steps / one 262144-ray tile
-            extra.update(inference_probe(cl, model, renderer, pool))
-            extra.update(bf16_probe(a, dev, batches, S))
-            extra.update(other_fp32_probe(a, dev, batches, S, "fp32" if a.dtype == "fp32x6" else "fp32x6"))
-            extra.update(small_batch_probe(a, dev, pool, S, tr.model.arena.range_of("grid_density", "grid_app", "net_app", "net_sem")))
-        if "bf16_ms_per_step" in extra:
-            extra["bf16"] = {"mlp_arithmetic": MLP_ARITHMETIC["bf16"], "ms_per_step": extra["bf16_ms_per_step"], "ray_samples_per_s": extra["bf16_ray_samples_per_s"],
-                             "roofline": {k: v for k, v in (extra.get("bf16_roofline") or {}).items() if k != "families"}}
-        if roof is not None:
-            # (the driver's record keeps `roofline`, `config` and `cpu_baseline` whole and only the NAMES of other keys: what a reader of that
-            # record should see of the extras rides inside `roofline`)
-            if "rays1024_ms_per_step" in extra:
-                extra["rays1024"] = {"ms_per_step": extra["rays1024_ms_per_step"], "nosync_ms_per_step": extra.get("rays1024_nosync_ms_per_step"),
-                                     "shape": "1024 main-pass rays + 1024 instance rays (configs[3] per-GPU shape)"}
-            for k in ("exact_fp32", "fp32x6", "bf16", "rays1024", "configs3_strong_scaling_projection", "inference_roofline"):
-                if k in extra:
-                    roof.setdefault("other_measurements", {})[k] = extra[k]
-    rccl_ranks = dist.get_world_size() if (world > 1 and backend == "nccl") else 0
-    if world > 1:
-        # every rank has left the timed region, the replays and the collectives: the group is done with.  Rank 0 then times the CPU path ALONE
-        # (the other ranks have exited; `cores` = what this process may use) and prints the line.
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0 and not a.no_cpu_baseline:
-        cpu = cpu_baseline(model, renderer, batches[0], a, S)
-    if rank == 0:
-        line = {"metric": "ray-samples/sec (train step) at 4096 rays", "value": value, "unit": "ray-samples/s",
-                "main_pass_samples_per_s": extra.get("main_pass_samples_per_s"), "n_gpus": world,
-                "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": ("strong" if a.global_rays else "weak"),
-                "vs_baseline": None,
-                "value_definition": "nominal ray-samples of one full training_step = (main-pass rays + instance-pass rays) x S, over all ranks, / step time; the "
-                                    "main pass alone (the 4096 rays of the metric's name) is `main_pass_samples_per_s`, and because cost follows the ACTIVE "
-                                    "samples (f_active of the nominal ones) `active_samples_per_s_main_pass` is the scene-independent figure",
-                "dtype": {"fp32": "f32", "bf16": "bf16", "fp32x6": "f32"}[a.dtype],
-                "data": "synthetic",
-                "config": {"workload": ("BASELINE configs[1] stand-in: ScanNet-shaped scene (C=22, E=3/D=6, grid 128^3, S=440), "
-                                        "full training_step = main pass 4096 rays + slow-fast instance pass 1024 rays, fp32") if a.dtype != "bf16" else
-                                       (f"BASELINE configs[2]-style bf16 mode on the configs[1] shapes (C={a.classes}, E=3/D=6, grid {a.grid}^3): MLP "
-                                        "operands bf16 (weights rounded in-kernel, hidden activations / gradients bf16-stored), fp32 accumulate; everything else fp32"),
-                           "mlp_arithmetic": MLP_ARITHMETIC[a.dtype],
-                           "main_pass_samples_per_s": extra.get("main_pass_samples_per_s"),
-                           "rays_per_gpu": a.rays, "instance_rays_per_gpu": a.inst_rays, "grid": a.grid, "classes": a.classes,
-                           "samples_per_ray": S, "chunk": a.chunk or a.rays, "lean_main_pass": bool(a.lean), "sync_free": bool(a.nosync),
-                           "parallelism": f"dp{world} (rays sharded, 1 all-reduce per backward)"},
-                "roofline": roof, "cpu_baseline": cpu,
-                "dist_backend": backend, "rccl_ranks": rccl_ranks,
-                "devices_visible": torch.cuda.device_count(),
-                "allreduce_overlap": (tr.overlap_decision or {"overlap": tr.overlap_allreduce}) if world > 1 else None,
-                "allreduce_cu_reserve": tr.allreduce_cu_reserve if world > 1 else None,
-                "allreduce_ms": ar_ms, "rank_ms_per_step_min_max": rank_ms, "data_parallel_self_check": dp_check, "soak": soak,
-                "scaling_note": ("`value` is BASELINE's metric (ray-samples/s of the whole job: every rank renders its own 4096 + 1024 rays -- N ranks "
-                                 "render N instance images per step where one rank renders one); the driver's efficiency = value(N) / (N value(1)), and "
-                                 "north_star's '>= 6x at 8 GPUs' is read against THIS ratio.  The step-TIME ratio of a fixed global batch "
-                                 "(--global-rays, configs[3]) is the other reading: see configs3_strong_scaling_projection")}
-        line.update(extra)
-        # (ADVICE r4) the arithmetic of the headline number at the top level, with the exact-fp32 step of the same run beside it when it was measured
-        line["arithmetic"] = {"fp32x6": "fp32x6 (fp32-faithful: six bf16 MFMA products of exactly three-way-split fp32 operands, fp32 accumulate)",
-                              "fp32": "exact fp32 (fp32 MFMA)", "bf16": "bf16 operands, fp32 accumulate"}[a.dtype]
-        if a.dtype == "fp32x6" and isinstance(extra.get("exact_fp32"), dict):
-            line["exact_fp32_ms_per_step"] = extra["exact_fp32"].get("ms_per_step")
-        line["step_ms_median"] = step_ms[len(step_ms) // 2]
-        line["step_ms_min_max"] = [step_ms[0], step_ms[-1]]
-        print(json.dumps(line))
+    return rec_mean, rec, rec_all
 
 
 def max_delta_across_ranks(t, cdev):
@@ -598,18 +651,23 @@ def bench_inference_sharded(a, model, renderer, dev, world, rank, backend):
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(zip(("rgb", "semantics", "instances", "distance"), out)))
     if rank == 0:
         P = rays.shape[0]
-        # active samples of the frame (cost follows them): counted once on this rank's tile, outside the timed region
-        b = inf.tile_bounds(P, world)
-        mine = rays[b[0]:b[1]]
-        act = 0
-        for i in range(0, mine.shape[0], chunk):
-            _, ctx = engine_render_forward(model, renderer, mine[i:i + chunk])
-            act += int(ctx.M)
-        fl = head_flops_per_active_sample(model)
         t_frame = dt / a.steps
-        tf = act * world * fl / t_frame / 1e12          # tiles are equal-sized; this rank's active fraction stands for the frame
+        roof = None
+        if a.full:
+            # active samples of the frame (cost follows them): counted once on this rank's tile, outside the timed region
+            b = inf.tile_bounds(P, world)
+            mine = rays[b[0]:b[1]]
+            act = 0
+            for i in range(0, mine.shape[0], chunk):
+                _, ctx = engine_render_forward(model, renderer, mine[i:i + chunk])
+                act += int(ctx.M)
+            fl = head_flops_per_active_sample(model)
+            tf = act * world * fl / t_frame / 1e12          # tiles are equal-sized; this rank's active fraction stands for the frame
+            roof = inference_roofline_object(tf, a.dtype, act * world / P, fl)
         print(json.dumps({"metric": "rays/sec (full-frame 1296x968 render, row tiles sharded over the ranks)", "value": P / t_frame,
                           "unit": "rays/s", "n_gpus": world, "steps": a.steps, "warmup": max(1, a.warmup), "ms_per_step": t_frame * 1e3,
                           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": {"fp32": "f32", "fp32x6": "f32"}.get(a.dtype, a.dtype),
@@ -620,11 +678,31 @@ def bench_inference_sharded(a, model, renderer, dev, world, rank, backend):
                                      "rays_per_frame": P, "samples_per_ray": S, "classes": a.classes, "grid": a.grid,
                                      "parallelism": f"row tiles over {world} rank(s), 1 all-gather per frame"},
                           "ray_samples_per_s": P * S / t_frame,
-                          "inference_roofline": inference_roofline_object(tf, a.dtype, act * world / P, fl),
+                          "inference_roofline": roof, "full": a.full,
                           "dist_backend": backend, "rccl_ranks": (dist.get_world_size() if backend == "nccl" else 0),
                           "devices_visible": torch.cuda.device_count()}))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: every array as float32 DIR/<name>.npy.  When they add up to more than DUMP_BUDGET_BYTES, an array larger than its
+    equal share of the budget is cut to a sample of its leading-dimension rows that fits the share: numpy default_rng(0), sorted, so the same
+    arguments give the same rows in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {name: t.detach().to(torch.float32).cpu().numpy() for name, t in arrays.items()}
+    share = DUMP_BUDGET_BYTES // len(host)
+    over = sum(x.nbytes for x in host.values()) > DUMP_BUDGET_BYTES
+    for name, x in host.items():
+        if over and x.nbytes > share:
+            rows = x.shape[0]
+            keep = max(1, share // (x.nbytes // rows))
+            x = x[np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x))
 
 
 def inference_roofline_object(tf, mode, act_per_ray, fl):

@@ -11,7 +11,7 @@ from conftest import REPO
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 
-def test_config_tree_matches_reference_interface():
+def test_config_tree_matches_reference_interface(tmp_path):
     from contrastive_lift_amd.config import load_config, save_config, load_run_config
     c = load_config(os.path.join(REPO, "config"), overrides=["+experiment=contrastive_lift_MOS", "template.lr=1e-3", "dataset_root=/x/scene_1"])
     assert c.dataset_class == "mos" and c.instance_loss_mode == "slow_fast" and c.use_DINO_style is True and c.max_instances == 3
@@ -20,7 +20,7 @@ def test_config_tree_matches_reference_interface():
     assert c.bbox_aabb_reset_epochs == [1, 2, 3] and c.grid_upscale_epochs == [1, 2, 3, 4] and c.late_semantic_optimization == 2
     d = load_config(os.path.join(REPO, "config"))
     assert d.instance_loss_mode == "linear_assignment" and d.max_instances == 25 and d.dataset_class == "panopli"
-    p = os.path.join("/tmp", "clift_cfg_test", "config.yaml")
+    p = str(tmp_path / "clift_cfg_test" / "config.yaml")
     save_config(c, p)
     assert load_run_config(p).dataset_root == "/x/scene_1"
 

@@ -13,7 +13,7 @@ PY
 timeout 900 python -m pytest tests/test_gpu_round3.py -q -m gpu -k "first2 or without_the_first" > $out/pytest_first2.log 2>&1; echo "first2 tests rc=$?" | tee -a $out/summary.txt
 tail -4 $out/pytest_first2.log | tee -a $out/summary.txt
 timeout 300 python tools/first2_bwd_probe.py 2>&1 | tee $out/probe.txt
-timeout 900 python bench.py --no-cpu-baseline > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" | tee -a $out/summary.txt
+timeout 900 python bench.py --full --no-cpu-baseline > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" | tee -a $out/summary.txt
 python - $out/bench.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,6 +8,6 @@ timeout 2400 python -m pytest tests -q -m gpu --timeout 900 --durations=25 > $ou
 echo "pytest gpu rc=$?" | tee -a $out/summary.txt
 tail -6 $out/pytest_gpu.log >> $out/summary.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 >> $out/summary.txt
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench rc=$?" >> $out/summary.txt
 cat $out/summary.txt

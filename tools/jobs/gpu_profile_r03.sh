@@ -19,6 +19,6 @@ for set in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/pmc_parse.py $out/pmc_bench_* 2>/dev/null | grep -v "rocclr\|at::native" > $out/pmc_bench_table.txt
 rm -rf $out/pmc_bench_FETCH_SIZE $out/pmc_bench_WRITE_SIZE
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 echo "bench rc=$?" >> $out/summary.txt
 cat $out/summary.txt; head -30 $out/kernel_stats_fp32.txt

@@ -9,7 +9,7 @@ timeout 2400 python -m pytest tests -q -m gpu --timeout 900 --durations=15 > $ou
 echo "pytest gpu (default fp32x6) rc=$?" | tee -a $out/summary.txt
 tail -n 30 $out/pytest_gpu.log | grep -E "passed|failed|FAILED|ERROR" >> $out/summary.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 1 >> $out/summary.txt
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 echo "bench rc=$? $(python -c "import json;d=json.load(open('$out/bench_default.json'));print(d['ms_per_step'], d['roofline']['frac'], d['roofline']['hbm']['frac'], d.get('exact_fp32_ms_per_step'), d.get('bf16_ms_per_step'), d.get('rays1024_ms_per_step'), d.get('rays8192_ms_per_step'))")" >> $out/summary.txt
 timeout 300 python tools/x6_ends_probe.py 249000 62000 > $out/x6_ends_probe.txt 2>&1
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$out/prof_x6" -o p -- python "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-extras --steps 20 --warmup 3 > "$GRAFT_REPO_ROOT/$out/bench_under_rocprof.json" 2> "$GRAFT_REPO_ROOT/$out/prof_x6.log" )

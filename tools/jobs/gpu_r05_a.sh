@@ -15,8 +15,8 @@ prof() {  # name, command...
   python tools/rocprof_summary.py "$db" $out/kernel_stats_$name.txt
   rm -rf $out/prof_$name
 }
-prof bf16 python "$GRAFT_REPO_ROOT/bench.py" --dtype bf16 --no-cpu-baseline --no-extras --steps 20 --warmup 3
-prof rays1024 python "$GRAFT_REPO_ROOT/bench.py" --rays 1024 --inst-rays 1024 --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof bf16 python "$PWD/bench.py" --full --dtype bf16 --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof rays1024 python "$PWD/bench.py" --full --rays 1024 --inst-rays 1024 --no-cpu-baseline --no-extras --steps 20 --warmup 3
 prof inference python "$GRAFT_REPO_ROOT/tools/inference_probe.py" fp32x6 32768
 for n in bf16 rays1024; do python -c "
 import json; d=json.loads(open('$out/$n.out').read().strip().splitlines()[-1]); print('$n ms_per_step', d['ms_per_step'], 'frac', d['roofline']['frac'])"; done

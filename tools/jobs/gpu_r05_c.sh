@@ -22,9 +22,9 @@ prof() {  # name, command...
   python tools/rocprof_summary.py "$db" $out/kernel_stats_$name.txt
   rm -rf $out/prof_$name
 }
-prof fp32x6 python "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-extras --steps 20 --warmup 3
-prof bf16 python "$GRAFT_REPO_ROOT/bench.py" --dtype bf16 --no-cpu-baseline --no-extras --steps 20 --warmup 3
-prof rays1024 python "$GRAFT_REPO_ROOT/bench.py" --rays 1024 --inst-rays 1024 --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof fp32x6 python "$PWD/bench.py" --full --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof bf16 python "$PWD/bench.py" --full --dtype bf16 --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof rays1024 python "$PWD/bench.py" --full --rays 1024 --inst-rays 1024 --no-cpu-baseline --no-extras --steps 20 --warmup 3
 prof inference python "$GRAFT_REPO_ROOT/tools/inference_probe.py" fp32x6 32768
 bash tools/jobs/gpu_timeline.sh $(basename $out)/tl1024 --rays 1024 --inst-rays 1024 > /dev/null 2>&1; tail -1 $out/tl1024/timeline.txt
 bash tools/jobs/gpu_timeline.sh $(basename $out)/tl1024_nosync --rays 1024 --inst-rays 1024 --nosync > /dev/null 2>&1; tail -1 $out/tl1024_nosync/timeline.txt

@@ -12,9 +12,9 @@ prof() {  # name, command...
   python tools/rocprof_summary.py "$db" $out/kernel_stats_$name.txt
   rm -rf $out/prof_$name
 }
-prof fp32x6 python "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-extras --steps 20 --warmup 3
-prof fp32 python "$GRAFT_REPO_ROOT/bench.py" --dtype fp32 --no-cpu-baseline --no-extras --steps 20 --warmup 3
-prof bf16 python "$GRAFT_REPO_ROOT/bench.py" --dtype bf16 --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof fp32x6 python "$PWD/bench.py" --full --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof fp32 python "$PWD/bench.py" --full --dtype fp32 --no-cpu-baseline --no-extras --steps 20 --warmup 3
+prof bf16 python "$PWD/bench.py" --full --dtype bf16 --no-cpu-baseline --no-extras --steps 20 --warmup 3
 prof inference python "$GRAFT_REPO_ROOT/tools/inference_probe.py" fp32x6 32768
 for n in fp32x6 fp32 bf16; do python -c "
 import json; d=json.loads(open('$out/$n.out').read().strip().splitlines()[-1]); print('$n ms_per_step', d['ms_per_step'], 'median', d.get('step_ms_median'), 'frac', d['roofline']['frac'])"; done

@@ -10,5 +10,5 @@ timeout 300 python tools/x6_fixed_probe.py 0 2>/dev/null | grep -E "X6_ABL|wgrad
 ( cd /tmp && timeout 400 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/$out/pmc" -o p -- python "$GRAFT_REPO_ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-extras > "$GRAFT_REPO_ROOT/$out/pmc.log" 2>&1 )
 python tools/pmc_parse.py $out/pmc/ 2>/dev/null | grep -E "k_wgrad_x6|k_wgrad_n6" > $out/pmc_wgrad_after.txt; rm -rf $out/pmc
 cat $out/pmc_wgrad_after.txt | cut -c1-200
-for i in 1 2; do timeout 300 python bench.py --no-cpu-baseline --no-extras > $out/bench_$i.json 2>/dev/null; python -c "
+for i in 1 2; do timeout 300 python bench.py --full --no-cpu-baseline --no-extras > $out/bench_$i.json 2>/dev/null; python -c "
 import json; d=json.loads(open('$out/bench_$i.json').read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['step_ms_median'], d['roofline']['frac'])"; done
