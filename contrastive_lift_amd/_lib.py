@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIFT_LIB_PATH") or os.path.join(_HERE, "libclift.so")      # (the override: timing probes of variant builds, tools/jobs)
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
@@ -49,7 +49,7 @@ class Gemm(C.Structure):
                 ("a_bf16", C.c_int), ("b_bf16", C.c_int), ("c_bf16", C.c_int), ("mask_bf16", C.c_int), ("sign_bits", C.c_void_p)]
 
 
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
+_P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 _SIGNATURES = {
     "clift_version": ([], C.c_int),
     "clift_set_cu_reserve": ([_I], C.c_int),
@@ -120,6 +120,7 @@ _SIGNATURES = {
     "clift_contrastive": ([_P, _P, _I, _I, _F, _P, _P, _P, _P], C.c_int),
     "clift_slow_fast": ([_P, _P, _P, _I, _I, _P, _P, _P, _P], C.c_int),
     "clift_nearest_centroid": ([_P, _I, _I, _P, _I, _P, _L, _P, _P], C.c_int),
+    "clift_meanshift": ([_P, _L, _I, _I, _P, _I, _D, _I, _P, _P, _P, _P], C.c_int),
     "clift_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P], C.c_int),
     "clift_ema": ([_P, _P, _L, _F, _P], C.c_int),
 }

@@ -1,7 +1,7 @@
 """Inference render loop and post-processing -- mirror of reference inference/render_panopli.py:108-140 (per-frame
 chunked rendering with is_train=False and the halved step ratio), util/camera.py:86-104 (distance_to_depth),
-RP:422-427 (create_instances_from_semantics), RP:371-419 (assign_clusters) and RP:196-263 (MeanShift clustering, which
-stays sklearn on the CPU exactly like the reference).
+RP:422-427 (create_instances_from_semantics), RP:371-419 (assign_clusters) and RP:196-368 (MeanShift clustering: sklearn on the CPU exactly like
+the reference, or DeviceMeanShift with the per-seed climb on the GPU).
 """
 import numpy as np
 import torch
@@ -151,13 +151,98 @@ def _nearest_centroid(points, centroids, device):
     return lab.cpu().numpy().astype(np.int64)
 
 
-def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000, use_silverman=False, use_dbscan=False, cluster_size=500):
+def bin_seeds(X, bin_size, min_bin_freq=1):
+    """sklearn.cluster.get_bin_seeds, vectorised: bins np.round(X / bin_size) (in X's dtype), the bins holding at least ``min_bin_freq``
+    points in order of first occurrence, as fp32 and scaled back by ``bin_size``; X itself when bin_size is 0 or every point is its own bin."""
+    if bin_size == 0:
+        return X
+    binned = np.round(X / bin_size) + 0.0                         # (+ 0.0: -0.0 and 0.0 are one bin, as they are one dict key)
+    uniq, first, freq = np.unique(binned, axis=0, return_index=True, return_counts=True)
+    keep = freq >= min_bin_freq
+    seeds = uniq[keep][np.argsort(first[keep], kind="stable")].astype(np.float32)
+    if len(seeds) == len(X):
+        return X
+    return seeds * bin_size
+
+
+def device_shift(X, seeds, bandwidth, max_iter, device):
+    """clift_meanshift on ``device``: returns (centers (S, d) fp32, counts (S,) int, iters (S,) int) as numpy arrays."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.CliftError(f"DeviceMeanShift: clift_meanshift runs on a GPU device, got {dev}")
+    x = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float32), device=dev)
+    sd = torch.as_tensor(np.ascontiguousarray(seeds, dtype=np.float32), device=dev)
+    S, d = sd.shape
+    centers = torch.empty((S, d), dtype=torch.float32, device=dev)
+    counts = torch.empty((S,), dtype=torch.int32, device=dev)
+    iters = torch.empty((S,), dtype=torch.int32, device=dev)
+    _lib.call("clift_meanshift", _lib.ptr(x), x.shape[0], x.shape[1], d, _lib.ptr(sd), S, float(bandwidth), int(max_iter), _lib.ptr(centers),
+              _lib.ptr(counts), _lib.ptr(iters), _lib.stream())
+    return centers.cpu().numpy(), counts.cpu().numpy().astype(np.int64), iters.cpu().numpy().astype(np.int64)
+
+
+class DeviceMeanShift:
+    """sklearn ``MeanShift(bandwidth, bin_seeding=True, min_bin_freq, cluster_all=False, max_iter)`` with the per-seed climb on the GPU
+    (clift_meanshift: one launch for all seeds).  The host part is sklearn's ``fit``: bin seeding (``bin_seeds``), results with exactly
+    equal centre tuples merged, seeds with an empty neighbourhood dropped (ValueError when none is left), sorted by (count, centre)
+    descending, then near-duplicates within ``bandwidth`` removed with sklearn's NearestNeighbors (the centre with more points stays).
+    ``fit`` sets ``cluster_centers_`` (K, d) fp32 and ``n_iter_``; ``predict`` is the nearest centre (clift_nearest_centroid).
+    X is taken as fp32 (the reference clusters fp32 features).  ``shift_fn(X, seeds, bandwidth, max_iter) -> (centers, counts, iters)``
+    replaces the device climb (CPU tests of the host logic)."""
+
+    def __init__(self, bandwidth, min_bin_freq=10, max_iter=300, device="cuda", shift_fn=None):
+        self.bandwidth, self.min_bin_freq, self.max_iter = float(bandwidth), int(min_bin_freq), int(max_iter)
+        self.device = device
+        self.shift_fn = shift_fn or (lambda X, seeds, bw, it: device_shift(X, seeds, bw, it, self.device))
+
+    def fit(self, X):
+        from sklearn.neighbors import NearestNeighbors
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        bw = self.bandwidth
+        seeds = bin_seeds(X, bw, self.min_bin_freq)
+        centers, counts, iters = self.shift_fn(X, seeds, bw, self.max_iter)
+        centers = np.asarray(centers, dtype=np.float32)
+        intensity = {}
+        for c, n in zip(centers, np.asarray(counts).tolist()):
+            if n:
+                intensity[tuple(c)] = n
+        self.n_iter_ = int(np.max(iters)) if len(iters) else 0
+        if not intensity:
+            raise ValueError(f"No point was within bandwidth={bw:f} of any seed. Try a different seeding strategy or increase the bandwidth.")
+        ranked = sorted(intensity.items(), key=lambda tup: (tup[1], tup[0]), reverse=True)
+        sorted_centers = np.array([tup[0] for tup in ranked])
+        unique = np.ones(len(sorted_centers), dtype=bool)
+        nbrs = NearestNeighbors(radius=bw).fit(sorted_centers)
+        for i, center in enumerate(sorted_centers):
+            if unique[i]:
+                unique[nbrs.radius_neighbors([center], return_distance=False)[0]] = 0
+                unique[i] = 1
+        self.cluster_centers_ = sorted_centers[unique]
+        return self
+
+    def predict(self, X):
+        return _nearest_centroid(np.asarray(X, dtype=np.float32), self.cluster_centers_, self.device)
+
+
+def _meanshift(pts, bandwidth, meanshift, device):
+    """The reference's MeanShift(bandwidth, cluster_all=False, bin_seeding=True, min_bin_freq=10) fit: sklearn on the CPU ("sklearn") or
+    DeviceMeanShift ("device")."""
+    if meanshift == "sklearn":
+        from sklearn.cluster import MeanShift
+        return MeanShift(bandwidth=bandwidth, cluster_all=False, bin_seeding=True, min_bin_freq=10).fit(pts)
+    if meanshift == "device":
+        return DeviceMeanShift(bandwidth, min_bin_freq=10, device=device).fit(pts)
+    raise ValueError(f"meanshift must be 'sklearn' or 'device' (got {meanshift!r})")
+
+
+def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000, use_silverman=False, use_dbscan=False, cluster_size=500,
+            meanshift="sklearn"):
     """RP:196-263: 3-sigma outlier filter, per-axis rescale to the
     unit box, a 50000-point subsample drawn with ``np.random.choice`` from numpy's GLOBAL generator exactly as the reference
     does (seed it with ``np.random.seed`` for reproducible runs), sklearn MeanShift (optionally with Silverman's bandwidth) or, with
     ``use_dbscan``, HDBSCAN (``_hdbscan_fit``), then every pixel is assigned to its nearest cluster.  Returns (one-hot (num_images, P, K+1) float64, centroids in feature
-    units).  Scenes with fewer thing pixels than ``num_points`` use all of them (the reference raises there)."""
-    from sklearn.cluster import MeanShift
+    units).  Scenes with fewer thing pixels than ``num_points`` use all of them (the reference raises there).  ``meanshift="device"`` runs
+    the MeanShift fit as DeviceMeanShift (GPU) instead of sklearn."""
     feats = np.asarray(all_thing_features)
     thing = feats[..., 0] == -float("inf")
     f_th = feats[thing][:, 1:]
@@ -179,7 +264,7 @@ def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000,
             raise _lib.CliftError("HDBSCAN found no cluster (every sampled point is noise); the reference fails here too (np.stack of an empty list)")
         all_labels = _nearest_centroid((f_all.reshape(-1, f_all.shape[-1]) - bias) * factor, centers, device)
     else:
-        ms = MeanShift(bandwidth=bandwidth, cluster_all=False, bin_seeding=True, min_bin_freq=10).fit(pts)
+        ms = _meanshift(pts, bandwidth, meanshift, device)
         all_labels = ms.predict((f_all.reshape(-1, f_all.shape[-1]) - bias) * factor)
         centers = ms.cluster_centers_
     all_labels[~thing] = -1
@@ -191,13 +276,15 @@ def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000,
 
 
 def cluster_segmentwise(all_thing_features, all_points_semantics, bandwidth, device, num_images, num_points=50000, use_silverman=False,
-                        use_dbscan=False, cluster_size=500):
+                        use_dbscan=False, cluster_size=500, meanshift="sklearn", return_dict=False):
     """RP:265-368: the clustering of ``cluster`` (MeanShift, or HDBSCAN with ``use_dbscan``) run separately inside every predicted thing class, labels of
     successive classes offset so they stay disjoint; classes with fewer than 100 (filtered) points get no instances (-1).
     Returns (one-hot (num_images, P, max label + 2) float64, concatenated centroids in feature units).  Like the reference,
     a class that is skipped for having too few points still appends the previous class's centroids (rescaled with its own
-    statistics) to the returned list -- only the one-hot output is consumed by the render script."""
-    from sklearn.cluster import MeanShift
+    statistics) to the returned list -- only the one-hot output is consumed by the render script.  ``meanshift="device"`` runs the fits
+    as DeviceMeanShift.  With ``return_dict`` the centroids come back as the reference's per-class cache (extract_train_centroids.py:211-313):
+    ``{thing class (np.int64): centroids in feature units}``, incl. that stale entry for a skipped class; this is the mapping that
+    ``assign_clusters`` (--cached_centroids_path) reads."""
     sem = torch.cat([s_.cpu() for s_ in all_points_semantics], 0).argmax(-1).numpy()
     feats = np.asarray(all_thing_features)
     thing = feats[..., 0] == -float("inf")
@@ -207,7 +294,7 @@ def cluster_segmentwise(all_thing_features, all_points_semantics, bandwidth, dev
     all_labels = np.zeros(n_all, dtype=np.int32)
     th_labels = np.zeros(f_th.shape[0], dtype=np.int32)
     max_label = 0
-    cents_all, centroids = [], None
+    cents_all, cents_by_cls, centroids = [], {}, None
     for cls in np.unique(th_sem):
         m = th_sem == cls
         fc = f_th[m]
@@ -235,11 +322,12 @@ def cluster_segmentwise(all_thing_features, all_points_semantics, bandwidth, dev
             if use_silverman:
                 from scipy.stats import gaussian_kde
                 bw = gaussian_kde(pts.T, bw_method="silverman").covariance_factor()
-            ms = MeanShift(bandwidth=bw, cluster_all=False, bin_seeding=True, min_bin_freq=10).fit(pts)
+            ms = _meanshift(pts, bw, meanshift, device)
             centroids = ms.cluster_centers_
             lab = ms.predict((fc.reshape(-1, fc.shape[-1]) - bias) * factor)
         if centroids is not None:
             cents_all.append(centroids / factor + bias)
+            cents_by_cls[cls] = cents_all[-1]
         lab[lab != -1] += max_label
         if np.any(lab != -1):
             max_label = lab.max() + 1
@@ -247,6 +335,8 @@ def cluster_segmentwise(all_thing_features, all_points_semantics, bandwidth, dev
     all_labels[thing] = th_labels
     all_labels[~thing] = -1
     onehot = _one_hot(torch.as_tensor(all_labels, dtype=torch.int64, device=device), num_images, device)
+    if return_dict:
+        return onehot, cents_by_cls
     return onehot, (np.concatenate(cents_all, axis=0) if cents_all else np.zeros((0, f_th.shape[1])))
 
 

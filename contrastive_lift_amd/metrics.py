@@ -25,6 +25,12 @@ def _non_robust(sem_pred, sem_tgt, thr):
 
 def panoptic_quality(preds, target, things, stuff, allow_unknown_preds_category=False, robust=0.005):
     """preds, target: (..., 2) integer [category, instance].  Returns (pq, sq, rq) as 0-dim float64 tensors."""
+    return panoptic_quality_compute(*panoptic_quality_match(preds, target, things, stuff, allow_unknown_preds_category, robust))
+
+
+def panoptic_quality_match(preds, target, things, stuff, allow_unknown_preds_category=False, robust=0.005):
+    """The matching half of ``panoptic_quality`` (util/panoptic_quality.py:250-268): returns (things, stuff, iou_sum, tp, fp, fn) -- the
+    categories kept after the robust-class filter and the per-category vectors (things first), float64 numpy arrays."""
     p = _np(preds).reshape(-1, 2).astype(np.int64).copy()
     t = _np(target).reshape(-1, 2).astype(np.int64).copy()
     if p.shape != t.shape:
@@ -85,6 +91,13 @@ def panoptic_quality(preds, target, things, stuff, allow_unknown_preds_category=
         if up[a] == void_key or p_void_t[a] / ap[a] > 0.5:
             continue
         fp[cid[int(up[a] // base)]] += 1
+    return things, stuff, iou_sum, tp, fp, fn
+
+
+def panoptic_quality_compute(things, stuff, iou_sum, tp, fp, fn):
+    """The scoring half (util/panoptic_quality.py:177-222, "all"): per-category PQ / SQ / RQ averaged over every entry of the vectors.
+    Returns (pq, sq, rq) as 0-dim float64 tensors (NaN for empty vectors)."""
+    iou_sum, tp, fp, fn = (np.asarray(v, dtype=np.float64) for v in (iou_sum, tp, fp, fn))
     den = tp + 0.5 * fp + 0.5 * fn
     with np.errstate(divide="ignore", invalid="ignore"):
         pq = np.where(den > 0, iou_sum / den, 0.0)
@@ -92,3 +105,28 @@ def panoptic_quality(preds, target, things, stuff, allow_unknown_preds_category=
         rq = np.where(den > 0, tp / den, 0.0)
     f = lambda v: torch.tensor(float(np.mean(v)) if len(v) else float("nan"), dtype=torch.float64)
     return f(pq), f(sq), f(rq)
+
+
+def panoptic_quality_per_frame(sem_pred, inst_pred, sem_target, inst_target, is_thing, faulty_gt=()):
+    """PQ of a set of frames scored frame by frame, as the reference's bandwidth search does it (inference/find_bandwidth.py:314-376,
+    MY_calculate_panoptic_quality_per_frame_folders[_MOS]): per frame, target pixels whose class is in ``faulty_gt`` are dropped, every
+    thing class of the target becomes the first thing class, and the frame is matched on its own (``panoptic_quality_match`` with unknown
+    predicted categories allowed); the per-category vectors of all frames are concatenated and averaged (not a scene aggregate).
+    Arguments are dicts {frame name: (H, W) integer image} keyed alike (names are numeric stems, taken in numeric order).
+    Returns (pq, sq, rq) floats."""
+    things = set(i for i, t in enumerate(is_thing) if t)
+    stuff = set(i for i, t in enumerate(is_thing) if not t)
+    first_thing = list(things)[0]
+    parts = [[], [], [], []]
+    for name in sorted(sem_pred, key=lambda x: int(str(x).split(".")[0])):
+        ts = np.asarray(sem_target[name])
+        valid = ~np.isin(ts, list(faulty_gt))
+        ts = ts[valid].astype(np.int64)
+        ts = np.where(np.isin(ts, list(things)), first_thing, ts)
+        pred = np.stack([np.asarray(sem_pred[name])[valid], np.asarray(inst_pred[name])[valid]], -1).astype(np.int64)
+        tgt = np.stack([ts, np.asarray(inst_target[name])[valid]], -1).astype(np.int64)
+        m = panoptic_quality_match(pred, tgt, things, stuff, True)
+        for j in range(4):
+            parts[j].append(m[2 + j])
+    pq, sq, rq = panoptic_quality_compute(things, stuff, *(np.concatenate(p_) for p_ in parts))
+    return float(pq), float(sq), float(rq)

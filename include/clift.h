@@ -453,6 +453,17 @@ int clift_slow_fast(const float* inst, const int* labels, const float* conf, int
 int clift_nearest_centroid(const float* feat, int ldf, int E, const float* centroids, int K, const unsigned char* valid,
                            long n, int* labels, clift_stream_t s);
 
+/* ---- mean-shift (ABI 19): the per-seed climb of sklearn MeanShift.fit (sklearn/cluster/_mean_shift.py, _mean_shift_single_seed), which the
+ * reference runs for every clustering of rendered instance features (inference/render_panopli.py:196-368).  X (n, ldx) fp32 points,
+ * seeds (S, d) fp32.  For every seed, until the fp32 norm of the step is <= 1e-3 * bandwidth or max_iter steps were completed:
+ * neighbours = the points with sum_k (double(x_k) - double(m_k))^2 <= bandwidth^2 (fp64, dimension order), m = fp32(fp64 neighbour
+ * sum / count).  Writes centers (S, d) (the last mean), counts (S) (neighbours of the last step; 0 = empty neighbourhood, the centre is
+ * then the last mean reached) and iters (S) (completed iterations).  The sum runs over a fixed split of the points, so the centre depends
+ * only on the neighbour set (bit-identical for two seeds that end on the same set).  1 <= d <= 32 (larger d is an error), ldx >= d,
+ * n < 2^31, bandwidth > 0, max_iter >= 0. */
+int clift_meanshift(const float* X, long n, int ldx, int d, const float* seeds, int S, double bandwidth, int max_iter,
+                    float* centers, int* counts, int* iters, clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,

@@ -80,7 +80,8 @@ def glasbey(n):
 
 
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
-                              cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500):
+                              cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
+                              meanshift="sklearn"):
     out = output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise)
     out.mkdir(exist_ok=True, parents=True)
     # launched under torch.distributed.run: one process per GPU, every frame rendered as row-tiles (one per rank) and
@@ -135,10 +136,10 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
     else:
         if not segmentwise:
             insts, _ = inf.cluster(all_thing, bandwidth, device, num_images=len(rgbs), use_silverman=use_silverman, use_dbscan=use_dbscan,
-                                   cluster_size=cluster_size)
+                                   cluster_size=cluster_size, meanshift=meanshift)
         else:
             insts, _ = inf.cluster_segmentwise(all_thing, sems, bandwidth, device, num_images=len(rgbs), use_silverman=use_silverman,
-                                               use_dbscan=use_dbscan, cluster_size=cluster_size)
+                                               use_dbscan=use_dbscan, cluster_size=cluster_size, meanshift=meanshift)
     for d in ("vis_semantics_and_surrogate", "pred_semantics", "pred_surrogateid"):
         (out / d).mkdir(exist_ok=True)
     for j, frame_name in enumerate(names):
@@ -169,6 +170,8 @@ if __name__ == "__main__":
     ap.add_argument("--use_silverman", action="store_true")
     ap.add_argument("--cached_centroids_path", type=str, required=False)
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="reference hard-codes [256, 384] (RP:450)")
+    ap.add_argument("--meanshift", choices=("sklearn", "device"), default="sklearn",
+                    help="where the MeanShift fits run: sklearn on the CPU (the reference) or the GPU (DeviceMeanShift)")
     args = ap.parse_args()
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
@@ -177,4 +180,4 @@ if __name__ == "__main__":
     print(render_panopli_checkpoint(cfg, "trajectory_blender", test_only=not args.render_trajectory, bandwidth=args.bandwidth,
                                     use_dbscan=args.use_dbscan, segmentwise=args.segmentwise,
                                     cached_centroids_path=args.cached_centroids_path, use_silverman=args.use_silverman,
-                                    cluster_size=args.cluster_size))
+                                    cluster_size=args.cluster_size, meanshift=args.meanshift))
