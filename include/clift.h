@@ -464,6 +464,30 @@ int clift_nearest_centroid(const float* feat, int ldf, int E, const float* centr
 int clift_meanshift(const float* X, long n, int ldx, int d, const float* seeds, int S, double bandwidth, int max_iter,
                     float* centers, int* counts, int* iters, clift_stream_t s);
 
+/* ---- instances in 3-D (ABI 20; csrc/points3d.hip): the per-instance steps of the reference's inference/visualize_bboxes.py (filter_pointcloud
+ * :52-74, get_tight_bbox :78-131) for ALL instances of a scene per launch.  pts (n, 3) fp32, rows SORTED BY INSTANCE; seg (G + 1) int64 device
+ * offsets, non-decreasing, 0 <= seg[g] <= n: instance g owns rows seg[g] .. seg[g+1] (may be empty).  n < 2^31 - 1024.  Entries of seg outside
+ * [0, n] are clamped, never followed.
+ *
+ * clift_knn_kth_dist: d2_out[i] (n) fp64 = the SQUARED distance from row i to its k-th nearest row of the same instance, itself included
+ * (sklearn.neighbors.KDTree(P).query(P, k)[0][:, -1], squared).  The distance of rows a, b is ((dx*dx + dy*dy) + dz*dz) with
+ * dx = double(a.x) - double(b.x) (likewise dy, dz), every product and sum rounded separately to fp64 (no contraction) -- the number sklearn's
+ * fp64 KD-tree computes; the k smallest of these do not depend on the order the candidates are visited in.  1 <= k <= 16.  Every row of an
+ * instance with fewer than k rows gets +inf (the KD-tree raises there), and so does a row outside [seg[0], seg[G]). */
+int clift_knn_kth_dist(const float* pts, long n, const long* seg, int G, int k, double* d2_out, clift_stream_t s);
+/* clift_segment_moments: out (G, 10) fp64, per instance over its rows i with keep[i] != 0 (keep (n) uint8; NULL = all rows), with
+ * q = double(p) - centre[g] (centre (G, 3) fp64; NULL = zero):  count, sum qx, qy, qz, sum qx*qx, qx*qy, qx*qz, qy*qy, qy*qz, qz*qz.
+ * fp64, every product and sum rounded separately, over a FIXED split of the instance's rows (row seg[g] + t + 256 j on thread t in order of j,
+ * 64 threads folded by an xor butterfly, the four partials added in order): no atomics, two runs give the same bits.  An instance without
+ * kept rows gets zeros.  (Two calls -- centre = NULL for the mean, then centre = mean -- give centred second moments without cancellation.) */
+int clift_segment_moments(const float* pts, long n, const long* seg, int G, const unsigned char* keep, const double* centre, double* out,
+                          clift_stream_t s);
+/* clift_segment_extent: frame (G, 12) fp64 = the 3 x 3 axes A row-major, then the centre c.  out (G, 6) fp64 = per instance the minimum
+ * (3) and the maximum (3), over its kept rows, of  v_r = ((A[r][0]*qx + A[r][1]*qy) + A[r][2]*qz),  q = double(p) - c, rounded as above.
+ * An instance without kept rows gets +inf / -inf. */
+int clift_segment_extent(const float* pts, long n, const long* seg, int G, const unsigned char* keep, const double* frame, double* out,
+                         clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,

@@ -8,7 +8,9 @@ Reads ``runs/<experiment>/config.yaml`` next to the checkpoint (RP:445), rebuild
 renderer buffers, upsamples to the checkpoint's grid if it was saved after an upscale epoch (RP:91-98), loads the weights,
 halves the step ratio (RP:104) and renders every test frame in chunks on the GPU.  Writes ``instance_features.npy``,
 ``thing_features.npy``, ``slow_features.npy``, ``pred_semantics/*.png`` (uint8), ``pred_surrogateid/*.png`` (uint16) and
-``vis_semantics_and_surrogate/*.png`` under ``runs/<scene>_<test|trajectory>_<experiment>/`` (RP:142-193).
+``vis_semantics_and_surrogate/*.png`` under ``runs/<scene>_<test|trajectory>_<experiment>/`` (RP:142-193).  With ``--save_pointcloud``
+also ``pointcloud.pkl``: every rendered pixel back-projected along its ray (RP:124) with its surrogate id, the input of
+``inference/fit_bboxes.py`` and of the reference's ``inference/visualize_bboxes.py``.
 """
 import argparse
 import os
@@ -24,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import contrastive_lift_amd as cl                                   # noqa: E402
 from contrastive_lift_amd import inference as inf                    # noqa: E402
+from contrastive_lift_amd import points3d                            # noqa: E402
 from contrastive_lift_amd.config import load_run_config              # noqa: E402
 from contrastive_lift_amd.data import get_scene                       # noqa: E402
 
@@ -81,7 +84,7 @@ def glasbey(n):
 
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
                               cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
-                              meanshift="sklearn"):
+                              meanshift="sklearn", save_pointcloud=False):
     out = output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise)
     out.mkdir(exist_ok=True, parents=True)
     # launched under torch.distributed.run: one process per GPU, every frame rendered as row-tiles (one per rank) and
@@ -100,7 +103,7 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
     model, renderer, _ = build_from_checkpoint(config, scene, device)
     renderer.update_step_ratio(renderer.step_ratio * 0.5)                                    # RP:104
     fg = scene.segmentation_data.fg_classes
-    rgbs, sems, depths, inst_feats, thing_feats, slow_feats = [], [], [], [], [], []
+    rgbs, sems, depths, inst_feats, thing_feats, slow_feats, points = [], [], [], [], [], [], []
     # RP:67-72: the test split, or the predefined trajectory trajectories/<trajectory_name>.pkl (frames named by index, all
     # with the intrinsics of frame 0)
     if test_only:
@@ -113,6 +116,8 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
             names.append(name)
             p_rgb, p_sem, p_inst, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg)
             depths.append(inf.distance_to_depth(K_frame, p_dist.view(H, W)))
+            if save_pointcloud:
+                points.append(points3d.backproject(rays, p_dist).float().cpu())
             if config.use_delta:
                 p_inst = p_inst + (rays[:, 0:3] + p_dist[:, None] * rays[:, 3:6])
             if model.slow_fast_mode:
@@ -153,6 +158,14 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
         d = (d - d.min()) / max(float(np.ptp(d)), 1e-8)
         vis = np.concatenate([rgbs[j].reshape(H, W, 3).cpu().numpy(), pal[sem_id], pal[sur_id], np.repeat(d[..., None], 3, -1)], 1)
         Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_semantics_and_surrogate" / name)
+    if save_pointcloud:
+        # the layout visualize_bboxes.py:269-275 loads: points (P, 3), instances (P,) = the ids written to pred_surrogateid (0 = stuff)
+        cloud = {"points": torch.cat(points, 0).numpy().astype(np.float32),
+                 "instances": torch.cat([i.argmax(dim=1) for i in insts], 0).cpu().numpy().astype(np.uint16),
+                 "semantics": torch.cat([s.argmax(dim=1) for s in sems], 0).cpu().numpy().astype(np.uint8),
+                 "rgb": (torch.cat(rgbs, 0).cpu().numpy().clip(0, 1) * 255).astype(np.uint8)}
+        with open(out / "pointcloud.pkl", "wb") as f:
+            pickle.dump(cloud, f)
     return out
 
 
@@ -172,6 +185,8 @@ if __name__ == "__main__":
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="reference hard-codes [256, 384] (RP:450)")
     ap.add_argument("--meanshift", choices=("sklearn", "device"), default="sklearn",
                     help="where the MeanShift fits run: sklearn on the CPU (the reference) or the GPU (DeviceMeanShift)")
+    ap.add_argument("--save_pointcloud", action="store_true",
+                    help="also write pointcloud.pkl (points, instances, semantics, rgb of every rendered pixel) for inference/fit_bboxes.py")
     args = ap.parse_args()
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
@@ -180,4 +195,5 @@ if __name__ == "__main__":
     print(render_panopli_checkpoint(cfg, "trajectory_blender", test_only=not args.render_trajectory, bandwidth=args.bandwidth,
                                     use_dbscan=args.use_dbscan, segmentwise=args.segmentwise,
                                     cached_centroids_path=args.cached_centroids_path, use_silverman=args.use_silverman,
-                                    cluster_size=args.cluster_size, meanshift=args.meanshift))
+                                    cluster_size=args.cluster_size, meanshift=args.meanshift,
+                                    save_pointcloud=args.save_pointcloud))
