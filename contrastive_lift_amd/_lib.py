@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIFT_LIB_PATH") or os.path.join(_HERE, "libclift.so")      # (the override: timing probes of variant builds, tools/jobs)
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
@@ -53,6 +53,10 @@ _P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 _SIGNATURES = {
     "clift_version": ([], C.c_int),
     "clift_set_cu_reserve": ([_I], C.c_int),
+    "clift_set_switches": ([C.c_uint], C.c_uint),
+    "clift_get_switches": ([], C.c_uint),
+    "clift_gemm_route": ([_P], C.c_int),
+    "clift_gemm_route_name": ([_I], C.c_char_p),
     "clift_segment_loss": ([_P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _I, _P], C.c_int),
     "clift_gemm_workspace_bytes": ([_I, _I], C.c_long),
     "clift_out_layer_fwd": ([_P, _I, _P, _I, _P, _I, _I, _P, _I, _I, _P], C.c_int),
@@ -168,6 +172,20 @@ def load():
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+_gemm_routes = None
+
+
+def gemm_routes():
+    """{name: value} of clift_gemm_route_t (include/clift.h), read from the library."""
+    global _gemm_routes
+    if _gemm_routes is None:
+        lib, _gemm_routes, r = load(), {}, 0
+        while lib.clift_gemm_route_name(r) != b"INVALID":
+            _gemm_routes[lib.clift_gemm_route_name(r).decode()] = r
+            r += 1
+    return _gemm_routes
 
 
 def ptr(t):

@@ -11,6 +11,9 @@
 void clift_set_error(const char* fmt, ...);
 int clift_check_launch(const char* what);
 int clift_persistent_cus();      // blocks of a one-block-per-CU persistent launch: 256 - clift_set_cu_reserve()
+unsigned clift_switches();       // the kernel-switch word (core.hip; CLIFT_SWITCH_* of clift.h)
+// true when none of the given switches is set: clift_switch_off(CLIFT_SWITCH_TILED_ONLY) = "persistent kernels allowed"
+static inline bool clift_switch_off(unsigned bits) { return (clift_switches() & bits) == 0; }
 
 #define CLIFT_REQUIRE(cond, ...)              \
     do {                                      \

@@ -1,6 +1,8 @@
 // core.hip -- ABI version and error plumbing of libclift.so.
 #include "clift_dev.h"
 #include <stdarg.h>
+#include <stdlib.h>
+#include <string.h>
 
 static thread_local char g_err[512] = "";
 
@@ -20,7 +22,34 @@ int clift_check_launch(const char* what) {
     return 0;
 }
 
-extern "C" int clift_version(void) { return 20; }
+extern "C" int clift_version(void) { return 21; }
+
+// Kernel switches (clift.h, CLIFT_SWITCH_*): one word of host state, seeded from the environment on first use -- the library's only read of
+// the environment -- and changed at run time through clift_set_switches.  Kernel files read it through clift_switch_off (clift_dev.h).
+static unsigned switches_from_env() {
+    static const struct { const char* name; const char* value; unsigned bit; } vars[] = {
+        {"CLIFT_NO_PERSISTENT", nullptr, CLIFT_SWITCH_TILED_ONLY},          // (set to anything)
+        {"CLIFT_X6_TILED", nullptr, CLIFT_SWITCH_X6_TILED},
+        {"CLIFT_DENS_FWD", "thread", CLIFT_SWITCH_DENS_FWD_THREAD},
+        {"CLIFT_DENS_SCATTER", "walk", CLIFT_SWITCH_DENS_SCATTER_WALK}};
+    unsigned w = 0;
+    for (const auto& v : vars) {
+        const char* e = getenv(v.name);
+        if (e && (!v.value || strcmp(e, v.value) == 0)) w |= v.bit;
+    }
+    return w;
+}
+static unsigned& switch_word() {
+    static unsigned w = switches_from_env();
+    return w;
+}
+unsigned clift_switches() { return switch_word(); }
+extern "C" unsigned clift_get_switches(void) { return switch_word(); }
+extern "C" unsigned clift_set_switches(unsigned word) {
+    const unsigned prev = switch_word();
+    switch_word() = word & CLIFT_SWITCH_ALL;
+    return prev;
+}
 
 // Data-parallel runs: while an asynchronous RCCL all-reduce is in flight the persistent launches (one block per CU, held for the whole
 // launch) leave `k` CUs to the collective's kernels.  Host state of the calling process; takes effect at the next launch.

@@ -212,108 +212,202 @@ static int launch_gemm(const GemmP& p, int a_trans, int b_trans, int splits, hip
 
 extern "C" long clift_gemm_workspace_bytes(int N, int K) { return clift_gemm_split_workspace_bytes(N, K); }
 
-extern "C" int clift_gemm(const clift_gemm_t* h, clift_stream_t s) {
-    CLIFT_REQUIRE(h->M >= 0 && h->N >= 0 && h->K >= 0, "clift_gemm: negative dimension");
-    if (h->M == 0 || h->N == 0) return 0;
-    CLIFT_REQUIRE((h->a_bf16 || h->lda % 4 == 0) && (h->b_bf16 || h->ldb % 4 == 0), "clift_gemm: lda/ldb of fp32 operands must be multiples of 4 (got %d, %d)", h->lda, h->ldb);
-    CLIFT_REQUIRE(((uintptr_t)h->A & 15) == 0 && ((uintptr_t)h->B & 15) == 0, "clift_gemm: A/B must be 16-byte aligned");
+// ---- routing: which kernel a descriptor runs on.  Host arithmetic on the descriptor and the switch word (clift_dev.h) only: no data pointer is
+// dereferenced, nothing is launched.  Order matters: the first route whose predicate holds is taken.
+#define ROUTE_REQUIRE(cond, ...)                 \
+    do {                                         \
+        if (!(cond)) {                           \
+            clift_set_error(__VA_ARGS__);        \
+            return CLIFT_GEMM_ROUTE_INVALID;     \
+        }                                        \
+    } while (0)
+
+// *kper = the k range of one blockIdx.z slice of the tiled kernels
+static int gemm_route(const clift_gemm_t* h, int* kper_out) {
+    const bool persistent = clift_switch_off(CLIFT_SWITCH_TILED_ONLY), x6_persistent = clift_switch_off(CLIFT_SWITCH_X6_TILED);
+    // -- argument checks
+    ROUTE_REQUIRE(h->M >= 0 && h->N >= 0 && h->K >= 0, "clift_gemm: negative dimension");
+    if (h->M == 0 || h->N == 0) return CLIFT_GEMM_ROUTE_NONE;
+    ROUTE_REQUIRE((h->a_bf16 || h->lda % 4 == 0) && (h->b_bf16 || h->ldb % 4 == 0), "clift_gemm: lda/ldb of fp32 operands must be multiples of 4 (got %d, %d)", h->lda, h->ldb);
+    ROUTE_REQUIRE(((uintptr_t)h->A & 15) == 0 && ((uintptr_t)h->B & 15) == 0, "clift_gemm: A/B must be 16-byte aligned");
     int splits = h->split_k > 1 ? h->split_k : 1;
-    CLIFT_REQUIRE(splits == 1 || h->accumulate, "clift_gemm: split_k > 1 requires accumulate");
-    CLIFT_REQUIRE(splits == 1 || (!h->bias && !h->act && !h->mask), "clift_gemm: split_k > 1 excludes bias/act/mask");
-    CLIFT_REQUIRE(!h->colsum || h->a_trans, "clift_gemm: colsum requires a_trans (wgrad form)");
+    ROUTE_REQUIRE(splits == 1 || h->accumulate, "clift_gemm: split_k > 1 requires accumulate");
+    ROUTE_REQUIRE(splits == 1 || (!h->bias && !h->act && !h->mask), "clift_gemm: split_k > 1 excludes bias/act/mask");
+    ROUTE_REQUIRE(!h->colsum || h->a_trans, "clift_gemm: colsum requires a_trans (wgrad form)");
+    ROUTE_REQUIRE(!h->sign_bits || (h->precision == 2 && !h->a_trans && h->N == 256 && h->K == 256 && splits == 1 && !h->accumulate && !h->c_trans &&
+                                    h->lda % 4 == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && x6_persistent &&
+                                    ((!h->b_trans && !h->mask) || (h->b_trans && !h->mask && !h->bias && h->act == 0))),
+                  "clift_gemm: sign_bits goes with the persistent fp32x6 256 x 256 forms only (forward: written; dgrad with mask = NULL: read)");
+    ROUTE_REQUIRE(h->precision == 1 || !(h->a_bf16 || h->b_bf16 || h->c_bf16 || h->mask_bf16),
+                  "clift_gemm: bf16-stored tensors (a/b/c/mask_bf16) are only supported with precision 1");
+    ROUTE_REQUIRE(!h->c_bf16 || (!h->accumulate && !h->c_trans), "clift_gemm: a bf16-stored output cannot be accumulated into or transposed");
+    int kper = cdiv(cdiv(h->K, splits), BK) * BK;
+    if (kper < BK) kper = BK;
+    splits = cdiv(h->K, kper);
+    if (splits < 1) splits = 1;
+    *kper_out = kper;
+    ROUTE_REQUIRE(h->precision >= 0 && h->precision <= 2, "clift_gemm: precision must be 0 (fp32), 1 (bf16 operands) or 2 (fp32x6 split), got %d", h->precision);
+
+    // -- precision 1: bf16 operands (gemm_bf16.hip, layer_bf16.hip, layer_nb16.hip)
+    if (h->precision == 1) {
+        const int a_trans = h->a_trans, b_trans = h->b_trans;
+        // storage combinations that exist: streamed operands bf16-stored together (A; and B exactly in the wgrad form), weights fp32
+        ROUTE_REQUIRE(!h->b_bf16 || (h->a_bf16 && a_trans && b_trans), "clift_gemm(bf16): a bf16-stored B needs the wgrad form with a bf16-stored A");
+        ROUTE_REQUIRE(!(h->a_bf16 && a_trans && b_trans) || h->b_bf16, "clift_gemm(bf16): the wgrad form takes both streamed operands bf16-stored or neither");
+        if (!a_trans && h->N == 256 && h->K == 256 && h->M >= 64 && h->a_bf16 && h->c_bf16 && splits == 1 && !h->accumulate && !h->c_trans &&
+            h->lda % 8 == 0 && h->ldc % 8 == 0 && ((((uintptr_t)h->A) | ((uintptr_t)h->C)) & 15) == 0 && h->ldb % 4 == 0 && (((uintptr_t)h->B) & 15) == 0 &&
+            (b_trans ? (h->mask && h->mask_bf16 && !h->bias && h->act == 0 && h->ldmask % 8 == 0 && (((uintptr_t)h->mask) & 15) == 0) : !h->mask))
+            return CLIFT_GEMM_ROUTE_LAYER_BF16;                      // streamed hidden layer: persistent blocks, weights in registers
+        if (a_trans && b_trans && h->M == 256 && h->N == 256 && h->K >= 64 && h->a_bf16 && h->b_bf16 && h->accumulate && !h->c_trans && !h->bias && !h->mask &&
+            h->lda % 8 == 0 && h->ldb % 8 == 0 && ((((uintptr_t)h->A) | ((uintptr_t)h->B)) & 15) == 0)
+            return CLIFT_GEMM_ROUTE_WGRAD_BF16;                      // streamed weight gradient: persistent blocks, transposed LDS reads
+        if (!a_trans && b_trans && !h->a_bf16 && !h->b_bf16 && h->c_bf16 && h->mask && h->mask_bf16 && h->N == 256 && h->K <= 32 && h->K <= h->lda && h->lda <= 32 &&
+            h->lda % 4 == 0 && h->M >= 4096 && splits == 1 && !h->accumulate && !h->c_trans && !h->bias && h->act == 0 && h->ldc % 4 == 0 && h->ldmask % 4 == 0 &&
+            ((((uintptr_t)h->C) | ((uintptr_t)h->mask)) & 7) == 0 && persistent)
+            return CLIFT_GEMM_ROUTE_DGRAD_NARROW_BF16;               // output-layer dgrad with bf16-stored mask / result (fp32 products: exact)
+        // the 128-wide appearance MLP with bf16-stored streams (layer_nb16.hip): forward K = 160 / 128 -> 128 (bias, ReLU), masked input gradient
+        // 128 -> 128, unmasked input gradient 128 -> 160 (bf16- or fp32-stored result), weight gradients 128 x {128, 160}
+        if (!a_trans && h->a_bf16 && splits == 1 && !h->accumulate && !h->c_trans && h->lda % 8 == 0 && h->lda >= h->K && (((uintptr_t)h->A) & 15) == 0 &&
+            h->ldb % 4 == 0 && (((uintptr_t)h->B) & 15) == 0 && (((uintptr_t)h->C) & 15) == 0 && h->M >= 64 && persistent) {
+            const bool fwd = !b_trans && h->N == 128 && (h->K == 128 || h->K == 160) && h->c_bf16 && h->ldc % 8 == 0 && h->ldc >= 128 && !h->mask && h->ldb >= h->K;
+            const bool dg_m = b_trans && h->N == 128 && h->K == 128 && h->c_bf16 && h->ldc % 8 == 0 && h->ldc >= 128 && h->mask && h->mask_bf16 && h->ldmask % 8 == 0 &&
+                              h->ldmask >= 128 && (((uintptr_t)h->mask) & 15) == 0 && !h->bias && h->act == 0 && h->ldb >= 128;
+            const bool dg_u = b_trans && h->N == 160 && h->K == 128 && !h->mask && !h->bias && h->act == 0 && h->ldb >= 160 && h->ldc >= 160 &&
+                              (h->c_bf16 ? h->ldc % 8 == 0 : h->ldc % 4 == 0);
+            if (fwd || dg_m || dg_u) return CLIFT_GEMM_ROUTE_LAYER_NB16;
+        }
+        if (a_trans && b_trans && h->M == 128 && (h->N == 128 || h->N == 160) && h->K >= 64 && h->a_bf16 && h->b_bf16 && h->accumulate && !h->c_trans && !h->bias && !h->mask &&
+            h->lda % 8 == 0 && h->lda >= 128 && h->ldb % 8 == 0 && h->ldb >= h->N && h->ldc >= h->N && ((((uintptr_t)h->A) | ((uintptr_t)h->B)) & 15) == 0 &&
+            persistent)
+            return CLIFT_GEMM_ROUTE_WGRAD_NB16;
+        // the tiled kernel's (a_trans, !b_trans) form has no instantiation for a bf16-stored A
+        ROUTE_REQUIRE(!(h->a_bf16 && a_trans && !b_trans), "clift_gemm(bf16): a bf16-stored transposed A needs the wgrad form (b_trans = 1)");
+        if (h->N > 128) return CLIFT_GEMM_ROUTE_TILED_BF16_128X256;
+        if (h->N > 32) return CLIFT_GEMM_ROUTE_TILED_BF16_128X128;
+        return CLIFT_GEMM_ROUTE_TILED_BF16_256X32;
+    }
+
+    // -- precision 2: fp32x6
+    // the 256 x 256 hidden layers: persistent split kernels (layer_x6.hip), every M (a row's bits must not depend on its launch)
+    if (h->precision == 2 && !h->a_trans && h->N == 256 && h->K == 256 && splits == 1 && !h->accumulate && !h->c_trans && h->lda % 4 == 0 &&
+        h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && x6_persistent &&
+        ((!h->b_trans && !h->mask) ||
+         (h->b_trans && h->mask && !h->bias && h->act == 0 && h->ldmask % 4 == 0 && (((uintptr_t)h->mask) & 15) == 0) ||
+         (h->b_trans && !h->mask && h->sign_bits && !h->bias && h->act == 0)))
+        return CLIFT_GEMM_ROUTE_LAYER_X6;
+    // fp32x6 weight gradient of the 256 x 256 layers (layer_x6w.hip)
+    if (h->precision == 2 && h->a_trans && h->b_trans && h->M == 256 && h->N == 256 && h->K >= 4096 && h->accumulate && !h->c_trans && !h->bias && !h->mask &&
+        h->act == 0 && h->lda % 4 == 0 && h->ldb % 4 == 0 && (((uintptr_t)h->A) & 15) == 0 && (((uintptr_t)h->B) & 15) == 0)
+        return CLIFT_GEMM_ROUTE_WGRAD_X6;
+    // fp32x6, the 128-wide appearance layers (layer_n6.hip): forward K = 128 / 160 -> 128 (bias, ReLU), masked input gradient 128 -> 128, unmasked
+    // input gradient 128 -> 160, every M (a row's bits must not depend on its launch); and their weight gradients 128 x {128, 160}
+    if (h->precision == 2 && !h->a_trans && splits == 1 && !h->accumulate && !h->c_trans && h->lda % 4 == 0 && h->lda >= h->K && h->ldc % 4 == 0 &&
+        (((uintptr_t)h->C) & 15) == 0 && persistent && x6_persistent) {
+        const bool fwd = !h->b_trans && h->N == 128 && (h->K == 128 || h->K == 160) && !h->mask && h->ldb >= h->K && h->ldc >= 128 && (h->act == 0 || h->act == 1);
+        const bool dg_m = h->b_trans && h->N == 128 && h->K == 128 && h->mask && !h->bias && h->act == 0 && h->ldmask % 4 == 0 && h->ldmask >= 128 &&
+                          (((uintptr_t)h->mask) & 15) == 0 && h->ldb >= 128 && h->ldc >= 128;
+        const bool dg_u = h->b_trans && h->N == 160 && h->K == 128 && !h->mask && !h->bias && h->act == 0 && h->ldb >= 160 && h->ldc >= 160;
+        if (fwd || dg_m || dg_u) return CLIFT_GEMM_ROUTE_LAYER_N6;
+    }
+    if (h->precision == 2 && h->a_trans && h->b_trans && h->M == 128 && (h->N == 128 || h->N == 160) && h->K >= 1 && h->accumulate && !h->c_trans && !h->bias &&
+        !h->mask && h->act == 0 && h->lda % 4 == 0 && h->lda >= 128 && h->ldb % 4 == 0 && h->ldb >= h->N && h->ldc >= h->N &&
+        persistent && x6_persistent)
+        return CLIFT_GEMM_ROUTE_WGRAD_N6;
+    // fp32x6: forward / dgrad forms (row-major A, one weight-sized B); any other shape takes the tiled split kernel
+    if (h->precision == 2 && !h->a_trans && !h->accumulate && splits == 1 && !h->c_trans && (long)h->N * h->K <= (1L << 22))
+        return CLIFT_GEMM_ROUTE_SPLIT_TILED;
+
+    // -- precision 0: exact fp32 -- and what is left of precision 2 (forms without a split kernel run exact)
+    const bool exact = h->precision == 0;
+    // (every M: a row's result must not depend on how many rows share its launch -- a frame rendered in row tiles over several GPUs
+    // has to be bit-identical to the unsharded render, and the tiled kernel sums k in a different order)
+    if (exact && !h->a_trans && !h->b_trans && h->N == 256 && h->K == 256 && splits == 1 && !h->accumulate && !h->c_trans &&
+        !h->mask && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && persistent)
+        return CLIFT_GEMM_ROUTE_LAYER_F32_FWD;                      // persistent forward layer: weights in registers, LDS-DMA row stream
+    if (exact && !h->a_trans && h->b_trans && h->N == 256 && h->K == 256 && h->M >= 4096 && splits == 1 && !h->accumulate && !h->c_trans &&
+        h->mask && !h->bias && h->act == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && h->ldmask % 4 == 0 && (((uintptr_t)h->mask) & 15) == 0 &&
+        persistent)
+        return CLIFT_GEMM_ROUTE_LAYER_F32_DGRAD;                    // persistent masked dgrad of the same layers
+    if (exact && !h->a_trans && h->b_trans && (h->N == 256 || h->N == 128) && h->K <= 32 && h->K <= h->lda && h->lda <= 32 && h->M >= 4096 && splits == 1 &&
+        !h->accumulate && !h->c_trans && h->mask && !h->bias && h->act == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && h->ldmask % 4 == 0 &&
+        (((uintptr_t)h->mask) & 15) == 0 && persistent)
+        return CLIFT_GEMM_ROUTE_DGRAD_NARROW;                       // output-layer dgrad: a stream over the mask and the result
+    if (exact && !h->a_trans && h->b_trans && h->N <= 256 && h->N % 4 == 0 && h->N > 32 && h->K <= 32 && h->K <= h->lda && h->lda <= 32 && h->M >= 4096 &&
+        splits == 1 && !h->accumulate && !h->c_trans && !h->mask && !h->bias && h->act == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 &&
+        persistent)
+        return CLIFT_GEMM_ROUTE_DGRAD_NARROW;                       // unmasked narrow-K dgrad (appearance basis 27 -> 144): a stream over the result
+    // (up to ~150 k rows: beyond that the split-K tiled launch, whose k-loop is long by then, is as fast or faster: 304 vs 332 us at 249 k)
+    if (exact && h->a_trans && h->b_trans && h->M == 256 && h->N == 256 && h->K >= 4096 && h->accumulate && !h->c_trans && !h->bias && !h->mask &&
+        h->act == 0 && persistent)
+        // persistent 2-D weight gradient: 64 row ranges x four 128 x 128 quadrants, 64-row tiles (layer_n128.hip) -- 92 / 318 us at 62 k / 249 k rows
+        // (measured against 256 x 64 slices with 32-row tiles: 95 / 340, and the split-K tiled launch: 127 / 349; profiles/r02_*)
+        return CLIFT_GEMM_ROUTE_WGRAD_F32_QUADS;
+    // weight gradients of the 128-wide appearance layers (128 x 128 and 128 x 160 results): persistent row-range stream
+    if (exact && h->a_trans && h->b_trans && h->M == 128 && (h->N == 128 || h->N == 160) && h->ldb >= h->N && h->lda >= 128 && h->K >= 4096 &&
+        h->accumulate && !h->c_trans && !h->bias && !h->mask && h->act == 0 && persistent)
+        return CLIFT_GEMM_ROUTE_WGRAD_N128;
+    // the 128-wide layers of the appearance MLP (forward K = 128 / 160 with bias, masked dgrad K = 128): persistent, every M (see above)
+    if (exact && !h->a_trans && h->N == 128 && ((h->K == 128) || (h->K == 160 && !h->b_trans)) && h->lda >= h->K && splits == 1 &&
+        !h->accumulate && !h->c_trans && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 &&
+        ((!h->b_trans && !h->mask && h->ldb >= h->K) ||
+         (h->b_trans && h->mask && !h->bias && h->act == 0 && h->ldmask % 4 == 0 && (((uintptr_t)h->mask) & 15) == 0 && h->ldb >= 128)) &&
+        persistent)
+        return CLIFT_GEMM_ROUTE_LAYER_N128;
+    // dX of the first appearance layer, (M x 128) (128 x 160), no mask: columns 0..127 through the persistent 128-wide dgrad kernel,
+    // columns 128..159 through the tiled 32-column kernel (one tiled 128 x 256 launch: 183 us at 265 k rows; the pair: see DESIGN 5b)
+    if (exact && !h->a_trans && h->b_trans && h->N == 160 && h->K == 128 && h->M >= 4096 && splits == 1 && !h->accumulate && !h->c_trans &&
+        !h->mask && !h->bias && h->act == 0 && h->lda >= 128 && h->lda % 4 == 0 && h->ldb >= 160 && h->ldb % 4 == 0 && h->ldc >= 160 && h->ldc % 4 == 0 &&
+        (((uintptr_t)h->C) & 15) == 0 && (((uintptr_t)h->A) & 15) == 0 && (((uintptr_t)h->B) & 15) == 0 && persistent)
+        return CLIFT_GEMM_ROUTE_DGRAD_N160_PAIR;
+    if (h->N > 128) return CLIFT_GEMM_ROUTE_TILED_128X256;
+    if (h->N > 32) return CLIFT_GEMM_ROUTE_TILED_128X128;
+    return CLIFT_GEMM_ROUTE_TILED_256X32;
+}
+
+extern "C" int clift_gemm_route(const clift_gemm_t* h) {
+    int kper;
+    return gemm_route(h, &kper);
+}
+
+extern "C" const char* clift_gemm_route_name(int route) {
+    static const char* const names[CLIFT_GEMM_ROUTE_COUNT] = {
+        "NONE", "LAYER_X6", "WGRAD_X6", "LAYER_N6", "WGRAD_N6", "SPLIT_TILED", "LAYER_F32_FWD", "LAYER_F32_DGRAD", "DGRAD_NARROW", "WGRAD_F32_QUADS",
+        "WGRAD_N128", "LAYER_N128", "DGRAD_N160_PAIR", "TILED_128X256", "TILED_128X128", "TILED_256X32", "LAYER_BF16", "WGRAD_BF16",
+        "DGRAD_NARROW_BF16", "LAYER_NB16", "WGRAD_NB16", "TILED_BF16_128X256", "TILED_BF16_128X128", "TILED_BF16_256X32"};
+    return route >= 0 && route < CLIFT_GEMM_ROUTE_COUNT ? names[route] : "INVALID";
+}
+
+extern "C" int clift_gemm(const clift_gemm_t* h, clift_stream_t s) {
     GemmP p;
+    const int route = gemm_route(h, &p.k_per_split);
+    if (route == CLIFT_GEMM_ROUTE_INVALID) return 1;
+    if (route == CLIFT_GEMM_ROUTE_NONE) return 0;
     p.M = h->M; p.N = h->N; p.K = h->K;
     p.A = h->A; p.lda = h->lda; p.B = h->B; p.ldb = h->ldb; p.C = h->C; p.ldc = h->ldc;
     p.bias = h->bias; p.act = h->act; p.mask = h->mask; p.ldmask = h->ldmask; p.accumulate = h->accumulate;
     p.c_trans = h->c_trans; p.colsum = h->colsum;
     p.a_bf16 = h->a_bf16; p.b_bf16 = h->b_bf16; p.c_bf16 = h->c_bf16; p.mask_bf16 = h->mask_bf16;
     p.sign_bits = (unsigned char*)h->sign_bits;
-    CLIFT_REQUIRE(!h->sign_bits || (h->precision == 2 && !h->a_trans && h->N == 256 && h->K == 256 && splits == 1 && !h->accumulate && !h->c_trans &&
-                                     h->lda % 4 == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && getenv("CLIFT_X6_TILED") == nullptr &&
-                                     ((!h->b_trans && !h->mask) || (h->b_trans && !h->mask && !h->bias && h->act == 0))),
-                  "clift_gemm: sign_bits goes with the persistent fp32x6 256 x 256 forms only (forward: written; dgrad with mask = NULL: read)");
-    CLIFT_REQUIRE(h->precision == 1 || !(h->a_bf16 || h->b_bf16 || h->c_bf16 || h->mask_bf16),
-                  "clift_gemm: bf16-stored tensors (a/b/c/mask_bf16) are only supported with precision 1");
-    CLIFT_REQUIRE(!h->c_bf16 || (!h->accumulate && !h->c_trans), "clift_gemm: a bf16-stored output cannot be accumulated into or transposed");
-    int kper = cdiv(cdiv(h->K, splits), BK) * BK;
-    if (kper < BK) kper = BK;
-    splits = cdiv(h->K, kper);
-    if (splits < 1) splits = 1;
-    p.k_per_split = kper;
+    const int splits = cdiv(h->K, p.k_per_split) > 1 ? cdiv(h->K, p.k_per_split) : 1;
     hipStream_t st = as_stream(s);
-    CLIFT_REQUIRE(h->precision >= 0 && h->precision <= 2, "clift_gemm: precision must be 0 (fp32), 1 (bf16 operands) or 2 (fp32x6 split), got %d", h->precision);
-    if (h->precision == 1) return clift_gemm_bf16_launch(p, h->a_trans, h->b_trans, splits, st);
-    // fp32x6, the 256 x 256 hidden layers: persistent split kernels (layer_x6.hip), every M (a row's bits must not depend on its launch)
-    if (h->precision == 2 && !h->a_trans && h->N == 256 && h->K == 256 && splits == 1 && !h->accumulate && !h->c_trans && h->lda % 4 == 0 &&
-        h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && getenv("CLIFT_X6_TILED") == nullptr &&
-        ((!h->b_trans && !h->mask) ||
-         (h->b_trans && h->mask && !h->bias && h->act == 0 && h->ldmask % 4 == 0 && (((uintptr_t)h->mask) & 15) == 0) ||
-         (h->b_trans && !h->mask && h->sign_bits && !h->bias && h->act == 0)))
-        return clift_layer_x6_launch(p, h->b_trans, st);
-    // fp32x6 weight gradient of the 256 x 256 layers (layer_x6w.hip)
-    if (h->precision == 2 && h->a_trans && h->b_trans && h->M == 256 && h->N == 256 && h->K >= 4096 && h->accumulate && !h->c_trans && !h->bias && !h->mask &&
-        h->act == 0 && h->lda % 4 == 0 && h->ldb % 4 == 0 && (((uintptr_t)h->A) & 15) == 0 && (((uintptr_t)h->B) & 15) == 0)
-        return clift_wgrad_x6_launch(p, st);
-    // fp32x6, the 128-wide appearance layers (layer_n6.hip): forward K = 128 / 160 -> 128 (bias, ReLU), masked input gradient 128 -> 128, unmasked
-    // input gradient 128 -> 160, every M (a row's bits must not depend on its launch); and their weight gradients 128 x {128, 160}
-    if (h->precision == 2 && !h->a_trans && splits == 1 && !h->accumulate && !h->c_trans && h->lda % 4 == 0 && h->lda >= h->K && h->ldc % 4 == 0 &&
-        (((uintptr_t)h->C) & 15) == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr && getenv("CLIFT_X6_TILED") == nullptr) {
-        const bool fwd = !h->b_trans && h->N == 128 && (h->K == 128 || h->K == 160) && !h->mask && h->ldb >= h->K && h->ldc >= 128 && (h->act == 0 || h->act == 1);
-        const bool dg_m = h->b_trans && h->N == 128 && h->K == 128 && h->mask && !h->bias && h->act == 0 && h->ldmask % 4 == 0 && h->ldmask >= 128 &&
-                          (((uintptr_t)h->mask) & 15) == 0 && h->ldb >= 128 && h->ldc >= 128;
-        const bool dg_u = h->b_trans && h->N == 160 && h->K == 128 && !h->mask && !h->bias && h->act == 0 && h->ldb >= 160 && h->ldc >= 160;
-        if (fwd || dg_m || dg_u) return clift_layer_n6_launch(p, h->b_trans, st);
-    }
-    if (h->precision == 2 && h->a_trans && h->b_trans && h->M == 128 && (h->N == 128 || h->N == 160) && h->K >= 1 && h->accumulate && !h->c_trans && !h->bias &&
-        !h->mask && h->act == 0 && h->lda % 4 == 0 && h->lda >= 128 && h->ldb % 4 == 0 && h->ldb >= h->N && h->ldc >= h->N &&
-        getenv("CLIFT_NO_PERSISTENT") == nullptr && getenv("CLIFT_X6_TILED") == nullptr)
-        return clift_wgrad_n6_launch(p, st);
-    // fp32x6: forward / dgrad forms (row-major A, one weight-sized B); any other shape takes the tiled split kernel
-    if (h->precision == 2 && !h->a_trans && !h->accumulate && splits == 1 && !h->c_trans && (long)h->N * h->K <= (1L << 22)) {
+    switch (route) {
+    case CLIFT_GEMM_ROUTE_LAYER_X6: return clift_layer_x6_launch(p, h->b_trans, st);
+    case CLIFT_GEMM_ROUTE_WGRAD_X6: return clift_wgrad_x6_launch(p, st);
+    case CLIFT_GEMM_ROUTE_LAYER_N6: return clift_layer_n6_launch(p, h->b_trans, st);
+    case CLIFT_GEMM_ROUTE_WGRAD_N6: return clift_wgrad_n6_launch(p, st);
+    case CLIFT_GEMM_ROUTE_SPLIT_TILED: {
         const long need = clift_gemm_split_workspace_bytes(h->N, h->K);
         CLIFT_REQUIRE(h->workspace != nullptr && h->workspace_bytes >= need && (((uintptr_t)h->workspace & 15) == 0),
                       "clift_gemm: precision 2 needs a 16-byte aligned workspace of %ld bytes (got %ld)", need, h->workspace_bytes);
         return clift_gemm_split_launch(p, h->a_trans, h->b_trans, h->workspace, st);
     }
-    // (every M: a row's result must not depend on how many rows share its launch -- a frame rendered in row tiles over several GPUs
-    // has to be bit-identical to the unsharded render, and the tiled kernel sums k in a different order)
-    if (h->precision == 0 && !h->a_trans && !h->b_trans && h->N == 256 && h->K == 256 && splits == 1 && !h->accumulate && !h->c_trans &&
-        !h->mask && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_layer_f32_launch(p, 0, st);                    // persistent forward layer: weights in registers, LDS-DMA row stream
-    if (h->precision == 0 && !h->a_trans && h->b_trans && h->N == 256 && h->K == 256 && h->M >= 4096 && splits == 1 && !h->accumulate && !h->c_trans &&
-        h->mask && !h->bias && h->act == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && h->ldmask % 4 == 0 && (((uintptr_t)h->mask) & 15) == 0 &&
-        getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_layer_f32_launch(p, 1, st);                    // persistent masked dgrad of the same layers
-    if (h->precision == 0 && !h->a_trans && h->b_trans && (h->N == 256 || h->N == 128) && h->K <= 32 && h->K <= h->lda && h->lda <= 32 && h->M >= 4096 && splits == 1 &&
-        !h->accumulate && !h->c_trans && h->mask && !h->bias && h->act == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 && h->ldmask % 4 == 0 &&
-        (((uintptr_t)h->mask) & 15) == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_dgrad_narrow_stream_launch(p, 0, st);          // output-layer dgrad: a stream over the mask and the result
-    if (h->precision == 0 && !h->a_trans && h->b_trans && h->N <= 256 && h->N % 4 == 0 && h->N > 32 && h->K <= 32 && h->K <= h->lda && h->lda <= 32 && h->M >= 4096 &&
-        splits == 1 && !h->accumulate && !h->c_trans && !h->mask && !h->bias && h->act == 0 && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 &&
-        getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_dgrad_narrow_stream_launch(p, 0, st);          // unmasked narrow-K dgrad (appearance basis 27 -> 144): a stream over the result
-    // (up to ~150 k rows: beyond that the split-K tiled launch, whose k-loop is long by then, is as fast or faster: 304 vs 332 us at 249 k)
-    if (h->precision == 0 && h->a_trans && h->b_trans && h->M == 256 && h->N == 256 && h->K >= 4096 && h->accumulate && !h->c_trans && !h->bias && !h->mask &&
-        h->act == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        // persistent 2-D weight gradient: 64 row ranges x four 128 x 128 quadrants, 64-row tiles (layer_n128.hip) -- 92 / 318 us at 62 k / 249 k rows
-        // (measured against 256 x 64 slices with 32-row tiles: 95 / 340, and the split-K tiled launch: 127 / 349; profiles/r02_*)
-        return clift_wgrad_f32_quads_launch(p, st);
-    // weight gradients of the 128-wide appearance layers (128 x 128 and 128 x 160 results): persistent row-range stream
-    if (h->precision == 0 && h->a_trans && h->b_trans && h->M == 128 && (h->N == 128 || h->N == 160) && h->ldb >= h->N && h->lda >= 128 && h->K >= 4096 &&
-        h->accumulate && !h->c_trans && !h->bias && !h->mask && h->act == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_wgrad_n128_stream_launch(p, st);
-    // the 128-wide layers of the appearance MLP (forward K = 128 / 160 with bias, masked dgrad K = 128): persistent, every M (see above)
-    if (h->precision == 0 && !h->a_trans && h->N == 128 && ((h->K == 128) || (h->K == 160 && !h->b_trans)) && h->lda >= h->K && splits == 1 &&
-        !h->accumulate && !h->c_trans && h->ldc % 4 == 0 && (((uintptr_t)h->C) & 15) == 0 &&
-        ((!h->b_trans && !h->mask && h->ldb >= h->K) ||
-         (h->b_trans && h->mask && !h->bias && h->act == 0 && h->ldmask % 4 == 0 && (((uintptr_t)h->mask) & 15) == 0 && h->ldb >= 128)) &&
-        getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_layer_n128_launch(p, h->b_trans, st);
-    // dX of the first appearance layer, (M x 128) (128 x 160), no mask: columns 0..127 through the persistent 128-wide dgrad kernel,
-    // columns 128..159 through the tiled 32-column kernel (one tiled 128 x 256 launch: 183 us at 265 k rows; the pair: see DESIGN 5b)
-    if (h->precision == 0 && !h->a_trans && h->b_trans && h->N == 160 && h->K == 128 && h->M >= 4096 && splits == 1 && !h->accumulate && !h->c_trans &&
-        !h->mask && !h->bias && h->act == 0 && h->lda >= 128 && h->lda % 4 == 0 && h->ldb >= 160 && h->ldb % 4 == 0 && h->ldc >= 160 && h->ldc % 4 == 0 &&
-        (((uintptr_t)h->C) & 15) == 0 && (((uintptr_t)h->A) & 15) == 0 && (((uintptr_t)h->B) & 15) == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr) {
+    case CLIFT_GEMM_ROUTE_LAYER_F32_FWD: return clift_layer_f32_launch(p, 0, st);
+    case CLIFT_GEMM_ROUTE_LAYER_F32_DGRAD: return clift_layer_f32_launch(p, 1, st);
+    case CLIFT_GEMM_ROUTE_DGRAD_NARROW: return clift_dgrad_narrow_stream_launch(p, 0, st);
+    case CLIFT_GEMM_ROUTE_WGRAD_F32_QUADS: return clift_wgrad_f32_quads_launch(p, st);
+    case CLIFT_GEMM_ROUTE_WGRAD_N128: return clift_wgrad_n128_stream_launch(p, st);
+    case CLIFT_GEMM_ROUTE_LAYER_N128: return clift_layer_n128_launch(p, h->b_trans, st);
+    case CLIFT_GEMM_ROUTE_DGRAD_N160_PAIR: {
         GemmP p1 = p;
         p1.N = 128; p1.mask = p1.A; p1.ldmask = p1.lda; p1.act = 7;
         const int rc = clift_layer_n128_launch(p1, 1, st);
@@ -322,11 +416,16 @@ extern "C" int clift_gemm(const clift_gemm_t* h, clift_stream_t s) {
         p2.N = 32; p2.B = p.B + 128; p2.C = p.C + 128;
         return launch_gemm<256, 32, 4, 1>(p2, 0, 1, 1, st);
     }
-    if (h->N > 128) {
-        return launch_gemm<128, 256, 2, 4>(p, h->a_trans, h->b_trans, splits, st);
+    case CLIFT_GEMM_ROUTE_TILED_128X256: return launch_gemm<128, 256, 2, 4>(p, h->a_trans, h->b_trans, splits, st);
+    case CLIFT_GEMM_ROUTE_TILED_128X128: return launch_gemm<128, 128, 2, 2>(p, h->a_trans, h->b_trans, splits, st);
+    case CLIFT_GEMM_ROUTE_TILED_256X32: return launch_gemm<256, 32, 4, 1>(p, h->a_trans, h->b_trans, splits, st);
+    case CLIFT_GEMM_ROUTE_LAYER_BF16: return clift_layer_bf16_launch(p, h->b_trans, st);
+    case CLIFT_GEMM_ROUTE_WGRAD_BF16: return clift_wgrad_bf16_stream_launch(p, st);
+    case CLIFT_GEMM_ROUTE_DGRAD_NARROW_BF16: return clift_dgrad_narrow_stream_launch(p, 1, st);
+    case CLIFT_GEMM_ROUTE_LAYER_NB16: return clift_layer_nb16_launch(p, h->b_trans, st);
+    case CLIFT_GEMM_ROUTE_WGRAD_NB16: return clift_wgrad_nb16_launch(p, st);
+    default: return clift_gemm_bf16_tiled_launch(p, route, h->a_trans, h->b_trans, splits, st);      // the three TILED_BF16 routes
     }
-    if (h->N > 32) return launch_gemm<128, 128, 2, 2>(p, h->a_trans, h->b_trans, splits, st);
-    return launch_gemm<256, 32, 4, 1>(p, h->a_trans, h->b_trans, splits, st);
 }
 
 // ============================================================================ K = 3 first layers
@@ -458,7 +557,7 @@ extern "C" int clift_linear_k3_bwd(const float* x4, const float* dH, int ldh, in
                                    int dh_bf16, clift_stream_t s) {
     if (M <= 0) return 0;
     if (Nout == 256 && M >= 4096 && db && (((uintptr_t)x4) & 15) == 0 && (((uintptr_t)dH) & 15) == 0 && ldh % (dh_bf16 ? 8 : 4) == 0 &&
-        getenv("CLIFT_NO_PERSISTENT") == nullptr)
+        clift_switch_off(CLIFT_SWITCH_TILED_ONLY))
         return clift_k3_bwd_stream_launch(x4, dH, ldh, M, dW, ldw, db, dh_bf16, as_stream(s));      // matrix-core stream over dH (narrow_stream.hip)
     const int rpb = 512;
     k_linear_k3_bwd<<<dim3(cdiv(M, rpb), cdiv(Nout, 256)), 1024, 0, as_stream(s)>>>(x4, dH, ldh, M, Nout, rpb, dW, ldw, db, dh_bf16);
@@ -527,7 +626,7 @@ extern "C" int clift_wgrad_narrow(const float* dY, int ldd, int no, const float*
     CLIFT_REQUIRE(no >= 1 && no <= 32, "clift_wgrad_narrow: out_features must be in [1,32] (got %d)", no);
     if (M <= 0 || ni <= 0) return 0;
     if ((ni == 256 || (!x_bf16 && ni >= 32 && ni < 256 && ni % 4 == 0)) && M >= 4096 && ldd % 4 == 0 && ldd >= no && ldd <= 32 &&
-        (((uintptr_t)dY) & 15) == 0 && (((uintptr_t)X) & 15) == 0 && ldx % (x_bf16 ? 8 : 4) == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr)
+        (((uintptr_t)dY) & 15) == 0 && (((uintptr_t)X) & 15) == 0 && ldx % (x_bf16 ? 8 : 4) == 0 && clift_switch_off(CLIFT_SWITCH_TILED_ONLY))
         return clift_wgrad_narrow_stream_launch(dY, ldd, no, X, ldx, ni, M, gW, ldw, gb, x_bf16, as_stream(s));   // matrix-core stream over X
     const int rpb = 128;        // (insensitive between 64 and 520 rows per block: the kernel is FMA-bound, not launch-shape-bound)
     const dim3 grid(cdiv(M, rpb), cdiv(ni, 256));

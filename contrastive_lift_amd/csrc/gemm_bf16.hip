@@ -255,9 +255,7 @@ static int launch_one_h(const GemmP& p, int splits, hipStream_t st) {
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), 1, splits), block(WM * WN * 64);
     const bool vec = gemm_vector_epilogue_ok(p);
     if (p.a_bf16) {
-        if (AT != BT) {            // (a_trans, !b_trans) / (!a_trans, b_trans with bf16 B) forms have no bf16-stored instantiation
-            CLIFT_REQUIRE(!AT, "clift_gemm(bf16): a bf16-stored transposed A needs the wgrad form (b_trans = 1)");
-        }
+        // (the (a_trans, !b_trans) form with a bf16-stored A is refused by clift_gemm_route: it has no instantiation that is meant to run)
         if (!vec) k_gemm_bf16<BM, BN, WM, WN, AT, BT, false, true><<<grid, block, 0, st>>>(p);
         else k_gemm_bf16<BM, BN, WM, WN, AT, BT, true, true><<<grid, block, 0, st>>>(p);
     } else {
@@ -275,37 +273,10 @@ static int launch_gemm_h(const GemmP& p, int a_trans, int b_trans, int splits, h
     return launch_one_h<BM, BN, WM, WN, true, false>(p, splits, st);
 }
 
-int clift_gemm_bf16_launch(const GemmP& p, int a_trans, int b_trans, int splits, hipStream_t st) {
-    // storage combinations that exist: streamed operands bf16-stored together (A; and B exactly in the wgrad form), weights fp32
-    CLIFT_REQUIRE(!p.b_bf16 || (p.a_bf16 && a_trans && b_trans), "clift_gemm(bf16): a bf16-stored B needs the wgrad form with a bf16-stored A");
-    CLIFT_REQUIRE(!(p.a_bf16 && a_trans && b_trans) || p.b_bf16, "clift_gemm(bf16): the wgrad form takes both streamed operands bf16-stored or neither");
-    if (!a_trans && p.N == 256 && p.K == 256 && p.M >= 64 && p.a_bf16 && p.c_bf16 && splits == 1 && !p.accumulate && !p.c_trans &&
-        p.lda % 8 == 0 && p.ldc % 8 == 0 && ((((uintptr_t)p.A) | ((uintptr_t)p.C)) & 15) == 0 && p.ldb % 4 == 0 && (((uintptr_t)p.B) & 15) == 0 &&
-        (b_trans ? (p.mask && p.mask_bf16 && !p.bias && p.act == 0 && p.ldmask % 8 == 0 && (((uintptr_t)p.mask) & 15) == 0) : !p.mask))
-        return clift_layer_bf16_launch(p, b_trans, st);             // streamed hidden layer: persistent blocks, weights in registers
-    if (a_trans && b_trans && p.M == 256 && p.N == 256 && p.K >= 64 && p.a_bf16 && p.b_bf16 && p.accumulate && !p.c_trans && !p.bias && !p.mask &&
-        p.lda % 8 == 0 && p.ldb % 8 == 0 && ((((uintptr_t)p.A) | ((uintptr_t)p.B)) & 15) == 0)
-        return clift_wgrad_bf16_stream_launch(p, st);              // streamed weight gradient: persistent blocks, transposed LDS reads
-    if (!a_trans && b_trans && !p.a_bf16 && !p.b_bf16 && p.c_bf16 && p.mask && p.mask_bf16 && p.N == 256 && p.K <= 32 && p.K <= p.lda && p.lda <= 32 &&
-        p.lda % 4 == 0 && p.M >= 4096 && splits == 1 && !p.accumulate && !p.c_trans && !p.bias && p.act == 0 && p.ldc % 4 == 0 && p.ldmask % 4 == 0 &&
-        ((((uintptr_t)p.C) | ((uintptr_t)p.mask)) & 7) == 0 && getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_dgrad_narrow_stream_launch(p, 1, st);          // output-layer dgrad with bf16-stored mask / result (fp32 products: exact)
-    // the 128-wide appearance MLP with bf16-stored streams (layer_nb16.hip): forward K = 160 / 128 -> 128 (bias, ReLU), masked input gradient
-    // 128 -> 128, unmasked input gradient 128 -> 160 (bf16- or fp32-stored result), weight gradients 128 x {128, 160}
-    if (!a_trans && p.a_bf16 && splits == 1 && !p.accumulate && !p.c_trans && p.lda % 8 == 0 && p.lda >= p.K && (((uintptr_t)p.A) & 15) == 0 &&
-        p.ldb % 4 == 0 && (((uintptr_t)p.B) & 15) == 0 && (((uintptr_t)p.C) & 15) == 0 && p.M >= 64 && getenv("CLIFT_NO_PERSISTENT") == nullptr) {
-        const bool fwd = !b_trans && p.N == 128 && (p.K == 128 || p.K == 160) && p.c_bf16 && p.ldc % 8 == 0 && p.ldc >= 128 && !p.mask && p.ldb >= p.K;
-        const bool dg_m = b_trans && p.N == 128 && p.K == 128 && p.c_bf16 && p.ldc % 8 == 0 && p.ldc >= 128 && p.mask && p.mask_bf16 && p.ldmask % 8 == 0 &&
-                          p.ldmask >= 128 && (((uintptr_t)p.mask) & 15) == 0 && !p.bias && p.act == 0 && p.ldb >= 128;
-        const bool dg_u = b_trans && p.N == 160 && p.K == 128 && !p.mask && !p.bias && p.act == 0 && p.ldb >= 160 && p.ldc >= 160 &&
-                          (p.c_bf16 ? p.ldc % 8 == 0 : p.ldc % 4 == 0);
-        if (fwd || dg_m || dg_u) return clift_layer_nb16_launch(p, b_trans, st);
-    }
-    if (a_trans && b_trans && p.M == 128 && (p.N == 128 || p.N == 160) && p.K >= 64 && p.a_bf16 && p.b_bf16 && p.accumulate && !p.c_trans && !p.bias && !p.mask &&
-        p.lda % 8 == 0 && p.lda >= 128 && p.ldb % 8 == 0 && p.ldb >= p.N && p.ldc >= p.N && ((((uintptr_t)p.A) | ((uintptr_t)p.B)) & 15) == 0 &&
-        getenv("CLIFT_NO_PERSISTENT") == nullptr)
-        return clift_wgrad_nb16_launch(p, st);
-    if (p.N > 128) return launch_gemm_h<128, 256, 2, 4>(p, a_trans, b_trans, splits, st);
-    if (p.N > 32) return launch_gemm_h<128, 128, 2, 2>(p, a_trans, b_trans, splits, st);
+// the tiled bf16 kernel by block tile (route = one of CLIFT_GEMM_ROUTE_TILED_BF16_*; the routing itself: clift_gemm_route, gemm.hip)
+int clift_gemm_bf16_tiled_launch(const GemmP& p, int route, int a_trans, int b_trans, int splits, hipStream_t st) {
+    if (route == CLIFT_GEMM_ROUTE_TILED_BF16_128X256) return launch_gemm_h<128, 256, 2, 4>(p, a_trans, b_trans, splits, st);
+    if (route == CLIFT_GEMM_ROUTE_TILED_BF16_128X128) return launch_gemm_h<128, 128, 2, 2>(p, a_trans, b_trans, splits, st);
+    CLIFT_REQUIRE(route == CLIFT_GEMM_ROUTE_TILED_BF16_256X32, "clift_gemm: no kernel for route %d", route);
     return launch_gemm_h<256, 32, 4, 1>(p, a_trans, b_trans, splits, st);
 }

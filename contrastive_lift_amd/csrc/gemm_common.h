@@ -38,7 +38,7 @@ static inline bool gemm_vector_epilogue_ok(const GemmP& p) {
            (!p.mask || ((p.ldmask % 4 == 0) && (((uintptr_t)p.mask & 15) == 0)));
 }
 
-int clift_gemm_bf16_launch(const GemmP& p, int a_trans, int b_trans, int splits, hipStream_t st);   // gemm_bf16.hip
+int clift_gemm_bf16_tiled_launch(const GemmP& p, int route, int a_trans, int b_trans, int splits, hipStream_t st);   // gemm_bf16.hip
 int clift_layer_bf16_launch(const GemmP& p, int b_trans, hipStream_t st);                            // layer_bf16.hip
 int clift_wgrad_bf16_stream_launch(const GemmP& p, hipStream_t st);
 int clift_layer_nb16_launch(const GemmP& p, int b_trans, hipStream_t st);                            // layer_nb16.hip

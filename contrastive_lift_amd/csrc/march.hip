@@ -142,9 +142,7 @@ extern "C" int clift_density_fwd(const clift_march_t* h_m, const clift_vm_t* h_d
                                  const float* jitter, int N, float* sigma, clift_stream_t s) {
     CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
     if (N <= 0) return 0;
-    const char* form = getenv("CLIFT_DENS_FWD");                         // test hook: "thread" = the per-thread form
-    const bool per_thread = form && !strcmp(form, "thread");
-    if (per_thread) {
+    if (!clift_switch_off(CLIFT_SWITCH_DENS_FWD_THREAD)) {              // test hook: the per-thread form
         const long total = (long)N * h_m->n_samples;
         k_density_fwd<<<cdiv(total * 4, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_dens), rays, jitter, total, sigma);
     } else {
@@ -610,8 +608,8 @@ extern "C" int clift_density_bwd(const clift_march_t* h_m, const clift_vm_t* h_d
     int lg = 0;
     while ((1 << lg) < Cc) ++lg;
     const int DENS_SEG = DENS_SEG_DEFAULT;
-    const char* mode = getenv("CLIFT_DENS_SCATTER");                  // test hook: "walk" = the group-per-segment walk (the only form for comps > 16) for any comps
-    if (Cc <= 16 && !(mode && strcmp(mode, "walk") == 0)) {
+    // (test hook CLIFT_SWITCH_DENS_SCATTER_WALK: the group-per-segment walk -- the only form for comps > 16 -- for any comps)
+    if (Cc <= 16 && clift_switch_off(CLIFT_SWITCH_DENS_SCATTER_WALK)) {
         const int slab = (line_lds_floats(h_dens->res, Cc) * 4 + 15) / 16 * 16;
         const int rec_bytes = 3 * DU_SEG * (int)sizeof(DensRec);     // 6 KB per wave
         int wpb = 16, bpc = 1;

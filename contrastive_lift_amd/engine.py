@@ -11,6 +11,7 @@ Per chunk of N rays (reference renderer.py:80-176):
   xyz heads: K=3 first layer -> GEMM+ReLU chain -> narrow GEMM (-> softmax)
   composite.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -129,9 +130,9 @@ def _app_precision():
     # fp32x6 (2): only the 256 x 256 layers have persistent split kernels; the 128-wide appearance layers would fall to the TILED split kernel
     # (gemm_split.hip), which is slower than the exact persistent kernels and -- seen with two processes sharing the GPU -- the one kernel of that
     # mode whose results were disturbed by the other process's fp32x6 launches (profiles/r03_x6_notes.txt).  Exact fp32 there.
-    if MLP_PRECISION == 1 and APP_BF16 and os.environ.get("CLIFT_NO_PERSISTENT") is None:
+    if MLP_PRECISION == 1 and APP_BF16 and persistent_ok():
         return _Precision(1)
-    if MLP_PRECISION == 2 and APP_X6 and os.environ.get("CLIFT_NO_PERSISTENT") is None and os.environ.get("CLIFT_X6_TILED") is None:
+    if MLP_PRECISION == 2 and APP_X6 and persistent_ok() and persistent_x6_ok():
         return _Precision(2)
     if MLP_PRECISION in (1, 2):
         return _Precision(0)
@@ -150,6 +151,61 @@ def set_mlp_precision(name):
     prev = {0: "fp32", 1: "bf16", 2: "fp32x6"}[MLP_PRECISION]
     MLP_PRECISION = _PRECISIONS[str(name).lower()]
     return prev
+
+
+# Kernel switches (include/clift.h, CLIFT_SWITCH_*): the library's word, set through kernel_switches() below -- or, once, at the first launch of
+# a process started with one of the switch variables of include/clift.h in its environment.  The fusion conditions of this module read the
+# cached copy: it changes in kernel_switches() only, so no library call is added to the launch path.
+SWITCH_TILED_ONLY, SWITCH_X6_TILED, SWITCH_DENS_FWD_THREAD, SWITCH_DENS_SCATTER_WALK = 1, 2, 4, 8
+_switches = None
+
+
+def _switch_word():
+    global _switches
+    if _switches is None:
+        _switches = int(_lib.load().clift_get_switches())
+    return _switches
+
+
+def persistent_ok():
+    """Persistent / streaming / fused kernels allowed (the tiled-only switch is off)."""
+    return not _switch_word() & SWITCH_TILED_ONLY
+
+
+def persistent_x6_ok():
+    """Persistent fp32x6 split kernels allowed (the x6-tiled switch is off)."""
+    return not _switch_word() & SWITCH_X6_TILED
+
+
+@contextlib.contextmanager
+def kernel_switches(tiled_only=None, x6_tiled=None, dens_fwd_thread=None, dens_scatter_walk=None):
+    """Context: set (True) or clear (False) kernel switches of the library -- None leaves one as it is -- and restore the word on exit.
+    The cross-checks of the test-suite and the A/B tools: the independent tiled kernels against the persistent ones on the same inputs."""
+    global _switches
+    prev = word = _switch_word()
+    for bit, on in ((SWITCH_TILED_ONLY, tiled_only), (SWITCH_X6_TILED, x6_tiled), (SWITCH_DENS_FWD_THREAD, dens_fwd_thread),
+                    (SWITCH_DENS_SCATTER_WALK, dens_scatter_walk)):
+        if on is not None:
+            word = (word | bit) if on else (word & ~bit)
+    _lib.load().clift_set_switches(word)
+    _switches = word
+    try:
+        yield
+    finally:
+        _lib.load().clift_set_switches(prev)
+        _switches = prev
+
+
+_x6_routes = None
+
+
+def _x6_persistent_routes():
+    """The clift_gemm routes of the persistent fp32x6 split kernels (they need no workspace)."""
+    global _x6_routes
+    if _x6_routes is None:
+        routes = _lib.gemm_routes()
+        _x6_routes = frozenset(routes[n] for n in ("LAYER_X6", "WGRAD_X6", "LAYER_N6", "WGRAD_N6"))
+    return _x6_routes
 
 
 def sign_bits_for(M, dev):
@@ -174,39 +230,26 @@ def gemm(M, N, K, A, lda, B, ldb, Cm, ldc, a_trans=0, b_trans=0, bias=None, act=
     g.c_trans = int(c_trans)
     g.colsum = colsum.data_ptr() if colsum is not None else None
     g.sign_bits = sign_bits.data_ptr() if sign_bits is not None else None
-    # fp32x6 mode: the 256 x 256 hidden layers (forward / dgrad) run as persistent split kernels (csrc/layer_x6.hip); every other
-    # launch -- narrow layers (HBM streams), the 128-wide appearance MLP, the other weight gradients -- stays on its exact-fp32 persistent kernel,
-    # which is faster than the tiled split kernel the library would pick for it
-    x6 = N == 256 and K == 256 and not a_trans and not accumulate and not c_trans
-    # ... and their weight gradients (csrc/layer_x6w.hip)
-    x6w = (a_trans and b_trans and M == 256 and N == 256 and K >= 4096 and accumulate and not c_trans and bias is None and mask is None
-           and not act and int(lda) % 4 == 0 and int(ldb) % 4 == 0 and A.dtype == torch.float32 and B.dtype == torch.float32)
-    # ... and the 128-wide layers of the appearance MLP (csrc/layer_n6.hip): forward K in {128, 160} -> 128, masked dgrad 128 -> 128, unmasked dgrad
-    # 128 -> 160, weight gradients 128 x {128, 160}
-    f32s = A.dtype == torch.float32 and B.dtype == torch.float32 and Cm.dtype == torch.float32
-    n6 = (f32s and not a_trans and not accumulate and not c_trans and int(lda) % 4 == 0 and int(lda) >= K and int(ldc) % 4 == 0 and g.C % 16 == 0 and
-          ((not b_trans and N == 128 and K in (128, 160) and mask is None and int(ldb) >= K and act in (0, 1)) or
-           (b_trans and K == 128 and bias is None and not act and
-            ((N == 128 and mask is not None and int(ldmask) % 4 == 0 and int(ldmask) >= 128 and g.mask % 16 == 0) or (N == 160 and mask is None and int(ldb) >= 160)))))
-    n6w = (f32s and a_trans and b_trans and M == 128 and N in (128, 160) and accumulate and not c_trans and bias is None and mask is None and not act
-           and int(lda) % 4 == 0 and int(lda) >= 128 and int(ldb) % 4 == 0 and int(ldb) >= N and int(ldc) >= N)
-    if os.environ.get("CLIFT_NO_PERSISTENT") is not None or os.environ.get("CLIFT_X6_TILED") is not None:
-        n6 = n6w = False
-    g.precision = MLP_PRECISION if (MLP_PRECISION != 2 or x6 or x6w or n6 or n6w) else 0
     g.a_bf16, g.b_bf16 = int(A.dtype == torch.bfloat16), int(B.dtype == torch.bfloat16)
     g.c_bf16, g.mask_bf16 = int(Cm.dtype == torch.bfloat16), int(mask is not None and mask.dtype == torch.bfloat16)
-    if g.precision == 2 and not (x6w or n6 or n6w):
-        # the persistent split kernel takes 16-byte aligned rows; anything else (odd output pitch ...) goes to the library's tiled split
-        # kernel, which needs a workspace for the split weight planes
-        persistent = (int(lda) % 4 == 0 and int(ldc) % 4 == 0 and g.C % 16 == 0 and (mask is None or (int(ldmask) % 4 == 0 and g.mask % 16 == 0))
-                      and ((not b_trans and mask is None) or (b_trans and (mask is not None or sign_bits is not None) and bias is None and not act))
-                      and not os.environ.get("CLIFT_X6_TILED"))
-        if not persistent:
-            nbytes = int(_lib.load().clift_gemm_workspace_bytes(int(N), int(K)))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=A.device)      # split weight planes (stream-ordered scratch)
-            if _lib._launch_stream is not None:   # launched on a side stream (Branches): the allocator must not recycle it earlier
-                ws.record_stream(_lib._launch_stream)
-            g.workspace, g.workspace_bytes = ws.data_ptr(), nbytes
+    g.precision = MLP_PRECISION
+    # fp32x6 mode: the launches the library has persistent split kernels for -- the 256 x 256 hidden layers (csrc/layer_x6.hip, layer_x6w.hip) and the
+    # 128-wide layers of the appearance MLP (csrc/layer_n6.hip), forward / dgrad / weight gradient -- run on them; clift_gemm_route says which those are
+    route = _lib.load().clift_gemm_route(C.byref(g)) if MLP_PRECISION == 2 else None
+    if MLP_PRECISION == 2 and route not in _x6_persistent_routes():
+        if N == 256 and K == 256 and not a_trans and not accumulate and not c_trans:
+            # a 256 x 256 forward / dgrad the persistent kernel does not take (rows not 16-byte aligned, odd output pitch, the x6-tiled switch ...)
+            # goes to the library's tiled split kernel, which needs a workspace for the split weight planes
+            if route != 0:      # (route 0: an empty launch, nothing runs)
+                nbytes = int(_lib.load().clift_gemm_workspace_bytes(int(N), int(K)))
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=A.device)      # split weight planes (stream-ordered scratch)
+                if _lib._launch_stream is not None:   # launched on a side stream (Branches): the allocator must not recycle it earlier
+                    ws.record_stream(_lib._launch_stream)
+                g.workspace, g.workspace_bytes = ws.data_ptr(), nbytes
+        else:
+            # every other launch -- narrow layers (HBM streams), the remaining weight gradients -- stays on its exact-fp32 persistent kernel, which is
+            # faster than the tiled split kernel the library would pick for it
+            g.precision = 0
     call("clift_gemm", C.byref(g), stream())
 
 
@@ -324,8 +367,9 @@ def first2(M, xa, W0, b0, W1, b1, h1, h2):
 # The fusions of the xyz heads are not switchable (their A/Bs are settled: profiles/r02_*, r03_ab_first2_bwd.txt, r04_ab_x6_fused_ends.txt): the K = 3
 # layer is generated inside the second layer's kernel; the first activation is never written -- the backward consumes the second layer's input
 # gradient inside its kernel (first2_bwd) and regenerates the activation for the weight gradient (first2_wgrad); an E <= 4 output layer is
-# applied inside the last hidden layer's kernel; the output layer's weight and input gradient are one launch.  CLIFT_NO_PERSISTENT=1 selects
-# the independent tiled kernels for every layer instead (the cross-check the tests use).
+# applied inside the last hidden layer's kernel; the output layer's weight and input gradient are one launch.  The tiled-only switch --
+# kernel_switches(tiled_only=True), or its environment variable (include/clift.h) read once at start -- selects the independent tiled kernels for
+# every layer instead (the cross-check the tests use).
 APP_SCATTER_XA = True       # tests clear it: clift_app_gather_bwd without the forward's positions (xa = NULL: the lane-per-(plane, channel) walk)
 DENS_BWD_SIGMA = True       # tests clear it: clift_density_bwd without the forward's sigma (sigma = NULL: the softplus derivative re-summed)
 FIRST2_BF16_BWD_FUSED = True  # tests clear it: bf16 mode, the second layer's input gradient written and the K = 3 layer's weight gradient as its own launch
@@ -420,7 +464,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
     hdt = act_dtype()                     # bf16 mode stores the hidden activations as bf16 (half the HBM stream of these layers)
     rest = layers[1:-1]
     if (FUSE_HEAD_BF16 and MLP_PRECISION == 1 and hdt == torch.bfloat16 and len(layers) >= 4 and W0.shape[0] == 256
-            and tuple(layers[1][0].shape) == (256, 256) and tuple(layers[2][0].shape) == (256, 256) and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+            and tuple(layers[1][0].shape) == (256, 256) and tuple(layers[2][0].shape) == (256, 256) and persistent_ok()):
         # bf16 mode: K = 3 layer + two hidden layers (+ the output layer when it is <= 4 wide and follows directly) in one launch with the
         # activations resident in LDS; they are written (bf16) only for a backward pass
         Wo, bo = layers[-1]
@@ -437,7 +481,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         h = h3
         rest = layers[3:-1]
     elif (MLP_PRECISION == 0 and len(layers) >= 3 and W0.shape[0] == 256 and tuple(layers[1][0].shape) == (256, 256)
-            and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+            and persistent_ok()):
         W1, b1 = layers[1]
         # (with the fused backward the first layer's activation has no reader: both of its uses -- the ReLU mask of the second layer's input
         # gradient and the second layer's weight gradient -- re-derive it from the positions, so it is never written)
@@ -447,8 +491,8 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         acts += [h1, h]
         rest = layers[2:-1]
     elif (MLP_PRECISION == 2 and len(layers) >= 3 and W0.shape[0] == 256 and tuple(layers[1][0].shape) == (256, 256)
-            and (not keep_first or not KEEP_FIRST_ACT) and os.environ.get("CLIFT_NO_PERSISTENT") is None
-            and os.environ.get("CLIFT_X6_TILED") is None):
+            and (not keep_first or not KEEP_FIRST_ACT) and persistent_ok()
+            and persistent_x6_ok()):
         # fp32x6: the same fusion with the 256 x 256 layer on the split kernels; the first activation is never written (the backward, if any,
         # re-derives it: first2_bwd / first2_wgrad)
         W1, b1 = layers[1]
@@ -467,8 +511,8 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         acts.append(h)
     Wo, bo = layers[-1]
     fuse_out = (MLP_PRECISION in (0, 2) and len(rest) >= 1 and Wo.shape[0] <= 4 and tuple(rest[-1][0].shape) == (256, 256)
-                and h.dtype == torch.float32 and out.dtype == torch.float32 and os.environ.get("CLIFT_NO_PERSISTENT") is None
-                and (MLP_PRECISION == 0 or os.environ.get("CLIFT_X6_TILED") is None))
+                and h.dtype == torch.float32 and out.dtype == torch.float32 and persistent_ok()
+                and (MLP_PRECISION == 0 or persistent_x6_ok()))
     for li_, (W, b) in enumerate(rest):
         if fuse_out and li_ == len(rest) - 1:
             # last hidden layer + the narrow output layer in one launch; the hidden activation is written only for a backward
@@ -481,7 +525,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         hn = torch.empty((M, W.shape[0]), dtype=hdt, device=dev)
         # (fp32x6, a backward will run, and this is not the last hidden layer -- whose output the output layer's backward reads as values: sign bytes too)
         sb = (sign_bits_for(M, dev) if (keep_first and MLP_PRECISION == 2 and li_ < len(rest) - 1 and tuple(W.shape) == (256, 256) and h.dtype == torch.float32
-                                        and os.environ.get("CLIFT_X6_TILED") is None and os.environ.get("CLIFT_NO_PERSISTENT") is None) else None)
+                                        and persistent_x6_ok() and persistent_ok()) else None)
         gemm(M, W.shape[0], W.shape[1], h, h.shape[1], W, _pitch(W), hn, hn.shape[1], bias=b, act=1, sign_bits=sb)
         acts.append(hn)
         if sb is not None:
@@ -489,7 +533,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         h = hn
     W, b = Wo, bo
     if (MLP_PRECISION in (0, 2) and W.shape[0] <= 32 and W.shape[1] == 256 and h.dtype == torch.float32 and h.shape[1] == 256 and out.dtype == torch.float32
-            and _pitch(W) % 4 == 0 and b is not None and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+            and _pitch(W) % 4 == 0 and b is not None and persistent_ok()):
         # the E <= 32 output layer (+ the row softmax) as one stream over the hidden activation
         out_layer_fwd(M, h, W, b, out, ldo, col_off, out_act)
         return acts if keep_first else [None]
@@ -518,12 +562,12 @@ def xyz_mlp_bwd(layers, glayers, xa, acts, dpre, M, keep=None):
         no, ni = W.shape
         if li == 1 and (h is None or (not KEEP_FIRST_ACT and MLP_PRECISION in (0, 2) and no == 256 and ni == 256 and tuple(layers[0][0].shape) == (256, 3) and
                                       d.dtype == torch.float32 and h.dtype == torch.float32 and d.shape[1] % 4 == 0 and
-                                      os.environ.get("CLIFT_NO_PERSISTENT") is None)):
+                                      persistent_ok())):
             # second layer: its weight gradient (over the first layer's activation -- regenerated from the positions when the forward did not keep
             # it), then its input gradient formed and consumed by the first layer's weight gradient in one launch
             if no != 256 or ni != 256 or tuple(layers[0][0].shape) != (256, 3) or d.shape[1] != 256 or d.dtype != torch.float32:
                 raise _lib.CliftError("backward through an xyz head whose forward ran with keep_first=False (head not named in grad_heads)")
-            x6_ends = MLP_PRECISION == 2 and os.environ.get("CLIFT_X6_TILED") is None
+            x6_ends = MLP_PRECISION == 2 and persistent_x6_ok()
             if h is None:
                 (first2_x6_wgrad if x6_ends else first2_wgrad)(M, d, layers[0][0], layers[0][1], xa, gW, gb)
             else:
@@ -532,7 +576,7 @@ def xyz_mlp_bwd(layers, glayers, xa, acts, dpre, M, keep=None):
             return
         if (li == 1 and MLP_PRECISION == 1 and FIRST2_BF16_BWD_FUSED and h is not None and h.dtype == torch.bfloat16 and d.dtype == torch.bfloat16
                 and no == 256 and ni == 256 and tuple(layers[0][0].shape) == (256, 3) and d.shape[1] == 256 and h.shape[1] == 256 and M >= 4096
-                and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+                and persistent_ok()):
             # bf16 mode, second layer: its weight gradient, then its input gradient formed and consumed by the K = 3 layer's weight gradient in one launch
             wgrad(no, ni, M, d, d.shape[1], h, h.shape[1], gW, gb)
             call("clift_xyz_head_first2_bf16_bwd", ptr(d), 256, ptr(W), _pitch(W), ptr(h), 256, ptr(xa), M, ptr(glayers[0][0]), _pitch(glayers[0][0]),
@@ -558,7 +602,7 @@ def xyz_mlp_bwd(layers, glayers, xa, acts, dpre, M, keep=None):
         wgrad(no, ni, M, d, d.shape[1], h, h.shape[1], gW, gb)
         sb = acts.sign_bits_of(li - 1, M) if isinstance(acts, HeadActs) else None
         if (sb is not None and MLP_PRECISION == 2 and no == 256 and ni == 256 and d.dtype == torch.float32 and d.shape[1] % 4 == 0
-                and os.environ.get("CLIFT_X6_TILED") is None):
+                and persistent_x6_ok()):
             gemm(M, ni, no, d, d.shape[1], W, _pitch(W), dn, ni, b_trans=1, sign_bits=sb)      # mask = the signs the forward left behind
         else:
             gemm(M, ni, no, d, d.shape[1], W, _pitch(W), dn, ni, b_trans=1, mask=h, ldmask=h.shape[1])
@@ -588,7 +632,7 @@ def feat_mlp_fwd(layers, X, M, out, ldo, col_off=0, keep=True, out_act=0):
         h = hn
     Wo, bo = layers[-1]
     if (Wo.shape[0] <= 32 and h.shape[1] == 256 and _pitch(Wo) % 4 == 0 and _pitch(Wo) >= 256 and MLP_PRECISION in (0, 2)
-            and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+            and persistent_ok()):
         out_layer_fwd(M, h, Wo, bo, out, ldo, col_off, out_act)
     else:
         gemm(M, Wo.shape[0], _pitch(Wo), h, h.shape[1], Wo, _pitch(Wo), out, ldo, bias=bo, c_off=col_off)
@@ -801,7 +845,7 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
             W1 = views["render_appearance_mlp.mlp.0.weight"]
             nf, ldx = Wb.shape[0], _pitch(W1)
             if (APP_FRONT_FUSED and nf <= 28 and va.comps in (16, 32, 48) and Wb.shape[1] == nc and _pitch(Wb) % 4 == 0 and ldx % 4 == 0 and ldx <= 512
-                    and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+                    and persistent_ok()):
                 # the appearance front end as one launch: gather -> basis -> MLP input rows (the products are written only for a backward)
                 ldf = 28
                 F = torch.empty((M, nc), dtype=torch.float32, device=dev) if "app" in grad_heads else None
@@ -843,16 +887,16 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
             gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
             rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
             if (MLP_PRECISION in (0, 2) and hdt == torch.float32 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128
-                    and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+                    and persistent_ok()):
                 # second hidden layer + output layer + sigmoid in one launch; H2 is written only for a backward
                 H2 = torch.empty((M, 128), dtype=torch.float32, device=dev) if "app" in grad_heads else None
-                if MLP_PRECISION == 2 and os.environ.get("CLIFT_X6_TILED") is None:        # (only inside _app_precision() with APP_X6)
+                if MLP_PRECISION == 2 and persistent_x6_ok():        # (only inside _app_precision() with APP_X6)
                     call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
                          ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
                 else:
                     app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
             elif (MLP_PRECISION == 1 and hdt == torch.bfloat16 and H1.dtype == torch.bfloat16 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4
-                    and W3.shape[1] == 128 and M >= 64 and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+                    and W3.shape[1] == 128 and M >= 64 and persistent_ok()):
                 # bf16 mode: the same pair of layers over the bf16-stored activation (csrc/layer_nb16.hip)
                 H2 = torch.empty((M, 128), dtype=torch.bfloat16, device=dev) if "app" in grad_heads else None
                 call("clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
@@ -1038,12 +1082,12 @@ def render_backward(model, ctx, gviews, g_rgb=None, g_sem=None, g_inst=None, g_d
             n2 = W3.shape[1]
             dH2 = torch.empty((M, n2), dtype=H2.dtype, device=dev)
             if (APP_OUT_BWD_FUSED and H2.dtype == torch.float32 and n2 % 32 == 0 and n2 <= 256 and W3.shape[0] <= 4 and M >= 4096
-                    and _pitch(W3) >= n2 and _pitch(gW3) >= n2 and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+                    and _pitch(W3) >= n2 and _pitch(gW3) >= n2 and persistent_ok()):
                 # output layer: weight gradient and masked input gradient in one pass over the hidden activation (as in the xyz heads)
                 call("clift_out_layer_bwd_nh", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), n2, n2, M, ptr(dH2), n2, ptr(gW3), _pitch(gW3),
                      ptr(gb3), 0, stream())
             elif (APP_OUT_BWD_FUSED and MLP_PRECISION == 1 and H2.dtype == torch.bfloat16 and n2 == 128 and W3.shape[0] <= 4 and dpre.shape[1] == 4
-                    and _pitch(W3) >= 128 and _pitch(gW3) >= 128 and os.environ.get("CLIFT_NO_PERSISTENT") is None):
+                    and _pitch(W3) >= 128 and _pitch(gW3) >= 128 and persistent_ok()):
                 # bf16 mode: the same one pass over the bf16-stored activation; the input gradient leaves bf16-stored
                 call("clift_out_layer_bwd_n128_bf16", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), 128, M, ptr(dH2), 128, ptr(gW3), _pitch(gW3),
                      ptr(gb3), stream())

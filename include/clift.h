@@ -33,6 +33,19 @@ int clift_version(void);
  * the collective's kernels while an asynchronous all-reduce is in flight -- the persistent launches (one block per CU, held for the
  * whole launch) then use 256 - k blocks.  k = 0 restores the default.  Host state; takes effect at the next launch. */
 int clift_set_cu_reserve(int k);
+/* Kernel switches (ABI 21): one process-wide word of host state that the launch routing reads.  The cross-checks of the test-suite and the A/B
+ * tools set it; production runs leave it 0.  The word is seeded ONCE, at its first use, from the environment -- CLIFT_NO_PERSISTENT (set to
+ * anything), CLIFT_X6_TILED (set to anything), CLIFT_DENS_FWD=thread, CLIFT_DENS_SCATTER=walk -- so a process started with one of them behaves as
+ * before; at run time it changes through clift_set_switches only (returns the previous word; takes effect at the next launch). */
+enum {
+    CLIFT_SWITCH_TILED_ONLY = 1,         /* every layer on the independent tiled / VALU kernels instead of the persistent and streaming ones */
+    CLIFT_SWITCH_X6_TILED = 2,           /* fp32x6 on the tiled split kernel (csrc/gemm_split.hip) instead of the persistent split kernels */
+    CLIFT_SWITCH_DENS_FWD_THREAD = 4,    /* clift_density_fwd: the per-thread lookup (the form the wave-per-sweep kernel replaced; bit-identical) */
+    CLIFT_SWITCH_DENS_SCATTER_WALK = 8,  /* clift_density_bwd: the group-per-segment walk (the form for comps > 16) at any component count */
+    CLIFT_SWITCH_ALL = 15
+};
+unsigned clift_set_switches(unsigned word);
+unsigned clift_get_switches(void);
 const char* clift_last_error(void);
 
 /* One VM-decomposed table set (3 planes + 3 lines, equal component count). */
@@ -208,8 +221,9 @@ int clift_app_front_fwd_x(const clift_march_t* h_m, const clift_vm_t* h_app, con
  * Dispatch (no change of contract): the N = K = 256 hidden-layer forms with M >= 4096 -- forward (plain A, [n][k] weights, no
  *   mask) and masked dgrad (b_trans, fp32 mask, no bias/act) -- run as persistent kernels (csrc/layer_f32.hip: weights in registers,
  *   rows streamed by LDS-DMA); in precision 1 with bf16-stored A / C (/ mask) the same forms and the 256 x 256 wgrad run as
- *   streaming kernels (csrc/layer_bf16.hip).  Everything else takes the tiled kernels (csrc/gemm*.hip).  The environment variable
- *   CLIFT_NO_PERSISTENT=1 forces the tiled fp32 kernels (A/B comparisons in tests/test_gpu_parity.py). */
+ *   streaming kernels (csrc/layer_bf16.hip).  Everything else takes the tiled kernels (csrc/gemm*.hip).  clift_gemm_route (below) names the
+ *   kernel a descriptor goes to.  CLIFT_SWITCH_TILED_ONLY forces the tiled kernels (A/B comparisons in tests/test_gpu_parity.py): the
+ *   environment variable CLIFT_NO_PERSISTENT=1, read once at start, or clift_set_switches at run time. */
 typedef struct {
     int M, N, K;
     const float* A; int lda; int a_trans;
@@ -234,6 +248,43 @@ typedef struct {
                                      * the same M. */
 } clift_gemm_t;
 long clift_gemm_workspace_bytes(int N, int K);
+/* The kernel clift_gemm runs a descriptor on (ABI 21).  clift_gemm_route checks the descriptor like clift_gemm does and returns the route, or
+ * CLIFT_GEMM_ROUTE_INVALID with the message in clift_last_error(); it reads the descriptor and the switch word only -- no data pointer is
+ * dereferenced (addresses count for their alignment), the device is not touched, `workspace` is not looked at (clift_gemm demands it for
+ * CLIFT_GEMM_ROUTE_SPLIT_TILED).  The four routes CLIFT_GEMM_ROUTE_LAYER_X6 .. WGRAD_N6 are the persistent split kernels of precision 2. */
+typedef enum {
+    CLIFT_GEMM_ROUTE_INVALID = -1,
+    CLIFT_GEMM_ROUTE_NONE = 0,          /* M == 0 or N == 0: nothing to launch */
+    /* precision 2 (fp32x6) */
+    CLIFT_GEMM_ROUTE_LAYER_X6,          /* csrc/layer_x6.hip: 256 x 256 forward / dgrad */
+    CLIFT_GEMM_ROUTE_WGRAD_X6,          /* csrc/layer_x6w.hip: 256 x 256 weight gradient */
+    CLIFT_GEMM_ROUTE_LAYER_N6,          /* csrc/layer_n6.hip: the 128-wide appearance layers, forward / dgrad */
+    CLIFT_GEMM_ROUTE_WGRAD_N6,          /* ... their weight gradients */
+    CLIFT_GEMM_ROUTE_SPLIT_TILED,       /* csrc/gemm_split.hip: any other forward / dgrad shape (needs the workspace) */
+    /* precision 0 (exact fp32), and every precision 2 form without a split kernel */
+    CLIFT_GEMM_ROUTE_LAYER_F32_FWD,     /* csrc/layer_f32.hip */
+    CLIFT_GEMM_ROUTE_LAYER_F32_DGRAD,
+    CLIFT_GEMM_ROUTE_DGRAD_NARROW,      /* csrc/narrow_stream.hip */
+    CLIFT_GEMM_ROUTE_WGRAD_F32_QUADS,   /* csrc/layer_n128.hip */
+    CLIFT_GEMM_ROUTE_WGRAD_N128,
+    CLIFT_GEMM_ROUTE_LAYER_N128,
+    CLIFT_GEMM_ROUTE_DGRAD_N160_PAIR,   /* LAYER_N128 on columns 0..127 + TILED_256X32 on columns 128..159 */
+    CLIFT_GEMM_ROUTE_TILED_128X256,     /* csrc/gemm.hip, by block tile */
+    CLIFT_GEMM_ROUTE_TILED_128X128,
+    CLIFT_GEMM_ROUTE_TILED_256X32,
+    /* precision 1 (bf16 operands) */
+    CLIFT_GEMM_ROUTE_LAYER_BF16,        /* csrc/layer_bf16.hip */
+    CLIFT_GEMM_ROUTE_WGRAD_BF16,
+    CLIFT_GEMM_ROUTE_DGRAD_NARROW_BF16, /* csrc/narrow_stream.hip, bf16-stored mask / result */
+    CLIFT_GEMM_ROUTE_LAYER_NB16,        /* csrc/layer_nb16.hip */
+    CLIFT_GEMM_ROUTE_WGRAD_NB16,
+    CLIFT_GEMM_ROUTE_TILED_BF16_128X256, /* csrc/gemm_bf16.hip, by block tile */
+    CLIFT_GEMM_ROUTE_TILED_BF16_128X128,
+    CLIFT_GEMM_ROUTE_TILED_BF16_256X32,
+    CLIFT_GEMM_ROUTE_COUNT
+} clift_gemm_route_t;
+int clift_gemm_route(const clift_gemm_t* h);
+const char* clift_gemm_route_name(int route);   /* "LAYER_X6", ...; "INVALID" for anything that is not a route */
 long clift_sign_bits_bytes(int M);
 
 /* Backward of a narrow output layer (no <= 32 outputs: 22 classes / 3 instance dims) over a 256-wide ReLU hidden layer in ONE pass over

@@ -227,12 +227,9 @@ def test_persistent_fp32_hidden_layer(M):
     out2 = torch.zeros((M, 256), device=DEV)
     engine.gemm(M, 256, 256, Ad, 256, Wd, 256, out2, 256)
     rel_close(out2, ref - bias.double(), 2e-5, atol=2e-5 * float(ref.abs().max()), what="persistent fp32 layer, plain")
-    os.environ["CLIFT_NO_PERSISTENT"] = "1"          # the tiled kernel on the same inputs
-    try:
+    with engine.kernel_switches(tiled_only=True):          # the tiled kernel on the same inputs
         out3 = torch.zeros((M, 256), device=DEV)
         engine.gemm(M, 256, 256, Ad, 256, Wd, 256, out3, 256)
-    finally:
-        del os.environ["CLIFT_NO_PERSISTENT"]
     scale = (A.abs().double() @ W.abs().double().T).to(DEV)
     assert float(((out2 - out3).abs().double() / scale).max()) <= 2e-6
     # masked dgrad of the same layer (k_layer_f32_dgrad): dX = mask . (dY W), W read along its rows
@@ -327,13 +324,10 @@ def test_narrow_wgrad_stream(M, no, ldd, xb):
         refb = dY[:, :no].double().sum(0) - 1.0
         rel_close(gW, refw, 2e-5, atol=2e-5 * float(refw.abs().max()), what="narrow wgrad (stream)")
         rel_close(gb, refb, 2e-5, atol=2e-5 * M ** 0.5, what="narrow bias sums (stream)")
-        os.environ["CLIFT_NO_PERSISTENT"] = "1"
-        try:
+        with engine.kernel_switches(tiled_only=True):
             gW2 = torch.full((no, 256), 0.25, device=DEV)
             gb2 = torch.full((no,), -1.0, device=DEV)
             engine.wgrad(no, 256, M, dY.to(DEV), ldd, X.to(DEV), 256, gW2, gb2)
-        finally:
-            del os.environ["CLIFT_NO_PERSISTENT"]
         rel_close(gW, gW2, 2e-5, atol=2e-5 * float(refw.abs().max()), what="stream vs VALU kernel")
     finally:
         engine.set_mlp_precision(prev)
@@ -435,13 +429,10 @@ def test_persistent_fp32_weight_gradient(M):
     refb = dY.double().sum(0) - 2.0
     rel_close(gW, refw, 2e-5, atol=2e-5 * float(refw.abs().max()), what="persistent wgrad")
     rel_close(gb, refb, 2e-5, atol=2e-5 * M ** 0.5, what="persistent wgrad bias sums")
-    os.environ["CLIFT_NO_PERSISTENT"] = "1"
-    try:
+    with engine.kernel_switches(tiled_only=True):
         gW2 = torch.full((256, 256), 0.5, device=DEV)
         gb2 = torch.full((256,), -2.0, device=DEV)
         engine.wgrad(256, 256, M, dYd, 256, Xd, 256, gW2, gb2)
-    finally:
-        del os.environ["CLIFT_NO_PERSISTENT"]
     rel_close(gW, gW2, 2e-5, atol=2e-5 * float(refw.abs().max()), what="persistent vs tiled wgrad")
 
 

@@ -414,12 +414,9 @@ def test_persistent_128_wide_layers(M):
         engine.gemm(M, 128, K, Ad, K, Wd, K, out, 132, bias=bd, act=1)
         rel_close(out[:M, :128], ref, 2e-5, atol=2e-5 * float(ref.abs().max()), what=f"persistent 128-wide forward K={K}")
         assert bool((out[M:] == -7.0).all()) and bool((out[:, 128:] == -7.0).all())
-        os.environ["CLIFT_NO_PERSISTENT"] = "1"
-        try:
+        with engine.kernel_switches(tiled_only=True):
             out3 = torch.zeros((M, 128), device=DEV)
             engine.gemm(M, 128, K, Ad, K, Wd, K, out3, 128, bias=bd, act=1)
-        finally:
-            del os.environ["CLIFT_NO_PERSISTENT"]
         scale = (A.abs().double() @ W.abs().double().T + bias.abs().double()).to(DEV)
         assert float(((out[:M, :128] - out3).abs().double() / scale).max()) <= 2e-6
     A = torch.randn((M, 128), generator=g)
@@ -711,7 +708,7 @@ def test_appearance_scatter_four_channel_lanes_match_one_channel_lanes(res, N, m
 @pytest.mark.parametrize("res,N", [((20, 28, 36), 700), ((64, 64, 64), 2048), ((128, 128, 128), 4096)])
 def test_density_scatter_wave_walk_matches_group_walk(res, N, monkeypatch):
     """clift_density_bwd in its wave-per-(ray, 32-sample chunk) form (index work of the chunk done once, serial walk with per-channel work
-    only) against the group-per-4-sample-segment walk (CLIFT_DENS_SCATTER=walk), with and without the forward's sigma: the same per-sample
+    only) against the group-per-4-sample-segment walk (kernel_switches(dens_scatter_walk=True)), with and without the forward's sigma: the same per-sample
     terms up to fp32 round-off, merged over longer runs, so every density plane / line gradient agrees to fp32 summation order."""
     cl, op, orender, ofld, olosses, orays = _import()
     C_, E = 9, 3
@@ -722,11 +719,11 @@ def test_density_scatter_wave_walk_matches_group_walk(res, N, monkeypatch):
     got = {}
     from contrastive_lift_amd import engine
     for mode in ("walk", "wave", "wave_nosigma"):
-        monkeypatch.setenv("CLIFT_DENS_SCATTER", mode.split("_")[0])
         monkeypatch.setattr(engine, "DENS_BWD_SIGMA", mode != "wave_nosigma")
         m = build_model(cl, P, res, C_, E, -3.0, "softmax")
         r = cl.TensoRFRenderer(aabb, list(res), semantic_weight_mode="softmax").to(DEV)
-        _, grads = _run_forward_backward(cl, m, r, rays, jitter, False, cots + [1.0])
+        with engine.kernel_switches(dens_scatter_walk=(mode == "walk")):
+            _, grads = _run_forward_backward(cl, m, r, rays, jitter, False, cots + [1.0])
         got[mode] = {k: (None if g is None else g.detach().cpu()) for k, g in grads.items()}
     n = 0
     for k, ref in got["walk"].items():
@@ -741,7 +738,7 @@ def test_density_scatter_wave_walk_matches_group_walk(res, N, monkeypatch):
 @pytest.mark.parametrize("M,no,ldd,ni", [(4099, 3, 4, 128), (249003, 3, 4, 128), (40001, 27, 28, 144), (8191, 27, 28, 144), (5000, 22, 24, 36), (4096, 8, 8, 252)])
 def test_narrow_wgrad_stream_on_narrower_activations(M, no, ldd, ni):
     """k_wgrad_narrow_stream with X narrower than 256 columns (the appearance output layer: 3 x 128; the appearance basis matrix: 27 x 144):
-    waves whose 32 columns start past the width only copy and wait.  Against fp64 and against the VALU kernel (CLIFT_NO_PERSISTENT),
+    waves whose 32 columns start past the width only copy and wait.  Against fp64 and against the VALU kernel (the tiled-only switch),
     accumulating onto existing contents, with and without a bias gradient, ragged row counts."""
     from contrastive_lift_amd import engine
     g = torch.Generator().manual_seed(M + no + ni)
@@ -753,16 +750,12 @@ def test_narrow_wgrad_stream_on_narrower_activations(M, no, ldd, ni):
     refb = dY[:, :no].double().sum(0) - 1.0
     outs = []
     for valu in (False, True):
-        if valu:
-            os.environ["CLIFT_NO_PERSISTENT"] = "1"
-        try:
+        with engine.kernel_switches(tiled_only=valu):
             gW = torch.full((no, ni), 0.25, device=DEV)
             gb = torch.full((no,), -1.0, device=DEV)
             engine.wgrad(no, ni, M, dYd, ldd, X, ni, gW, gb)
             gW_nb = torch.full((no, ni), 0.25, device=DEV)
             engine.call("clift_wgrad_narrow", engine.ptr(dYd), ldd, no, engine.ptr(X), ni, ni, M, engine.ptr(gW_nb), ni, None, 0, engine.stream())
-        finally:
-            os.environ.pop("CLIFT_NO_PERSISTENT", None)
         rel_close(gW, refw, 2e-5, atol=2e-5 * float(refw.abs().max()), what=f"narrow wgrad ni={ni} valu={valu}")
         rel_close(gb, refb, 2e-5, atol=2e-5 * M ** 0.5, what="bias sums")
         rel_close(gW_nb, refw, 2e-5, atol=2e-5 * float(refw.abs().max()), what="no-bias form")

@@ -215,9 +215,9 @@ def test_density_forward_one_wave_per_ray_is_the_per_thread_kernel_bit_for_bit(r
     assert S % 64 != 0
     out = []
     for form in ("ray", "thread"):
-        monkeypatch.setenv("CLIFT_DENS_FWD", form)
         sg = torch.full((n_rays, S), -1.0, device=DEV)
-        call("clift_density_fwd", C.byref(ms), C.byref(vd), ptr(rd), ptr(jitter), n_rays, ptr(sg), stream())
+        with engine.kernel_switches(dens_fwd_thread=(form == "thread")):
+            call("clift_density_fwd", C.byref(ms), C.byref(vd), ptr(rd), ptr(jitter), n_rays, ptr(sg), stream())
         torch.cuda.synchronize()
         out.append(sg)
     assert torch.equal(out[0], out[1])

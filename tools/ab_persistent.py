@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B on the GPU box: gradients of the mid-size parity scene with the persistent kernels (default) vs the tiled kernels
-(CLIFT_NO_PERSISTENT=1).  Same inputs; prints per tensor the largest difference relative to the tensor's scale and how many entries
+(engine.kernel_switches(tiled_only=True)).  Same inputs; prints per tensor the largest difference relative to the tensor's scale and how many entries
 differ by more than 1e-4 of it -- a handful of ReLU-kink / activity-threshold flips is expected, anything systematic is a bug."""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,12 +14,12 @@ P, rays, rng = scene(op, orays, 23, res, C_, E, n_rays, amp=2.2, sg=0.4)
 jitter = torch.from_numpy(rng.uniform(0, 1, n_rays).astype(np.float32))
 cots = [torch.from_numpy(rng.standard_normal(s).astype(np.float32)) for s in ((n_rays, 3), (n_rays, C_), (n_rays, 2 * E))]
 out = {}
+from contrastive_lift_amd import engine
 for tag in ("persistent", "tiled"):
-    if tag == "tiled":
-        os.environ["CLIFT_NO_PERSISTENT"] = "1"
     m = build_model(cl, P, res, C_, E, -3.0, "softmax")
     r = cl.TensoRFRenderer(aabb, list(res), semantic_weight_mode="softmax").to("cuda")
-    outs, grads = _run_forward_backward(cl, m, r, rays, jitter, False, cots + [3.0])
+    with engine.kernel_switches(tiled_only=(tag == "tiled")):
+        outs, grads = _run_forward_backward(cl, m, r, rays, jitter, False, cots + [3.0])
     out[tag] = (outs, {k: (None if g is None else g.detach().double().cpu()) for k, g in grads.items()})
 for i, nm in enumerate(("rgb", "sem", "inst")):
     a, b = out["persistent"][0][i].double().cpu(), out["tiled"][0][i].double().cpu()

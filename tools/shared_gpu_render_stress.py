@@ -27,4 +27,4 @@ for it in range(iters):
             if bad[n] <= 2:
                 d = (a != b); idx = torch.nonzero(d)
                 print(tag, n, "iter", it, "ndiff", int(d.sum()), "rows", torch.unique(idx[:, 0]).numel(), "first", idx[0].tolist(), flush=True)
-print(tag, mode, os.environ.get("CLIFT_X6_TILED"), f"{time.time()-t0:.1f}s mismatches of {iters}:", bad, flush=True)
+print(tag, mode, "switches", engine._lib.load().clift_get_switches(), f"{time.time()-t0:.1f}s mismatches of {iters}:", bad, flush=True)

@@ -54,8 +54,7 @@ for M in [int(x) for x in sys.argv[1:]] or [249000, 62000]:
     for name, f in (("fwd", fwd), ("dgrad", dgr)):
         t32 = run("fp32", lambda: timeit(f))
         tx6 = run("fp32x6", lambda: timeit(f))
-        os.environ["CLIFT_X6_TILED"] = "1"
-        txt = run("fp32x6", lambda: timeit(f))
-        del os.environ["CLIFT_X6_TILED"]
+        with engine.kernel_switches(x6_tiled=True):
+            txt = run("fp32x6", lambda: timeit(f))
         print(f"{name} 256x256 M={M}: exact persistent {t32:7.1f} us ({fl/t32/1e6:6.1f} TF)   x6 persistent {tx6:7.1f} us ({fl/tx6/1e6:6.1f} TF-equiv, "
               f"{2*4*M*256/tx6/1e3:5.0f} GB/s)   x6 tiled {txt:7.1f} us")
