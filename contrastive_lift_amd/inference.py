@@ -346,15 +346,32 @@ def psnr(image_pred, image_gt):
 
 
 class ConfusionMatrix:
-    """util/metrics.py:29-75: confusion counts + robust mIoU (classes that are rare in both marginals are ignored)."""
+    """util/metrics.py:29-75: confusion counts + robust mIoU (classes that are rare in both marginals are ignored).
+    ``backend="device"`` / ``"counts"``: the counts come from one label-overlap count per batch (overlap.py: classes against classes, one
+    frame; ground truth outside [0, n) is dropped like the host mask does) -- "device" takes CUDA tensors as they are.  ``add_batch`` may
+    name another backend for one batch."""
 
-    def __init__(self, num_classes, ignore_class=None, robust=0.005):
-        self.n, self.ignore, self.robust = num_classes, list(ignore_class or []), robust
+    def __init__(self, num_classes, ignore_class=None, robust=0.005, backend="host"):
+        from . import overlap
+        self.n, self.ignore, self.robust, self.backend = num_classes, list(ignore_class or []), robust, overlap.check_backend(backend)
         self.cm = np.zeros((num_classes, num_classes))
 
     def _matrix(self, gt, pred):
         m = (gt >= 0) & (gt < self.n)
         return np.bincount(self.n * gt[m].astype(int) + pred[m], minlength=self.n ** 2).reshape(self.n, self.n)
+
+    def _matrix_counted(self, gt, pred, backend):
+        from . import overlap
+        counter = overlap.Counter(backend, gt.device if torch.is_tensor(gt) and gt.is_cuda else None)
+        gt, pred = counter.labels(gt), counter.labels(pred)
+        if gt.shape[0] != pred.shape[0]:
+            raise ValueError("ground truth and prediction differ in size")
+        n = self.n
+        a_base = np.concatenate([np.arange(n), [-1]]).astype(np.int32)[None]                  # class n = "outside [0, n)": dropped
+        pred = counter.int32(pred, *counter.extremes([pred])[0])
+        counts = counter.count(counter.remap_outside(gt, n), None, pred, None, [0, int(gt.shape[0])], a_base, np.zeros((1, n + 1), np.int32),
+                               np.arange(n, dtype=np.int32)[None], np.zeros((1, n), np.int32), n, n)
+        return counter.host(counts)[0]
 
     def _miou(self, cm):
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -365,8 +382,13 @@ class ConfusionMatrix:
             iou[i] = np.nan
         return np.nanmean(iou)
 
-    def add_batch(self, gt_image, pre_image, return_miou=False):
-        cm = self._matrix(np.asarray(gt_image), np.asarray(pre_image))
+    def add_batch(self, gt_image, pre_image, return_miou=False, backend=None):
+        from . import overlap
+        backend = self.backend if backend is None else overlap.check_backend(backend)
+        if backend == "host":
+            cm = self._matrix(np.asarray(gt_image), np.asarray(pre_image))
+        else:
+            cm = self._matrix_counted(gt_image, pre_image, backend)
         self.cm += cm
         if return_miou:
             return self._miou(cm)

@@ -539,6 +539,24 @@ int clift_segment_moments(const float* pts, long n, const long* seg, int G, cons
 int clift_segment_extent(const float* pts, long n, const long* seg, int G, const unsigned char* keep, const double* frame, double* out,
                          clift_stream_t s);
 
+/* ---- scoring (ABI 22; csrc/overlap.hip): the joint histogram of two label maps, per frame, after a per-frame class remapping -- the table under
+ * panoptic quality, the confusion matrix and the robust-class shares (contrastive_lift_amd/overlap.py).  Everything is DEVICE memory.  a_cls,
+ * a_inst, b_cls, b_inst: (P) int32 rows, P = frame_off[F]; frame_off (F + 1) int64, non-decreasing from 0: frame f owns rows frame_off[f] ..
+ * frame_off[f+1] (may be empty).  a_base, a_stride (F, Ca) and b_base, b_stride (F, Cb) int32: the slot of row i of frame f on side a is
+ *     sa = a_base[f][a_cls[i]] + a_stride[f][a_cls[i]] * a_inst[i]        (sb likewise),
+ * and the row adds 1 to counts[f][sa][sb], counts (F, NA, NB) int32.  In this order: a row whose class is outside [0, Ca) resp. [0, Cb) on either
+ * side is REJECTED; else a row with a negative base on either side is DROPPED (counted nowhere: classes the caller leaves out, invalid pixels);
+ * else a row with a non-zero stride and a NULL instance array or a negative instance id, or with a slot outside [0, NA) resp. [0, NB), on either
+ * side is REJECTED.  A rejected row adds 1 to rejected[f] (F) and nothing else; the caller reads rejected and raises.  No address outside counts
+ * and rejected is ever written.  a_inst / b_inst may be NULL when every stride of that side is 0.  The call clears counts and rejected on the
+ * stream itself, neither allocates nor synchronises (P is read on the device: the caller vouches that the row arrays hold frame_off[F] rows and
+ * that the offsets are monotone -- a piece of a non-monotone list is skipped or counted twice, never followed out of the row range).  Integer
+ * adds only: two runs give the same bits.  Errors (clift_last_error): F < 0, NA or NB or Ca or Cb < 1, NA * NB >= 2^31, a NULL required
+ * buffer.  F == 0 returns 0 at once; frame_off[F] == 0 leaves the cleared tables.  NA * NB <= 8192 counts in a block-private LDS table. */
+int clift_label_overlap(const int* a_cls, const int* a_inst, const int* b_cls, const int* b_inst, const long* frame_off, int F,
+                        const int* a_base, const int* a_stride, int Ca, const int* b_base, const int* b_stride, int Cb, int NA, int NB,
+                        int* counts, int* rejected, clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
