@@ -273,7 +273,7 @@ def _splits(out_rows, out_cols, K):
     return max(1, min((K + 255) // 256, (512 + tiles - 1) // tiles))
 
 
-def _lin_params(seq, views_prefix, views):
+def _lin_params(views_prefix, views):
     """[(W, b)] of an nn.Sequential MLP, fetched from a name->tensor dict (parameter or gradient views)."""
     out = []
     j = 0
@@ -708,7 +708,25 @@ def grid_head_bwd(model, views, gviews, ctx, st, nets, keep):
 
 # ----------------------------------------------------------------------------- forward
 class RenderCtx:
-    pass
+    """What a forward pass leaves for its backward (and for the trainer, the bench and the tools, which read M, N, capped, soak, ...).  Every
+    attribute a pass may set is declared here; one that a pass did not reach keeps its default."""
+
+    def __init__(self):
+        self.ms = self.res = self.rays = self.jitter = None                     # the march (_density_march)
+        self.sigma = self.alpha = self.T = self.w = self.ray_out = self.ray_start = self.act_idx = None
+        self.N = self.S = self.M = 0
+        self.capped = False                  # a sync-free chunk: M is the capacity, the row count stays on the device (ray_start[N])
+        self.white_bg = self.softmax_mode = self.stop_grad = self.C = self.D = 0
+        self.want = (False, False, False)    # (colour, semantic, instance) outputs composited
+        self.xa = None                       # (M, 4) positions of the active samples
+        self.rgb_s = self.sem_s = self.inst_s = None         # per-sample head outputs
+        self.rgb_raw = self.sem_raw = None                   # per-ray sums before background / normalisation
+        self.w_feat = None                   # "argmax" weights: the one-hot array the semantic and instance sums were taken with
+        self.F = self.feat = self.X = self.H1 = self.H2 = None                  # the appearance chain ("app" in grad_heads)
+        self.ldf = self.nf = self.ldx = 0
+        self.soak = None                     # SOAK_KEEP: references to the appearance chain's intermediates
+        self.sem_acts = self.inst_fast_acts = self.inst_slow_acts = None        # hidden activations of the xyz heads
+        self.sem_grid = self.inst_grid = None                                   # state of a head on its own grid (grid_head_fwd)
 
 
 INT_MAX = 2 ** 31 - 1
@@ -817,6 +835,70 @@ def _check_rays(rays, jitter):
     return rays, jitter
 
 
+_HEAD_MLPS = {"app": "render_appearance_mlp.mlp", "sem": "render_semantic_mlp.mlp", "fast": "render_instance_mlp.mlp",
+              "slow": "render_instance_mlp.slow_mlp"}
+
+
+def _head_params(views):
+    """{head: [(W, b)]} of the appearance, semantic, fast- and slow-instance MLPs (empty where the field has none), fetched once per pass from
+    the parameter views -- and, by the backward, from the gradient views."""
+    return {head: _lin_params(prefix, views) for head, prefix in _HEAD_MLPS.items()}
+
+
+def _head_chains(model, views, ctx, params, grad_heads, want_sem):
+    """The forward of the semantic head (``want_sem``) and of the instance head (ctx.D > 0) over the chunk's active samples, as
+    [(Branches slot, chain)]: the heads are independent of each other and of the appearance chain.  xyz MLPs or heads on their own VM grids;
+    the instance head's fast and slow nets write the two halves of ctx.inst_s.  A head named in ``grad_heads`` keeps its activations."""
+    M, dev, D = ctx.M, ctx.rays.device, ctx.D
+    chains = []
+    if want_sem:
+        def sem_chain(keep):
+            Ccls = ctx.C
+            sem_s = torch.empty((M, Ccls), dtype=torch.float32, device=dev)
+            sm = 2 if model.render_semantic_mlp.softmax else 0
+            if model.semantic_plane is not None:           # the head on its own VM grid
+                ctx.sem_grid = grid_head_fwd(model, views, ctx, "semantic", [(params["sem"], sem_s, Ccls, 0)], "sem" in grad_heads, sm)
+            else:
+                ctx.sem_acts = xyz_mlp_fwd(params["sem"], ctx.xa, M, sem_s, Ccls, keep_first="sem" in grad_heads, out_act=sm)
+            ctx.sem_s = sem_s
+        chains.append((1, sem_chain))
+    if D > 0:
+        E = model.render_instance_mlp.output_channels
+        ctx.inst_s = torch.empty((M, D), dtype=torch.float32, device=dev)
+        if model.instance_plane is not None:           # the head on its own VM grid: fast and slow nets read the same features
+            nets = [(params["fast"], ctx.inst_s, D, 0)] + ([(params["slow"], ctx.inst_s, D, E)] if model.slow_fast_mode else [])
+
+            def inst_grid_chain(keep):
+                ctx.inst_grid = grid_head_fwd(model, views, ctx, "instance", nets, "fast" in grad_heads or "slow" in grad_heads)
+            chains.append((2, inst_grid_chain))
+        else:
+            def fast_chain(keep):
+                ctx.inst_fast_acts = xyz_mlp_fwd(params["fast"], ctx.xa, M, ctx.inst_s, D, 0, keep_first="fast" in grad_heads)
+
+            def slow_chain(keep):
+                ctx.inst_slow_acts = xyz_mlp_fwd(params["slow"], ctx.xa, M, ctx.inst_s, D, E, keep_first="slow" in grad_heads)
+            chains.append((2, fast_chain))
+            if model.slow_fast_mode:
+                chains.append((3, slow_chain))
+    return chains
+
+
+def _composite_sides(ctx, colour, feats):
+    """What a compositing launch takes of the pass when the colour sums (``colour``) and / or the semantic and instance sums (``feats``) take part:
+    pointer selectors for the tensors of either side, the class and instance-feature counts, softmax_mode and white_bg."""
+    return ((lambda t: ptr(t) if colour else None), (lambda t: ptr(t) if feats else None), ctx.C if (feats and ctx.want[1]) else 0,
+            ctx.D if feats else 0, ctx.softmax_mode if feats else 0, ctx.white_bg if colour else 0)
+
+
+def _composite_fwd(ctx, w, out, colour=True, feats=True):
+    """One clift_composite_fwd launch over the weight array ``w`` (None: a chunk without active samples, backgrounds and zeros only) into
+    out = (rgb_raw, rgb_map, sem_raw, sem_map, inst_map)."""
+    rgb_raw, rgb_map, sem_raw, sem_map, inst_map = out
+    c, f, n_sem, D, softmax_mode, white_bg = _composite_sides(ctx, colour, feats)
+    call("clift_composite_fwd", ptr(w), ptr(ctx.ray_start), ptr(ctx.act_idx), ctx.N, n_sem, D, c(ctx.rgb_s), f(ctx.sem_s), f(ctx.inst_s), ptr(ctx.ray_out),
+         softmax_mode, white_bg, c(rgb_raw), c(rgb_map), f(sem_raw), f(sem_map), f(inst_map), stream())
+
+
 def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_sem=True, want_inst=True, grad_heads=("app", "sem", "fast", "slow"),
                    cap=None, want_dist=True):
     """Full renderer.forward (reference renderer.py:80-176).  Returns dict of outputs and the backward context.
@@ -830,11 +912,12 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
     st = stream()
     Ccls = model.num_semantic_classes
     D = model.dim_feature_instance if (want_inst and model.render_instance_mlp is not None) else 0
-    softmax_mode = 1 if renderer.semantic_weight_mode == "softmax" else 0
-    ctx.white_bg, ctx.softmax_mode, ctx.stop_grad = int(bool(white_bg)), softmax_mode, int(bool(renderer.stop_semantic_grad))
+    ctx.softmax_mode = 1 if renderer.semantic_weight_mode == "softmax" else 0
+    ctx.white_bg, ctx.stop_grad = int(bool(white_bg)), int(bool(renderer.stop_semantic_grad))
     ctx.C, ctx.D = Ccls, D
-    ctx.rgb_s = ctx.sem_s = ctx.inst_s = None
+    ctx.want = (want_rgb, want_sem, D > 0)
     if M > 0:
+        params = _head_params(views)
         xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
         ctx.xa = xa
         front = None
@@ -865,92 +948,59 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
 
         def app_chain(keep):
             with _app_precision():
-                _app_chain_fwd(keep)
-
-        def _app_chain_fwd(keep):
-            Wb = views["appearance_basis_mat.weight"]
-            nf, nc = Wb.shape
-            (W1, b1), (W2, b2), (W3, b3) = _lin_params(None, "render_appearance_mlp.mlp", views)
-            ldx = _pitch(W1)
-            hdt = act_dtype() if ldx % 8 == 0 else torch.float32      # bf16 mode: encoded input and hidden activations bf16-stored
-            if front is not None:
-                feat, ldf, X = front
-            else:
-                ldf = (nf + 3) // 4 * 4
-                feat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
-                with exact_fp32():          # (the basis Linear is not one of the bf16 layers in any mode)
-                    gemm(M, nf, nc, ctx.F, nc, Wb, _pitch(Wb), feat, ldf)
-                X = torch.empty((M, ldx), dtype=hdt, device=dev)
-                call("clift_app_encode_fwd", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(rays), ptr(ctx.act_idx), S, M,
-                     ptr(X), ldx, int(hdt == torch.bfloat16), stream())
-            H1 = torch.empty((M, W1.shape[0]), dtype=hdt, device=dev)
-            gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
-            rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
-            if (MLP_PRECISION in (0, 2) and hdt == torch.float32 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128
-                    and persistent_ok()):
-                # second hidden layer + output layer + sigmoid in one launch; H2 is written only for a backward
-                H2 = torch.empty((M, 128), dtype=torch.float32, device=dev) if "app" in grad_heads else None
-                if MLP_PRECISION == 2 and persistent_x6_ok():        # (only inside _app_precision() with APP_X6)
-                    call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
+                Wb = views["appearance_basis_mat.weight"]
+                nf, nc = Wb.shape
+                (W1, b1), (W2, b2), (W3, b3) = params["app"]
+                ldx = _pitch(W1)
+                hdt = act_dtype() if ldx % 8 == 0 else torch.float32      # bf16 mode: encoded input and hidden activations bf16-stored
+                if front is not None:
+                    feat, ldf, X = front
+                else:
+                    ldf = (nf + 3) // 4 * 4
+                    feat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
+                    with exact_fp32():          # (the basis Linear is not one of the bf16 layers in any mode)
+                        gemm(M, nf, nc, ctx.F, nc, Wb, _pitch(Wb), feat, ldf)
+                    X = torch.empty((M, ldx), dtype=hdt, device=dev)
+                    call("clift_app_encode_fwd", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(rays), ptr(ctx.act_idx), S, M,
+                         ptr(X), ldx, int(hdt == torch.bfloat16), stream())
+                H1 = torch.empty((M, W1.shape[0]), dtype=hdt, device=dev)
+                gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
+                rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
+                if (MLP_PRECISION in (0, 2) and hdt == torch.float32 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128
+                        and persistent_ok()):
+                    # second hidden layer + output layer + sigmoid in one launch; H2 is written only for a backward
+                    H2 = torch.empty((M, 128), dtype=torch.float32, device=dev) if "app" in grad_heads else None
+                    if MLP_PRECISION == 2 and persistent_x6_ok():        # (only inside _app_precision() with APP_X6)
+                        call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
+                             ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
+                    else:
+                        app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
+                elif (MLP_PRECISION == 1 and hdt == torch.bfloat16 and H1.dtype == torch.bfloat16 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4
+                        and W3.shape[1] == 128 and M >= 64 and persistent_ok()):
+                    # bf16 mode: the same pair of layers over the bf16-stored activation (csrc/layer_nb16.hip)
+                    H2 = torch.empty((M, 128), dtype=torch.bfloat16, device=dev) if "app" in grad_heads else None
+                    call("clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
                          ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
                 else:
-                    app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
-            elif (MLP_PRECISION == 1 and hdt == torch.bfloat16 and H1.dtype == torch.bfloat16 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4
-                    and W3.shape[1] == 128 and M >= 64 and persistent_ok()):
-                # bf16 mode: the same pair of layers over the bf16-stored activation (csrc/layer_nb16.hip)
-                H2 = torch.empty((M, 128), dtype=torch.bfloat16, device=dev) if "app" in grad_heads else None
-                call("clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
-                     ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
-            else:
-                H2 = torch.empty((M, W2.shape[0]), dtype=hdt, device=dev)
-                gemm(M, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
-                pre = torch.empty((M, 3), dtype=torch.float32, device=dev)
-                gemm(M, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
-                call("clift_rows_act_fwd", ptr(pre), 3, M, 3, 1, ptr(rgb_s), 3, stream())
-                keep.append(pre)
-            ctx.rgb_s = rgb_s
-            if SOAK_KEEP:
-                ctx.soak = dict(feat=feat, X=X, H1=H1)
-            if "app" in grad_heads:
-                ctx.feat, ctx.ldf, ctx.nf, ctx.X, ctx.ldx, ctx.H1, ctx.H2 = feat, ldf, nf, X, ldx, H1, H2
-            else:
-                ctx.F = None
-
-        def sem_chain(keep):
-            sem_layers = _lin_params(None, "render_semantic_mlp.mlp", views)
-            sem_s = torch.empty((M, Ccls), dtype=torch.float32, device=dev)
-            sm = 2 if model.render_semantic_mlp.softmax else 0
-            if model.semantic_plane is not None:           # the head on its own VM grid
-                ctx.sem_grid = grid_head_fwd(model, views, ctx, "semantic", [(sem_layers, sem_s, Ccls, 0)], "sem" in grad_heads, sm)
-            else:
-                ctx.sem_acts = xyz_mlp_fwd(sem_layers, xa, M, sem_s, Ccls, keep_first="sem" in grad_heads, out_act=sm)
-            ctx.sem_s = sem_s
+                    H2 = torch.empty((M, W2.shape[0]), dtype=hdt, device=dev)
+                    gemm(M, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
+                    pre = torch.empty((M, 3), dtype=torch.float32, device=dev)
+                    gemm(M, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
+                    call("clift_rows_act_fwd", ptr(pre), 3, M, 3, 1, ptr(rgb_s), 3, stream())
+                    keep.append(pre)
+                ctx.rgb_s = rgb_s
+                if SOAK_KEEP:
+                    ctx.soak = dict(feat=feat, X=X, H1=H1)
+                if "app" in grad_heads:
+                    ctx.feat, ctx.ldf, ctx.nf, ctx.X, ctx.ldx, ctx.H1, ctx.H2 = feat, ldf, nf, X, ldx, H1, H2
+                else:
+                    ctx.F = None
 
         br = Branches(model=model)
         if want_rgb:
             br.run(0, app_chain)
-        if want_sem:
-            br.run(1, sem_chain)
-        if D > 0:
-            E = model.render_instance_mlp.output_channels
-            ctx.inst_s = torch.empty((M, D), dtype=torch.float32, device=dev)
-
-            def fast_chain(keep):
-                ctx.inst_fast_acts = xyz_mlp_fwd(_lin_params(None, "render_instance_mlp.mlp", views), xa, M, ctx.inst_s, D, 0,
-                                                 keep_first="fast" in grad_heads)
-
-            def slow_chain(keep):
-                ctx.inst_slow_acts = xyz_mlp_fwd(_lin_params(None, "render_instance_mlp.slow_mlp", views), xa, M, ctx.inst_s, D, E,
-                                                 keep_first="slow" in grad_heads)
-            if model.instance_plane is not None:           # the head on its own VM grid: fast and slow nets read the same features
-                nets = [(_lin_params(None, "render_instance_mlp.mlp", views), ctx.inst_s, D, 0)]
-                if model.slow_fast_mode:
-                    nets.append((_lin_params(None, "render_instance_mlp.slow_mlp", views), ctx.inst_s, D, E))
-                br.run(2, lambda keep: setattr(ctx, "inst_grid", grid_head_fwd(model, views, ctx, "instance", nets, "fast" in grad_heads or "slow" in grad_heads)))
-            else:
-                br.run(2, fast_chain)
-                if model.slow_fast_mode:
-                    br.run(3, slow_chain)
+        for slot, chain in _head_chains(model, views, ctx, params, grad_heads, want_sem):
+            br.run(slot, chain)
         br.join()
     # (the sum kernel writes every (ray, channel) when there are heads to sum; only a chunk without active samples needs the zeros)
     fresh = torch.empty if M > 0 else torch.zeros
@@ -959,33 +1009,66 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
     sem_raw = fresh((N, Ccls), dtype=torch.float32, device=dev) if want_sem else None
     sem_map = torch.empty((N, Ccls), dtype=torch.float32, device=dev) if want_sem else None
     inst_map = fresh((N, D), dtype=torch.float32, device=dev) if D > 0 else None
-    ctx.w_feat = None
+    out = (rgb_raw, rgb_map, sem_raw, sem_map, inst_map)
     if M > 0 and renderer.semantic_weight_mode == "argmax" and (want_sem or D > 0):
         # renderer.py:142-143: the semantic / instance sums take the one-hot of each ray's heaviest sample (of ALL its samples: a heaviest
         # sample below the threshold is not in the list and the ray's sums stay 0, as in the reference, whose heads are 0 there); the colours
         # keep the weights -- two passes of the compositing kernels, one per weight array
         ctx.w_feat = torch.zeros_like(ctx.w).scatter_(1, ctx.w.argmax(dim=1, keepdim=True), 1.0)
         if want_rgb:
-            call("clift_composite_fwd", ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx), N, 0, 0, ptr(ctx.rgb_s), None, None, ptr(ctx.ray_out), 0,
-                 ctx.white_bg, ptr(rgb_raw), ptr(rgb_map), None, None, None, st)
-        call("clift_composite_fwd", ptr(ctx.w_feat), ptr(ctx.ray_start), ptr(ctx.act_idx), N, Ccls if want_sem else 0, D, None, ptr(ctx.sem_s),
-             ptr(ctx.inst_s), ptr(ctx.ray_out), softmax_mode, 0, None, None, ptr(sem_raw), ptr(sem_map), ptr(inst_map), st)
-    elif M > 0:
-        call("clift_composite_fwd", ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx), N, Ccls if want_sem else 0, D,
-             ptr(ctx.rgb_s), ptr(ctx.sem_s), ptr(ctx.inst_s), ptr(ctx.ray_out), softmax_mode, ctx.white_bg,
-             ptr(rgb_raw), ptr(rgb_map), ptr(sem_raw), ptr(sem_map), ptr(inst_map), st)
-    else:   # no active sample in the chunk (reference: the `if appearance_mask.any()` branch is skipped)
-        call("clift_composite_fwd", None, ptr(ctx.ray_start), ptr(ctx.act_idx), N, Ccls if want_sem else 0, D,
-             None, None, None, ptr(ctx.ray_out), softmax_mode, ctx.white_bg,
-             ptr(rgb_raw), ptr(rgb_map), ptr(sem_raw), ptr(sem_map), ptr(inst_map), st)
+            _composite_fwd(ctx, ctx.w, out, feats=False)
+        _composite_fwd(ctx, ctx.w_feat, out, colour=False)
+    else:   # (no active sample in the chunk -- reference: the `if appearance_mask.any()` branch is skipped -- no weights and no head outputs)
+        _composite_fwd(ctx, ctx.w if M > 0 else None, out)
     ctx.rgb_raw, ctx.sem_raw = rgb_raw, sem_raw
-    ctx.want = (want_rgb, want_sem, D > 0)
     out = dict(rgb=rgb_map, semantics=sem_map, instances=inst_map, depth=ctx.ray_out[:, 1],
                dist_reg=ctx.ray_out[:, 5].mean() if want_dist else None, opacity=ctx.ray_out[:, 0])     # (the trainer never reads the VALUE of the regulariser)
     return out, ctx
 
 
 # ----------------------------------------------------------------------------- backward
+def _composite_bwd(ctx, w, grads, rows, colour=True, feats=True, wgrad=True):
+    """One clift_composite_bwd launch over the weight array ``w``: per-sample gradients w.r.t. the heads' ACTIVATED outputs into
+    rows = (d_rgb, d_sem, d_inst) and -- ``wgrad`` -- the weight and opacity gradients.  grads = (g_rgb, g_sem, g_inst, ge (scratch), g_w, g_op)."""
+    (g_rgb, g_sem, g_inst, ge, g_w, g_op), (d_rgb, d_sem, d_inst) = grads, rows
+    c, f, n_sem, D, softmax_mode, white_bg = _composite_sides(ctx, colour, feats)
+    call("clift_composite_bwd", ptr(w), ptr(ctx.ray_start), ptr(ctx.act_idx), ctx.N, ctx.S, ctx.M, n_sem, D, c(ctx.rgb_s), f(ctx.sem_s), f(ctx.inst_s),
+         c(ctx.rgb_raw), f(ctx.sem_raw), softmax_mode, white_bg, ctx.stop_grad if (feats and wgrad) else 1, c(g_rgb), f(g_sem), f(g_inst), ptr(ge),
+         c(d_rgb), f(d_sem), f(d_inst), ptr(g_w) if wgrad else None, ptr(g_op) if wgrad else None, stream())
+
+
+def _composite_bwd_act(ctx, w, grads, rows, sem_kind, E_inst, colour=True, feats=True, wgrad=True):
+    """One clift_composite_bwd_act launch: _composite_bwd with the heads' output activations (sigmoid / ``sem_kind`` / identity) taken back in the
+    same kernel.  rows = (d_rgb (M, 4), d_sem, d_inst, d_inst_slow): the zero-padded PRE-activation gradient rows the heads' backward kernels
+    start from; the instance row splits into the fast and the slow net's (``E_inst`` columns each; d_inst_slow None: not wanted)."""
+    (g_rgb, g_sem, g_inst, ge, g_w, g_op), (d_rgb, d_sem, d_inst, d_inst_slow) = grads, rows
+    c, f, n_sem, D, softmax_mode, white_bg = _composite_sides(ctx, colour, feats)
+    ldp_sem, ldp_inst = ((ctx.C + 3) // 4 * 4, (E_inst + 3) // 4 * 4) if feats else (4, 4)
+    call("clift_composite_bwd_act", ptr(w), ptr(ctx.act_idx), ctx.N, ctx.S, ctx.M, n_sem, D, c(ctx.rgb_s), f(ctx.sem_s), f(ctx.inst_s),
+         c(ctx.rgb_raw), f(ctx.sem_raw), softmax_mode, white_bg, ctx.stop_grad if (feats and wgrad) else 1, c(g_rgb), f(g_sem), f(g_inst), ptr(ge),
+         sem_kind if feats else 0, c(d_rgb), 4, f(d_sem), ldp_sem, f(d_inst), f(d_inst_slow), ldp_inst, E_inst if feats else 0,
+         ptr(g_w) if wgrad else None, ptr(g_op) if wgrad else None, stream())
+
+
+def _head_dpre(fused_row, y, d, off, n, kind, M):
+    """d loss / d pre-activation output of a head, (M, n padded to a multiple of 4): ``fused_row`` where the compositing backward has already
+    taken the activation back (act_fused), else one clift_rows_act_bwd launch (``kind`` 0 identity / 1 sigmoid / 2 row softmax) over columns
+    [off, off + n) of the gradient ``d`` w.r.t. the activated output ``y`` (None for the identity)."""
+    if fused_row is not None:
+        return fused_row
+    ldp = (n + 3) // 4 * 4
+    dpre = torch.empty((M, ldp), dtype=torch.float32, device=d.device)
+    call("clift_rows_act_bwd", ptr(y), y.shape[1] if y is not None else 0, C.c_void_p(d.data_ptr() + 4 * off), d.shape[1], M, n, kind, ptr(dpre), ldp,
+         stream())
+    return dpre
+
+
+def _kept_grid_head(st):
+    if st["F"] is None:
+        raise _lib.CliftError("backward through a grid head whose forward ran without keeping its activations (head not named in grad_heads)")
+    return st
+
+
 def render_backward(model, ctx, gviews, g_rgb=None, g_sem=None, g_inst=None, g_dist=None, density_grad=True,
                     slow_grad=False, before_density=None):
     """Accumulate parameter gradients into ``gviews`` (name -> tensor with the parameter's layout).
@@ -995,9 +1078,8 @@ def render_backward(model, ctx, gviews, g_rgb=None, g_sem=None, g_inst=None, g_d
     views = model.named_views()
     N, S, M = ctx.N, ctx.S, ctx.M
     dev = ctx.rays.device
-    st = stream()
     global _limit_owner
-    if getattr(ctx, "capped", False):
+    if ctx.capped:
         if _limit_owner is not ctx:        # another chunk was marched since: put THIS chunk's row count back (device-to-device, 4 bytes)
             rows_limit(dev)[0:1].copy_(ctx.ray_start[N:N + 1])
             _limit_owner = ctx
@@ -1016,47 +1098,32 @@ def render_backward(model, ctx, gviews, g_rgb=None, g_sem=None, g_inst=None, g_d
         g_w = torch.empty((N, S), dtype=torch.float32, device=dev)
         g_op = torch.empty((N,), dtype=torch.float32, device=dev)
     if M > 0 and (g_rgb is not None or g_sem is not None or g_inst is not None):
-        ge = torch.empty((N, 3 + Ccls + D), dtype=torch.float32, device=dev)
+        params, gparams = _head_params(views), _head_params(gviews)
+        slow_grad = bool(slow_grad and model.slow_fast_mode)
         E_inst = model.render_instance_mlp.output_channels if (D > 0 and model.render_instance_mlp is not None) else 0
+        sem_kind = 2 if (model.render_semantic_mlp is not None and model.render_semantic_mlp.softmax) else 0
         act_fused = COMPOSITE_ACT_FUSED and (D == 0 or (E_inst >= 1 and 2 * E_inst >= D))
+        mk = lambda on, cols: torch.empty((M, cols), dtype=torch.float32, device=dev) if on else None
+        grads = (g_rgb, g_sem, g_inst, torch.empty((N, 3 + Ccls + D), dtype=torch.float32, device=dev), g_w, g_op)
         if act_fused:
             # the heads' output activations (sigmoid / softmax / identity) are taken back inside the compositing backward: what it writes are the
             # zero-padded pre-activation gradient rows the heads' backward kernels start from
-            ldp_sem, ldp_inst = (Ccls + 3) // 4 * 4, (E_inst + 3) // 4 * 4
-            d_rgb = torch.empty((M, 4), dtype=torch.float32, device=dev) if g_rgb is not None else None
-            d_sem = torch.empty((M, ldp_sem), dtype=torch.float32, device=dev) if g_sem is not None else None
-            d_inst = torch.empty((M, ldp_inst), dtype=torch.float32, device=dev) if g_inst is not None else None
-            d_inst_slow = (torch.empty((M, ldp_inst), dtype=torch.float32, device=dev)
-                           if (g_inst is not None and model.slow_fast_mode and slow_grad) else None)
-            sem_kind = 2 if (model.render_semantic_mlp is not None and model.render_semantic_mlp.softmax) else 0
-            if getattr(ctx, "w_feat", None) is not None:
-                # "argmax" weights (render_forward): the colours against the weights (with the weight / opacity gradients), then the semantic and
-                # instance rows against the one-hot array, which carries no gradient
-                call("clift_composite_bwd_act", ptr(ctx.w), ptr(ctx.act_idx), N, S, M, 0, 0, ptr(ctx.rgb_s), None, None, ptr(ctx.rgb_raw), None, 0,
-                     ctx.white_bg, 1, ptr(g_rgb), None, None, ptr(ge), 0, ptr(d_rgb), 4, None, 4, None, None, 4, 0, ptr(g_w), ptr(g_op), st)
-                call("clift_composite_bwd_act", ptr(ctx.w_feat), ptr(ctx.act_idx), N, S, M, Ccls if want_sem else 0, D, None, ptr(ctx.sem_s),
-                     ptr(ctx.inst_s), None, ptr(ctx.sem_raw), ctx.softmax_mode, 0, 1, None, ptr(g_sem), ptr(g_inst), ptr(ge), sem_kind, None, 4,
-                     ptr(d_sem), ldp_sem, ptr(d_inst), ptr(d_inst_slow), ldp_inst, E_inst, None, None, st)
-            else:
-                call("clift_composite_bwd_act", ptr(ctx.w), ptr(ctx.act_idx), N, S, M, Ccls if want_sem else 0, D,
-                     ptr(ctx.rgb_s), ptr(ctx.sem_s), ptr(ctx.inst_s), ptr(ctx.rgb_raw), ptr(ctx.sem_raw), ctx.softmax_mode,
-                     ctx.white_bg, ctx.stop_grad, ptr(g_rgb), ptr(g_sem), ptr(g_inst), ptr(ge), sem_kind, ptr(d_rgb), 4, ptr(d_sem), ldp_sem,
-                     ptr(d_inst), ptr(d_inst_slow), ldp_inst, E_inst, ptr(g_w), ptr(g_op), st)
+            ldp_inst = (E_inst + 3) // 4 * 4
+            d_rgb, d_sem, d_inst = mk(g_rgb is not None, 4), mk(g_sem is not None, (Ccls + 3) // 4 * 4), mk(g_inst is not None, ldp_inst)
+            d_inst_slow = mk(g_inst is not None and slow_grad, ldp_inst)
+            pre_rgb, pre_sem, pre_fast, pre_slow = d_rgb, d_sem, d_inst, d_inst_slow
+            composite = lambda w, **which: _composite_bwd_act(ctx, w, grads, (d_rgb, d_sem, d_inst, d_inst_slow), sem_kind, E_inst, **which)
+        else:       # (gradients w.r.t. the activated outputs: every head chain starts with its own clift_rows_act_bwd launch)
+            d_rgb, d_sem, d_inst = mk(g_rgb is not None, 3), mk(g_sem is not None, Ccls), mk(g_inst is not None, D)
+            pre_rgb = pre_sem = pre_fast = pre_slow = None
+            composite = lambda w, **which: _composite_bwd(ctx, w, grads, (d_rgb, d_sem, d_inst), **which)
+        if ctx.w_feat is not None:
+            # "argmax" weights (render_forward): the colours against the weights (with the weight / opacity gradients), then the semantic and
+            # instance rows against the one-hot array, which carries no gradient
+            composite(ctx.w, feats=False)
+            composite(ctx.w_feat, colour=False, wgrad=False)
         else:
-            d_rgb = torch.empty((M, 3), dtype=torch.float32, device=dev) if g_rgb is not None else None
-            d_sem = torch.empty((M, Ccls), dtype=torch.float32, device=dev) if g_sem is not None else None
-            d_inst = torch.empty((M, D), dtype=torch.float32, device=dev) if g_inst is not None else None
-            if getattr(ctx, "w_feat", None) is not None:      # "argmax" weights: as above
-                call("clift_composite_bwd", ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx), N, S, M, 0, 0, ptr(ctx.rgb_s), None, None,
-                     ptr(ctx.rgb_raw), None, 0, ctx.white_bg, 1, ptr(g_rgb), None, None, ptr(ge), ptr(d_rgb), None, None, ptr(g_w), ptr(g_op), st)
-                call("clift_composite_bwd", ptr(ctx.w_feat), ptr(ctx.ray_start), ptr(ctx.act_idx), N, S, M, Ccls if want_sem else 0, D, None,
-                     ptr(ctx.sem_s), ptr(ctx.inst_s), None, ptr(ctx.sem_raw), ctx.softmax_mode, 0, 1, None, ptr(g_sem), ptr(g_inst), ptr(ge), None,
-                     ptr(d_sem), ptr(d_inst), None, None, st)
-            else:
-                call("clift_composite_bwd", ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx), N, S, M, Ccls if want_sem else 0, D,
-                     ptr(ctx.rgb_s), ptr(ctx.sem_s), ptr(ctx.inst_s), ptr(ctx.rgb_raw), ptr(ctx.sem_raw), ctx.softmax_mode,
-                     ctx.white_bg, ctx.stop_grad, ptr(g_rgb), ptr(g_sem), ptr(g_inst), ptr(ge), ptr(d_rgb), ptr(d_sem), ptr(d_inst),
-                     ptr(g_w), ptr(g_op), st)
+            composite(ctx.w)
         br = Branches(model=model)
         if density_grad:
             model.xcd_workspace_for("density")
@@ -1066,117 +1133,79 @@ def render_backward(model, ctx, gviews, g_rgb=None, g_sem=None, g_inst=None, g_d
         # ---------------- appearance head
         def app_chain(keep):
             with _app_precision():
-                _app_chain_bwd(keep)
-
-        def _app_chain_bwd(keep):
-            app = _lin_params(None, "render_appearance_mlp.mlp", views)
-            gapp = _lin_params(None, "render_appearance_mlp.mlp", gviews)
-            (W1, b1), (W2, b2), (W3, b3) = app
-            (gW1, gb1), (gW2, gb2), (gW3, gb3) = gapp
-            if act_fused:
-                dpre = d_rgb
-            else:
-                dpre = torch.empty((M, 4), dtype=torch.float32, device=dev)
-                call("clift_rows_act_bwd", ptr(ctx.rgb_s), 3, ptr(d_rgb), 3, M, 3, 1, ptr(dpre), 4, stream())
-            H1, H2, X, ldx = ctx.H1, ctx.H2, ctx.X, ctx.ldx
-            n2 = W3.shape[1]
-            dH2 = torch.empty((M, n2), dtype=H2.dtype, device=dev)
-            if (APP_OUT_BWD_FUSED and H2.dtype == torch.float32 and n2 % 32 == 0 and n2 <= 256 and W3.shape[0] <= 4 and M >= 4096
-                    and _pitch(W3) >= n2 and _pitch(gW3) >= n2 and persistent_ok()):
-                # output layer: weight gradient and masked input gradient in one pass over the hidden activation (as in the xyz heads)
-                call("clift_out_layer_bwd_nh", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), n2, n2, M, ptr(dH2), n2, ptr(gW3), _pitch(gW3),
-                     ptr(gb3), 0, stream())
-            elif (APP_OUT_BWD_FUSED and MLP_PRECISION == 1 and H2.dtype == torch.bfloat16 and n2 == 128 and W3.shape[0] <= 4 and dpre.shape[1] == 4
-                    and _pitch(W3) >= 128 and _pitch(gW3) >= 128 and persistent_ok()):
-                # bf16 mode: the same one pass over the bf16-stored activation; the input gradient leaves bf16-stored
-                call("clift_out_layer_bwd_n128_bf16", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), 128, M, ptr(dH2), 128, ptr(gW3), _pitch(gW3),
-                     ptr(gb3), stream())
-            else:
-                wgrad(3, n2, M, dpre, 4, H2, n2, gW3, gb3)
-                gemm(M, n2, 3, dpre, 4, W3, _pitch(W3), dH2, n2, b_trans=1, mask=H2, ldmask=n2)
-            n1 = W2.shape[1]
-            wgrad(n2, n1, M, dH2, n2, H1, n1, gW2, gb2)
-            dH1 = torch.empty((M, n1), dtype=H1.dtype, device=dev)
-            gemm(M, n1, n2, dH2, n2, W2, _pitch(W2), dH1, n1, b_trans=1, mask=H1, ldmask=n1)
-            wgrad(n1, ldx, M, dH1, n1, X, ldx, gW1, gb1)
-            dX = torch.empty((M, ldx), dtype=torch.float32, device=dev)
-            gemm(M, ldx, n1, dH1, n1, W1, ldx, dX, ldx, b_trans=1)
-            nf, ldf = ctx.nf, ctx.ldf
-            Wb, gWb = views["appearance_basis_mat.weight"], gviews["appearance_basis_mat.weight"]
-            nc = Wb.shape[1]
-            va = vm_struct(views, "appearance", ctx.res)
-            ga = vm_grad_struct(model, gviews, "appearance")
-            dfeat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
-            call("clift_app_encode_bwd", ptr(ctx.feat), ldf, nf, model.pe_feat, ptr(dX), ldx, M, ptr(dfeat), ldf, stream())
-            call("clift_wgrad_narrow", ptr(dfeat), ldf, nf, ptr(ctx.F), nc, nc, M, ptr(gWb), _pitch(gWb), None, 0, stream())
-            dF = torch.empty((M, nc), dtype=torch.float32, device=dev)
-            with exact_fp32():              # (the basis Linear is not one of the bf16 layers in any mode)
-                gemm(M, nc, nf, dfeat, ldf, Wb, _pitch(Wb), dF, nc, b_trans=1)
-            call("clift_app_gather_bwd", C.byref(ctx.ms), C.byref(va), C.byref(ga), ptr(ctx.rays), ptr(ctx.jitter),
-                 ptr(ctx.act_idx), M, ptr(dF), ptr(ctx.xa) if APP_SCATTER_XA else None, stream())
-            vm_grad_finish(model, gviews, "appearance", ga)
-            keep.extend([dpre, dH2, dH1, dX, dfeat, dF])
+                (W1, b1), (W2, b2), (W3, b3) = params["app"]
+                (gW1, gb1), (gW2, gb2), (gW3, gb3) = gparams["app"]
+                dpre = _head_dpre(pre_rgb, ctx.rgb_s, d_rgb, 0, 3, 1, M)
+                H1, H2, X, ldx = ctx.H1, ctx.H2, ctx.X, ctx.ldx
+                n2 = W3.shape[1]
+                dH2 = torch.empty((M, n2), dtype=H2.dtype, device=dev)
+                if (APP_OUT_BWD_FUSED and H2.dtype == torch.float32 and n2 % 32 == 0 and n2 <= 256 and W3.shape[0] <= 4 and M >= 4096
+                        and _pitch(W3) >= n2 and _pitch(gW3) >= n2 and persistent_ok()):
+                    # output layer: weight gradient and masked input gradient in one pass over the hidden activation (as in the xyz heads)
+                    call("clift_out_layer_bwd_nh", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), n2, n2, M, ptr(dH2), n2, ptr(gW3), _pitch(gW3),
+                         ptr(gb3), 0, stream())
+                elif (APP_OUT_BWD_FUSED and MLP_PRECISION == 1 and H2.dtype == torch.bfloat16 and n2 == 128 and W3.shape[0] <= 4 and dpre.shape[1] == 4
+                        and _pitch(W3) >= 128 and _pitch(gW3) >= 128 and persistent_ok()):
+                    # bf16 mode: the same one pass over the bf16-stored activation; the input gradient leaves bf16-stored
+                    call("clift_out_layer_bwd_n128_bf16", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), 128, M, ptr(dH2), 128, ptr(gW3), _pitch(gW3),
+                         ptr(gb3), stream())
+                else:
+                    wgrad(3, n2, M, dpre, 4, H2, n2, gW3, gb3)
+                    gemm(M, n2, 3, dpre, 4, W3, _pitch(W3), dH2, n2, b_trans=1, mask=H2, ldmask=n2)
+                n1 = W2.shape[1]
+                wgrad(n2, n1, M, dH2, n2, H1, n1, gW2, gb2)
+                dH1 = torch.empty((M, n1), dtype=H1.dtype, device=dev)
+                gemm(M, n1, n2, dH2, n2, W2, _pitch(W2), dH1, n1, b_trans=1, mask=H1, ldmask=n1)
+                wgrad(n1, ldx, M, dH1, n1, X, ldx, gW1, gb1)
+                dX = torch.empty((M, ldx), dtype=torch.float32, device=dev)
+                gemm(M, ldx, n1, dH1, n1, W1, ldx, dX, ldx, b_trans=1)
+                nf, ldf = ctx.nf, ctx.ldf
+                Wb, gWb = views["appearance_basis_mat.weight"], gviews["appearance_basis_mat.weight"]
+                nc = Wb.shape[1]
+                va = vm_struct(views, "appearance", ctx.res)
+                ga = vm_grad_struct(model, gviews, "appearance")
+                dfeat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
+                call("clift_app_encode_bwd", ptr(ctx.feat), ldf, nf, model.pe_feat, ptr(dX), ldx, M, ptr(dfeat), ldf, stream())
+                call("clift_wgrad_narrow", ptr(dfeat), ldf, nf, ptr(ctx.F), nc, nc, M, ptr(gWb), _pitch(gWb), None, 0, stream())
+                dF = torch.empty((M, nc), dtype=torch.float32, device=dev)
+                with exact_fp32():              # (the basis Linear is not one of the bf16 layers in any mode)
+                    gemm(M, nc, nf, dfeat, ldf, Wb, _pitch(Wb), dF, nc, b_trans=1)
+                call("clift_app_gather_bwd", C.byref(ctx.ms), C.byref(va), C.byref(ga), ptr(ctx.rays), ptr(ctx.jitter),
+                     ptr(ctx.act_idx), M, ptr(dF), ptr(ctx.xa) if APP_SCATTER_XA else None, stream())
+                vm_grad_finish(model, gviews, "appearance", ga)
+                keep.extend([dpre, dH2, dH1, dX, dfeat, dF])
 
         # ---------------- semantic head
         def sem_chain(keep):
-            if act_fused:
-                dpre = d_sem
+            dpre = _head_dpre(pre_sem, ctx.sem_s, d_sem, 0, Ccls, sem_kind, M)
+            if ctx.sem_grid is not None:
+                grid_head_bwd(model, views, gviews, ctx, _kept_grid_head(ctx.sem_grid), [(params["sem"], gparams["sem"], ctx.sem_grid["acts"][0], dpre)], keep)
             else:
-                ldp = (Ccls + 3) // 4 * 4
-                dpre = torch.empty((M, ldp), dtype=torch.float32, device=dev)
-                kind = 2 if model.render_semantic_mlp.softmax else 0
-                call("clift_rows_act_bwd", ptr(ctx.sem_s), Ccls, ptr(d_sem), Ccls, M, Ccls, kind, ptr(dpre), ldp, stream())
-            if getattr(ctx, "sem_grid", None) is not None:
-                st_ = ctx.sem_grid
-                if st_["F"] is None:
-                    raise _lib.CliftError("backward through a grid head whose forward ran without keeping its activations (head not named in grad_heads)")
-                grid_head_bwd(model, views, gviews, ctx, st_, [(_lin_params(None, "render_semantic_mlp.mlp", views),
-                                                                _lin_params(None, "render_semantic_mlp.mlp", gviews), st_["acts"][0], dpre)], keep)
-                return
-            xyz_mlp_bwd(_lin_params(None, "render_semantic_mlp.mlp", views), _lin_params(None, "render_semantic_mlp.mlp", gviews),
-                        ctx.xa, ctx.sem_acts, dpre, M, keep)
+                xyz_mlp_bwd(params["sem"], gparams["sem"], ctx.xa, ctx.sem_acts, dpre, M, keep)
 
-        # ---------------- instance heads
-        def inst_chain(prefix, acts, off):
+        # ---------------- instance head: the fast net's half of the row, and -- slow_grad -- the slow net's
+        inst_nets = [("fast", pre_fast, 0, ctx.inst_fast_acts)] + ([("slow", pre_slow, E_inst, ctx.inst_slow_acts)] if slow_grad else [])
+
+        def inst_chain(head, fused_row, off, acts):
             def run(keep):
-                E = model.render_instance_mlp.output_channels
-                if act_fused:
-                    dpre = d_inst if off == 0 else d_inst_slow
-                else:
-                    ldp = (E + 3) // 4 * 4
-                    dpre = torch.empty((M, ldp), dtype=torch.float32, device=dev)
-                    call("clift_rows_act_bwd", None, 0, C.c_void_p(d_inst.data_ptr() + 4 * off), D, M, E, 0, ptr(dpre), ldp, stream())
-                xyz_mlp_bwd(_lin_params(None, prefix, views), _lin_params(None, prefix, gviews), ctx.xa, acts, dpre, M, keep)
+                xyz_mlp_bwd(params[head], gparams[head], ctx.xa, acts, _head_dpre(fused_row, None, d_inst, off, E_inst, 0, M), M, keep)
             return run
+
+        def inst_grid_chain(keep):
+            st_ = _kept_grid_head(ctx.inst_grid)
+            nets = [(params[head], gparams[head], st_["acts"][i], _head_dpre(fused_row, None, d_inst, off, E_inst, 0, M))
+                    for i, (head, fused_row, off, _) in enumerate(inst_nets)]
+            grid_head_bwd(model, views, gviews, ctx, st_, nets, keep)
 
         if d_rgb is not None:
             br.run(0, app_chain)
         if d_sem is not None:
             br.run(1, sem_chain)
-        if d_inst is not None and getattr(ctx, "inst_grid", None) is not None:
-            def inst_grid_chain(keep):
-                st_ = ctx.inst_grid
-                if st_["F"] is None:
-                    raise _lib.CliftError("backward through a grid head whose forward ran without keeping its activations (head not named in grad_heads)")
-                E_ = model.render_instance_mlp.output_channels
-                ldp = (E_ + 3) // 4 * 4
-
-                def pre(off, fused):
-                    if act_fused:
-                        return fused
-                    dp = torch.empty((M, ldp), dtype=torch.float32, device=dev)
-                    call("clift_rows_act_bwd", None, 0, C.c_void_p(d_inst.data_ptr() + 4 * off), D, M, E_, 0, ptr(dp), ldp, stream())
-                    return dp
-                nets = [(_lin_params(None, "render_instance_mlp.mlp", views), _lin_params(None, "render_instance_mlp.mlp", gviews), st_["acts"][0], pre(0, d_inst))]
-                if model.slow_fast_mode and slow_grad:
-                    nets.append((_lin_params(None, "render_instance_mlp.slow_mlp", views), _lin_params(None, "render_instance_mlp.slow_mlp", gviews),
-                                 st_["acts"][1], pre(E_, d_inst_slow)))
-                grid_head_bwd(model, views, gviews, ctx, st_, nets, keep)
+        if d_inst is not None and ctx.inst_grid is not None:
             br.run(2, inst_grid_chain)
         elif d_inst is not None:
-            br.run(2, inst_chain("render_instance_mlp.mlp", ctx.inst_fast_acts, 0))
-            if model.slow_fast_mode and slow_grad:
-                br.run(3, inst_chain("render_instance_mlp.slow_mlp", ctx.inst_slow_acts, model.render_instance_mlp.output_channels))
+            for i, net in enumerate(inst_nets):
+                br.run(2 + i, inst_chain(*net))
         if density_grad:
             if before_density is not None:
                 if br.enabled:
@@ -1219,59 +1248,32 @@ def feature_forward(model, renderer, rays, jitter, head, grad_heads=("app", "sem
     rays, jitter = _check_rays(rays, jitter)
     views = model.named_views()
     ctx = _density_march(model, renderer, rays, jitter, cap)
-    N, S, M = ctx.N, ctx.S, ctx.M
+    N, M = ctx.N, ctx.M
     dev = rays.device
-    st = stream()
     ctx.white_bg, ctx.stop_grad = 0, 1
     ctx.softmax_mode = 1 if (head == "semantic" and renderer.semantic_weight_mode == "softmax") else 0
     Ccls = model.num_semantic_classes if head == "semantic" else 0
     D = model.dim_feature_instance if head == "instance" else 0
     ctx.C, ctx.D = Ccls, D
-    ctx.rgb_s = ctx.sem_s = ctx.inst_s = None
-    ctx.rgb_raw = None
+    ctx.want = (False, head == "semantic", head == "instance")
     if M > 0:
-        xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
-        ctx.xa = xa
-        call("clift_active_xyz", C.byref(ctx.ms), ptr(rays), ptr(jitter), ptr(ctx.act_idx), M, ptr(xa), st)
-        if head == "semantic":
-            layers = _lin_params(None, "render_semantic_mlp.mlp", views)
-            ctx.sem_s = torch.empty((M, Ccls), dtype=torch.float32, device=dev)
-            sm = 2 if model.render_semantic_mlp.softmax else 0
-            if model.semantic_plane is not None:
-                ctx.sem_grid = grid_head_fwd(model, views, ctx, "semantic", [(layers, ctx.sem_s, Ccls, 0)], "sem" in grad_heads, sm)
-            else:
-                ctx.sem_acts = xyz_mlp_fwd(layers, xa, M, ctx.sem_s, Ccls, keep_first="sem" in grad_heads, out_act=sm)
-        elif model.instance_plane is not None:
-            E = model.render_instance_mlp.output_channels
-            ctx.inst_s = torch.empty((M, D), dtype=torch.float32, device=dev)
-            nets = [(_lin_params(None, "render_instance_mlp.mlp", views), ctx.inst_s, D, 0)]
-            if model.slow_fast_mode:
-                nets.append((_lin_params(None, "render_instance_mlp.slow_mlp", views), ctx.inst_s, D, E))
-            ctx.inst_grid = grid_head_fwd(model, views, ctx, "instance", nets, "fast" in grad_heads or "slow" in grad_heads)
-        else:
-            E = model.render_instance_mlp.output_channels
-            ctx.inst_s = torch.empty((M, D), dtype=torch.float32, device=dev)
+        ctx.xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        call("clift_active_xyz", C.byref(ctx.ms), ptr(rays), ptr(jitter), ptr(ctx.act_idx), M, ptr(ctx.xa), stream())
+        chains = _head_chains(model, views, ctx, _head_params(views), grad_heads, head == "semantic")
+        if head == "instance" and model.instance_plane is None:       # the fast and the slow xyz net: two branches
             br = Branches(model=model)
-
-            def fast_chain(keep):
-                ctx.inst_fast_acts = xyz_mlp_fwd(_lin_params(None, "render_instance_mlp.mlp", views), xa, M, ctx.inst_s, D, 0,
-                                                 keep_first="fast" in grad_heads)
-
-            def slow_chain(keep):
-                ctx.inst_slow_acts = xyz_mlp_fwd(_lin_params(None, "render_instance_mlp.slow_mlp", views), xa, M, ctx.inst_s, D, E,
-                                                 keep_first="slow" in grad_heads)
-            br.run(2, fast_chain)
-            if model.slow_fast_mode:
-                br.run(3, slow_chain)
+            for slot, chain in chains:
+                br.run(slot, chain)
             br.join()
+        else:       # the semantic head, the instance head on its grid: one chain, on the main stream
+            for _, chain in chains:
+                chain([])
     fresh = torch.empty if M > 0 else torch.zeros          # (as in render_forward: the sums are written in full unless the chunk is empty)
     sem_raw = fresh((N, Ccls), dtype=torch.float32, device=dev) if Ccls else None
     sem_map = torch.empty((N, Ccls), dtype=torch.float32, device=dev) if Ccls else None
     inst_map = fresh((N, D), dtype=torch.float32, device=dev) if D else None
-    call("clift_composite_fwd", ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx), N, Ccls, D, None, ptr(ctx.sem_s), ptr(ctx.inst_s),
-         ptr(ctx.ray_out), ctx.softmax_mode, 0, None, None, ptr(sem_raw), ptr(sem_map), ptr(inst_map), st)
+    _composite_fwd(ctx, ctx.w, (None, None, sem_raw, sem_map, inst_map), colour=False)
     ctx.sem_raw = sem_raw
-    ctx.want = (False, head == "semantic", head == "instance")
     if head == "instance":
         # renderer.py:213-215 (the trainer asks for the points only where its loss reads them: two elementwise launches otherwise unused)
         xyz = rays[:, 0:3] + ctx.ray_out[:, 1:2] * rays[:, 3:6] if want_xyz else None
@@ -1307,26 +1309,8 @@ def density_points(model, xyz, activation=True):
     return out
 
 
-@torch.no_grad()
-def appearance_feature_points(model, xyz):
-    """TensorVMSplit.compute_appearance_feature: VM products + basis Linear (no gradient)."""
-    x = _points(xyz)
-    reset_rows_limit(x.device)
-    n = x.shape[0]
-    views = model.named_views()
-    va = vm_struct(views, "appearance", grid_res(views))
-    nc = 3 * va.comps
-    F = torch.empty((n, nc), dtype=torch.float32, device=x.device)
-    call("clift_vm_products_points", C.byref(va), ptr(x), x.shape[1], n, ptr(F), stream())
-    Wb = views["appearance_basis_mat.weight"]
-    out = torch.empty((n, Wb.shape[0]), dtype=torch.float32, device=x.device)
-    gemm(n, Wb.shape[0], nc, F, nc, Wb, _pitch(Wb), out, out.shape[1])
-    return out
-
-
-@torch.no_grad()
-def grid_feature_points(model, prefix, xyz):
-    """TensorVMSplit.compute_semantic_feature / compute_instance_feature for a head on its own VM grid: VM products + basis Linear (no gradient)."""
+def _basis_feature_points(model, prefix, xyz, precision):
+    """VM products of the ``prefix`` tables at the points + basis Linear, the GEMM under the context ``precision``."""
     x = _points(xyz)
     reset_rows_limit(x.device)
     n = x.shape[0]
@@ -1337,9 +1321,22 @@ def grid_feature_points(model, prefix, xyz):
     call("clift_vm_products_points", C.byref(vm), ptr(x), x.shape[1], n, ptr(F), stream())
     Wb = views[f"{prefix}_basis_mat.weight"]
     out = torch.empty((n, Wb.shape[0]), dtype=torch.float32, device=x.device)
-    with exact_fp32():
+    with precision:
         gemm(n, Wb.shape[0], nc, F, nc, Wb, _pitch(Wb), out, out.shape[1])
     return out
+
+
+@torch.no_grad()
+def appearance_feature_points(model, xyz):
+    """TensorVMSplit.compute_appearance_feature: VM products + basis Linear (no gradient), the GEMM at the precision that is set."""
+    return _basis_feature_points(model, "appearance", xyz, contextlib.nullcontext())
+
+
+@torch.no_grad()
+def grid_feature_points(model, prefix, xyz):
+    """TensorVMSplit.compute_semantic_feature / compute_instance_feature for a head on its own VM grid: VM products + basis Linear (no gradient),
+    the GEMM exact as in grid_head_fwd."""
+    return _basis_feature_points(model, prefix, xyz, exact_fp32())
 
 
 @torch.no_grad()

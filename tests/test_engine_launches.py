@@ -1,0 +1,263 @@
+"""What the engine launches, pinned without a GPU: render / feature passes and the point-wise utilities run on CPU stand-in tensors with
+``engine.call`` replaced by a recorder (engine_recorder.py), and every launch -- entry point, scalars, NULL-ness, which buffer each pointer is
+in and where, struct fields, clift_gemm routes -- is compared with tests/golden/engine_launches.json, recorded from the engine as it stood
+before its head / compositing sequences were gathered into shared helpers.
+
+``cases()`` enumerates 860 cases on a 16^3 field, 64 rays, 22 classes, 6 instance features, the active-row count dictated by the stand-in:
+  * one baseline per (mode, field, M, pass): modes fp32 / bf16 / fp32x6; fields = xyz heads with and without slow-fast, the semantic head on
+    its own grid, the instance head on its own grid with slow-fast, both on grids; M in {0, 63, 300, 4096} (the code's thresholds are
+    M >= 64 and M >= 4096, M == 0 skips the heads); passes = render forward + backward with grad_heads all four / the trainer's main-pass
+    set / () (forward only), the instance feature pass with slow_grad off / on, the semantic feature pass                          (360)
+  * the sync-free (cap=) render passes, fp32 and fp32x6                                                                            (80)
+  * semantic_weight_mode argmax / none, white background, argmax on white, on the slow-fast xyz field and the all-grid field; the
+    semantic feature pass without softmax weights                                                                                  (120)
+  * slow-fast xyz field, M = 4096, one at a time: each fusion flag cleared, KEEP_FIRST_ACT set, kernel_switches(tiled_only=True),
+    kernel_switches(x6_tiled=True)                                                                                                 (234)
+  * COMPOSITE_ACT_FUSED cleared on the grid fields and together with argmax weights (the remaining compositing call sites)          (63)
+  * the point-wise utilities, once per mode                                                                                         (3)
+The golden file holds, per case, the sequence of entry points (indices into ``names``) and the sha256 of the full record, plus the sha256 of
+the enumeration.  ``python tests/test_engine_launches.py --dump DIR`` writes the full records, one JSON file per case, for diffing two trees;
+``--golden`` rewrites the golden file from the tree it runs in."""
+import contextlib
+import hashlib
+import json
+import os
+import sys
+
+import pytest
+import torch
+
+from conftest import REPO
+from engine_recorder import Recorder
+
+GOLDEN = os.path.join(REPO, "tests", "golden", "engine_launches.json")
+GRID, RAYS, CLASSES, DIM_INST = 16, 64, 22, 6
+MODES = ("fp32", "bf16", "fp32x6")
+ROWS = (0, 63, 300, 4096)
+FIELDS = {   # TensorVMSplit arguments
+    "xyz_sf": dict(use_semantic_mlp=True, use_instance_mlp=True, slow_fast_mode=True),
+    "xyz": dict(use_semantic_mlp=True, use_instance_mlp=True, slow_fast_mode=False),
+    "sem_grid": dict(use_semantic_mlp=False, num_semantics_comps=(32, 32, 32), use_instance_mlp=True, slow_fast_mode=True),
+    "inst_grid_sf": dict(use_semantic_mlp=True, use_instance_mlp=False, num_instance_comps=(32, 32, 32), slow_fast_mode=True),
+    "both_grid": dict(use_semantic_mlp=False, num_semantics_comps=(32, 32, 32), use_instance_mlp=False, num_instance_comps=(32, 32, 32),
+                      slow_fast_mode=False),
+}
+PASSES = ("render_all", "render_main", "render_fwd", "feat_inst", "feat_inst_slow", "feat_sem")
+CLEARED = ("APP_FRONT_FUSED", "COMPOSITE_ACT_FUSED", "APP_OUT_BWD_FUSED", "FUSE_HEAD_BF16", "FIRST2_BF16_BWD_FUSED", "OUT_BWD_BF16_FUSED",
+           "APP_SCATTER_XA", "DENS_BWD_SIGMA", "APP_BF16", "APP_X6")
+VARIATIONS = tuple("-" + f for f in CLEARED) + ("+KEEP_FIRST_ACT", "tiled_only", "x6_tiled")
+KEYS = ("mode", "field", "M", "pass", "weights", "white", "cap", "vary")
+
+
+def cases():
+    out = []
+
+    def add(mode, field, M, pas, weights="softmax", white=0, cap=0, vary=""):
+        out.append(dict(zip(KEYS, (mode, field, M, pas, weights, white, cap, vary))))
+
+    for mode in MODES:
+        for field in FIELDS:
+            for M in ROWS:
+                for pas in PASSES:
+                    add(mode, field, M, pas)
+                if mode != "bf16":
+                    add(mode, field, M, "render_all", cap=1)
+                    add(mode, field, M, "render_main", cap=1)
+        for field in ("xyz_sf", "both_grid"):
+            for M in ROWS:
+                for weights, white in (("argmax", 0), ("none", 0), ("softmax", 1), ("argmax", 1)):
+                    add(mode, field, M, "render_all", weights=weights, white=white)
+                add(mode, field, M, "feat_sem", weights="none")
+        for vary in VARIATIONS:
+            for pas in PASSES:
+                add(mode, "xyz_sf", 4096, pas, vary=vary)
+        for field in ("sem_grid", "both_grid"):
+            for pas in ("render_all", "feat_inst_slow", "feat_sem"):
+                add(mode, field, 4096, pas, vary="-COMPOSITE_ACT_FUSED")
+            add(mode, field, 300, "render_all", vary="-COMPOSITE_ACT_FUSED")
+        # (not with slow_grad: at the recorded commit the slow net of a grid instance head could not be differentiated with this flag cleared --
+        # the unfused branch never defined the fused slow row that the chain named, a NameError)
+        for pas in ("render_main", "feat_inst", "feat_sem"):
+            add(mode, "inst_grid_sf", 4096, pas, vary="-COMPOSITE_ACT_FUSED")
+        for field in ("xyz_sf", "both_grid"):
+            for M in (300, 4096):
+                for white in (0, 1):
+                    add(mode, field, M, "render_all", weights="argmax", white=white, vary="-COMPOSITE_ACT_FUSED")
+        add(mode, "xyz_sf", 4096, "render_main", weights="argmax", vary="-COMPOSITE_ACT_FUSED")
+        add(mode, "xyz_sf", 4096, "render_main", weights="argmax")
+        add(mode, "-", 301, "points")
+    return out
+
+
+def case_name(c):
+    return "/".join(str(c[k]) for k in KEYS)
+
+
+def cases_sha256(cs):
+    return hashlib.sha256(json.dumps([[c[k] for k in KEYS] for c in cs]).encode()).hexdigest()
+
+
+# ----------------------------------------------------------------------------- running one case
+_models = {}
+
+
+def field_on_cpu(kind, grid=GRID, classes=CLASSES, dim_inst=DIM_INST):
+    import contrastive_lift_amd as cl
+    key = (kind, grid, classes, dim_inst)
+    if key not in _models:
+        torch.manual_seed(0)
+        _models[key] = cl.TensorVMSplit([grid] * 3, num_semantic_classes=classes, dim_feature_instance=dim_inst, splus_density_shift=-3.0, device="cpu",
+                                        **FIELDS[kind])
+    return _models[key]
+
+
+def renderer_on_cpu(weights, grid=GRID):
+    import contrastive_lift_amd as cl
+    return cl.TensoRFRenderer(torch.tensor([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]]), [grid] * 3, semantic_weight_mode=weights, step_ratio=0.5)
+
+
+@contextlib.contextmanager
+def variation(vary):
+    from contrastive_lift_amd import engine
+    if vary in ("tiled_only", "x6_tiled"):
+        with engine.kernel_switches(**{vary: True}):
+            yield
+    elif vary:
+        name, prev = vary[1:], getattr(engine, vary[1:])
+        setattr(engine, name, vary[0] == "+")
+        try:
+            yield
+        finally:
+            setattr(engine, name, prev)
+    else:
+        yield
+
+
+def run_pass(engine, model, renderer, pas, rays, jitter, white, cap, n_classes, dim_inst):
+    """One forward (+ backward) of the engine; returns the context."""
+    N, gv = rays.shape[0], model.named_grad_views()
+    g = lambda *shape: torch.ones(shape, dtype=torch.float32, device=rays.device)
+    if pas == "render_all":
+        _, ctx = engine.render_forward(model, renderer, rays, jitter, white, cap=cap)
+        engine.render_backward(model, ctx, gv, g(N, 3), g(N, n_classes), g(N, dim_inst), g(1), density_grad=True, slow_grad=True)
+    elif pas == "render_main":       # (the trainer's main pass)
+        _, ctx = engine.render_forward(model, renderer, rays, jitter, white, grad_heads=("app", "sem"), want_dist=False, cap=cap)
+        engine.render_backward(model, ctx, gv, g(N, 3), g(N, n_classes), None, None, density_grad=True)
+    elif pas == "render_fwd":
+        _, ctx = engine.render_forward(model, renderer, rays, jitter, white, grad_heads=(), cap=cap)
+    elif pas in ("feat_inst", "feat_inst_slow"):
+        _, ctx = engine.feature_forward(model, renderer, rays, jitter, "instance", cap=cap)
+        engine.feature_backward(model, ctx, gv, g(N, dim_inst), slow_grad=pas == "feat_inst_slow")
+    else:
+        _, ctx = engine.feature_forward(model, renderer, rays, jitter, "semantic", cap=cap)
+        engine.feature_backward(model, ctx, gv, g(N, n_classes))
+    return ctx
+
+
+def run_points(engine, n):
+    xyz = torch.zeros((n, 3), dtype=torch.float32)
+    m = field_on_cpu("xyz_sf")
+    engine.density_points(m, xyz)
+    engine.density_points(m, xyz, activation=False)
+    feats = engine.appearance_feature_points(m, xyz)
+    engine.appearance_mlp_points(m.render_appearance_mlp, xyz, feats)
+    engine.xyz_mlp_points(m.render_semantic_mlp.mlp, xyz)
+    engine.xyz_mlp_points(m.render_instance_mlp.slow_mlp, xyz)
+    m = field_on_cpu("both_grid")
+    engine.feat_mlp_points(m.render_semantic_mlp.mlp, engine.grid_feature_points(m, "semantic", xyz))
+    engine.feat_mlp_points(m.render_instance_mlp.mlp, engine.grid_feature_points(m, "instance", xyz))
+
+
+def record(c, pointers=True):
+    """The launches of one case: [[entry point, arguments(, route)], ...]."""
+    from contrastive_lift_amd import engine
+    prev = engine.set_mlp_precision(c["mode"])
+    try:
+        with variation(c["vary"]):
+            if c["pass"] == "points":
+                models = [field_on_cpu("xyz_sf"), field_on_cpu("both_grid")]
+                with Recorder(roots=lambda: [m.param_flat for m in models], pointers=pointers) as rec:
+                    run_points(engine, c["M"])
+                return rec.launches
+            model, renderer = field_on_cpu(c["field"]), renderer_on_cpu(c["weights"])
+            rays, jitter = torch.zeros((RAYS, 8), dtype=torch.float32), torch.zeros((RAYS,), dtype=torch.float32)
+            roots = lambda: [model.param_flat, model.grad_flat, rays, jitter] + list(model.__dict__.get("_xcd_ws", {}).values())
+            with Recorder(active=c["M"], roots=roots, pointers=pointers) as rec:
+                run_pass(engine, model, renderer, c["pass"], rays, jitter, bool(c["white"]), c["M"] if c["cap"] else None, CLASSES, DIM_INST)
+            return rec.launches
+    finally:
+        engine.set_mlp_precision(prev)
+
+
+def digest(launches):
+    return hashlib.sha256(json.dumps(launches).encode()).hexdigest()
+
+
+def golden_document(cs):
+    names, rows = [], {}
+    for c in cs:
+        launches = record(c)
+        for n, *_ in launches:
+            if n not in names:
+                names.append(n)
+        rows[case_name(c)] = [[names.index(n) for n, *_ in launches], digest(launches)]
+    return dict(cases_sha256=cases_sha256(cs), names=names, cases=rows)
+
+
+# ----------------------------------------------------------------------------- tests
+def test_engine_launches_match_the_recorded_ones():
+    doc, cs = json.load(open(GOLDEN)), cases()
+    assert len(cs) == len(doc["cases"]) and cases_sha256(cs) == doc["cases_sha256"], "cases() no longer enumerates what the golden file was recorded for"
+    bad = []
+    for c in cs:
+        first, second = record(c), record(c)
+        assert json.dumps(first) == json.dumps(second), f"{case_name(c)}: two recordings of the same tree differ"
+        seq, sha = doc["cases"][case_name(c)]
+        got = [n for n, *_ in first]
+        want = [doc["names"][i] for i in seq]
+        if got != want:
+            k = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+            bad.append(f"{case_name(c)}: launch {k} is {got[k] if k < len(got) else 'missing'}, recorded {want[k] if k < len(want) else 'nothing'}")
+        elif digest(first) != sha:
+            bad.append(f"{case_name(c)}: same entry points, other arguments (compare --dump of the two trees)")
+    assert not bad, f"{len(bad)} of {len(cs)} cases differ:\n" + "\n".join(bad[:20])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["fp32x6", "bf16"])
+def test_stand_in_launches_what_the_gpu_run_launches(mode):
+    """The recorder's stand-in cannot drift from reality: a render forward + backward of 512 rays on the 32^3 synthetic scene, really launched,
+    and the same pass on the CPU stand-in with the row count the device found, give the same entry points with the same scalars."""
+    from contrastive_lift_amd import engine
+    from contrastive_lift_amd.synthetic import make_scene
+    n, grid = 512, 32
+    model, renderer, pool = make_scene(grid=grid, num_classes=CLASSES, max_instances=DIM_INST // 2, device="cuda", image=64, n_cams=1)
+    rays = pool[torch.randperm(pool.shape[0], generator=torch.Generator().manual_seed(3))[:n].to(pool.device)].contiguous()
+    jitter = torch.rand((n,), generator=torch.Generator().manual_seed(4)).to(pool.device)
+    prev = engine.set_mlp_precision(mode)
+    try:
+        with Recorder(launch=engine.call, pointers=False) as real:
+            ctx = run_pass(engine, model, renderer, "render_all", rays, jitter, False, None, CLASSES, DIM_INST)
+        torch.cuda.synchronize()
+        assert ctx.M > 0
+        cpu_model = field_on_cpu("xyz_sf", grid=grid)
+        with Recorder(active=ctx.M, pointers=False) as stand_in:
+            run_pass(engine, cpu_model, renderer_on_cpu("softmax", grid), "render_all", torch.zeros((n, 8)), torch.zeros((n,)), False, None, CLASSES, DIM_INST)
+    finally:
+        engine.set_mlp_precision(prev)
+    assert [l[0] for l in stand_in.launches] == [l[0] for l in real.launches]
+    assert stand_in.launches == real.launches
+
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["--dump"]:
+        os.makedirs(sys.argv[2], exist_ok=True)
+        for c in cases():
+            with open(os.path.join(sys.argv[2], case_name(c).replace("/", "__") + ".json"), "w") as f:
+                f.write("\n".join(json.dumps(l) for l in record(c)) + "\n")
+    elif sys.argv[1:2] == ["--golden"]:
+        with open(GOLDEN, "w") as f:
+            json.dump(golden_document(cases()), f, separators=(",", ":"))
+            f.write("\n")
+    else:
+        sys.exit("usage: test_engine_launches.py --dump DIR | --golden")
