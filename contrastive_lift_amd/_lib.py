@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIFT_LIB_PATH") or os.path.join(_HERE, "libclift.so")      # (the override: timing probes of variant builds, tools/jobs)
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
@@ -30,6 +30,15 @@ class March(C.Structure):
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("inv_ext2", C.c_float * 3), ("step_size", C.c_float),
                 ("n_samples", C.c_int), ("distance_scale", C.c_float), ("density_shift", C.c_float),
                 ("weight_thres", C.c_float)]
+
+
+class EditBoxRec(C.Structure):
+    _fields_ = [("axes", C.c_float * 9), ("centre", C.c_float * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+class EditRec(C.Structure):
+    _fields_ = [("mode", C.c_int), ("src", EditBoxRec), ("dst", EditBoxRec), ("map_m", C.c_float * 9), ("map_t", C.c_float * 3),
+                ("dir_inv", C.c_float * 9)]
 
 
 class TVSet(C.Structure):
@@ -65,6 +74,8 @@ _SIGNATURES = {
     "clift_last_error": ([], C.c_char_p),
     "clift_gen_rays": ([_I, _I, _P, _P, _F, _P, _P, _P], C.c_int),
     "clift_density_fwd": ([_P, _P, _P, _P, _I, _P, _P], C.c_int),
+    "clift_edit_density_fwd": ([_P, _P, _P, _P, _I, _P, _P], C.c_int),
+    "clift_edit_active": ([_P, _P, _P, _P, _I, _P, _P, _P], C.c_int),
     "clift_density_points": ([_P, _P, _I, _L, _F, _I, _P, _P], C.c_int),
     "clift_xyz_head_first2_fwd": ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P], C.c_int),
     "clift_xyz_head_first2_x6_fwd": ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P], C.c_int),

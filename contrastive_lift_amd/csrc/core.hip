@@ -22,7 +22,7 @@ int clift_check_launch(const char* what) {
     return 0;
 }
 
-extern "C" int clift_version(void) { return 22; }
+extern "C" int clift_version(void) { return 23; }
 
 // Kernel switches (clift.h, CLIFT_SWITCH_*): one word of host state, seeded from the environment on first use -- the library's only read of
 // the environment -- and changed at run time through clift_set_switches.  Kernel files read it through clift_switch_off (clift_dev.h).
@@ -73,6 +73,7 @@ void clift_bind_rows_limit_layer_bf16(const int* p);
 void clift_bind_rows_limit_layer_x6w(const int* p);
 void clift_bind_rows_limit_layer_nb16(const int* p);
 void clift_bind_rows_limit_layer_n6(const int* p);
+void clift_bind_rows_limit_edit(const int* p);
 
 extern "C" int clift_bind_rows_limit(const int* dev_limit) {
     clift_bind_rows_limit_march(dev_limit);
@@ -86,6 +87,7 @@ extern "C" int clift_bind_rows_limit(const int* dev_limit) {
     clift_bind_rows_limit_layer_x6w(dev_limit);
     clift_bind_rows_limit_layer_nb16(dev_limit);
     clift_bind_rows_limit_layer_n6(dev_limit);
+    clift_bind_rows_limit_edit(dev_limit);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { clift_set_error("clift_bind_rows_limit: %s", hipGetErrorString(e)); return 2; }
     return 0;
@@ -102,6 +104,7 @@ void clift_bind_grad_shards_layer_bf16(const void* p);
 void clift_bind_grad_shards_layer_x6w(const void* p);
 void clift_bind_grad_shards_layer_nb16(const void* p);
 void clift_bind_grad_shards_layer_n6(const void* p);
+void clift_bind_grad_shards_edit(const void* p);
 
 extern "C" int clift_bind_grad_shards(const void* dev_desc) {
     clift_bind_grad_shards_march(dev_desc);
@@ -115,6 +118,7 @@ extern "C" int clift_bind_grad_shards(const void* dev_desc) {
     clift_bind_grad_shards_layer_x6w(dev_desc);
     clift_bind_grad_shards_layer_nb16(dev_desc);
     clift_bind_grad_shards_layer_n6(dev_desc);
+    clift_bind_grad_shards_edit(dev_desc);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { clift_set_error("clift_bind_grad_shards: %s", hipGetErrorString(e)); return 2; }
     return 0;

@@ -1,0 +1,234 @@
+// edit.hip -- scene-editing renders: the sampling front end with one box edit in it (delete / extract / duplicate / manipulate an instance).
+// Reference: model/renderer/panopli_tensoRF_renderer.py:303-623 (forward_delete / _extract / _duplicate / _manipulate) on
+// split_points_minimal (:785-797).  The render kernels recompute a sample's position from (ray, jitter, k), so a per-sample mask or a
+// coordinate remap cannot be injected between them from outside: an edit render has these two kernels in their place and then runs on
+// the point-wise kernels (clift_vm_products_points, clift_app_encode_points), the MLP chains and the march / compaction / compositing
+// kernels unchanged.  Edits render without jitter (perturb = 0, is_train = False in the reference's four methods).
+#include "clift_dev.h"
+#include <math.h>
+#include <stddef.h>
+CLIFT_ROWS_LIMIT_BINDER(edit)
+
+struct BoxP {
+    float A[9], c[3], lo[3], hi[3];
+};
+struct EditP {
+    int mode;
+    BoxP src, dst;
+    float M[9], t[3], Dinv[9];
+};
+
+static inline BoxP to_dev(const clift_edit_box_t& b) {
+    BoxP p;
+    for (int i = 0; i < 9; ++i) p.A[i] = b.axes[i];
+    for (int i = 0; i < 3; ++i) { p.c[i] = b.centre[i]; p.lo[i] = b.lo[i]; p.hi[i] = b.hi[i]; }
+    return p;
+}
+static inline EditP to_dev(const clift_edit_t* e) {
+    EditP p;
+    p.mode = e->mode;
+    p.src = to_dev(e->src);
+    p.dst = to_dev(e->dst);
+    for (int i = 0; i < 9; ++i) { p.M[i] = e->map_m[i]; p.Dinv[i] = e->dir_inv[i]; }
+    for (int i = 0; i < 3; ++i) p.t[i] = e->map_t[i];
+    return p;
+}
+// edit_finite walks the record as one int followed by floats only: no padding, nothing but floats after the mode
+static_assert(sizeof(clift_edit_t) == sizeof(int) + 57 * sizeof(float) && offsetof(clift_edit_t, src) == sizeof(int), "clift_edit_t: int mode + 57 floats");
+static bool edit_finite(const clift_edit_t* e) {
+    const float* f = e->src.axes;                                       // the record is one int followed by floats only (clift.h)
+    const int n = (int)((sizeof(clift_edit_t) - sizeof(int)) / sizeof(float));
+    for (int i = 0; i < n; ++i)
+        if (!isfinite(f[i])) return false;
+    return true;
+}
+static int edit_check(const clift_edit_t* e, const char* who) {
+    CLIFT_REQUIRE(e != nullptr, "%s: no edit record", who);
+    CLIFT_REQUIRE(e->mode >= CLIFT_EDIT_DELETE && e->mode <= CLIFT_EDIT_MANIPULATE, "%s: unknown edit mode %d", who, e->mode);
+    CLIFT_REQUIRE(edit_finite(e), "%s: the edit record holds a value that is not finite", who);
+    return 0;
+}
+
+// row-vector product of a row-major 3x3 with v, every multiply / add rounded separately, left to right
+__device__ __forceinline__ float row3(const float* a, const float v[3]) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(a[0], v[0]), __fmul_rn(a[1], v[1])), __fmul_rn(a[2], v[2]));
+}
+// lo <= A (p - c) <= hi, faces inclusive (a NaN coordinate is outside)
+__device__ __forceinline__ bool in_box(const BoxP& b, const float p[3]) {
+    const float d[3] = {__fsub_rn(p[0], b.c[0]), __fsub_rn(p[1], b.c[1]), __fsub_rn(p[2], b.c[2])};
+    bool in = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float q = row3(b.A + 3 * i, d);
+        in = in && (b.lo[i] <= q) && (q <= b.hi[i]);
+    }
+    return in;
+}
+
+// One sample under the edit.  World point and in-aabb flag from the UNEDITED sample with sample_xn's separately rounded ops (the reference
+// takes mask_xyz before it remaps, :304,457,540), box classification in fp32, then the affine remap of a sample inside the destination
+// box; xn = normalised coordinates of the (remapped) point -- the very bits of sample_xn when the sample is not remapped.
+struct EditS {
+    bool in;      // inside the aabb (before the remap)
+    bool kill;    // sigma = 0 by the edit's kill rule
+    bool moved;   // inside the destination box: position remapped, view direction turned
+};
+__device__ __forceinline__ EditS edit_sample(const RayG& g, const MarchP& m, const EditP& e, float z, float xn[3]) {
+    EditS s;
+    float p[3];
+    s.in = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+        s.in = s.in && !(m.lo[i] > p[i]) && !(p[i] > m.hi[i]);
+    }
+    const bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
+    s.moved = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
+    s.kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !s.moved) : false;
+    if (s.moved) {
+        const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xn[i] = __fsub_rn(__fmul_rn(__fsub_rn(p[i], m.lo[i]), m.inv2[i]), 1.0f);
+    return s;
+}
+
+// ============================================================================ density forward under an edit
+// The wave-per-sweep form of k_density_fwd_ray (march.hip), restated here because the tap records are built from the EDITED position: lane =
+// sample sets the ray up once, classifies and remaps its sample and writes the tap records of the three planes to the wave's LDS slot; four
+// passes of 16 samples x 4 lanes then do the 18 table reads.  Same taps, same FMA order, same quad sum as clift_density_fwd, so a sample
+// the edit neither remaps nor kills gets the very bits of the unedited pass.  A remapped point may leave the aabb: make_tap clamps every
+// index and zeroes the weight of a tap outside the table (grid_sample's zero padding), as k_density_points relies on.  A killed sample
+// reads no table at all.  With a remap the samples that are looked up are no prefix of the ray any more: the only early exit left is a
+// sweep none of whose samples is looked up.
+struct alignas(16) EdRec {
+    int o[4];
+    float w[4];
+    int z[2];
+    float wz[2];
+};
+constexpr int EDR_WAVES = 4;
+
+__global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_density_fwd(MarchP m, EditP e, VmP t, const float* __restrict__ rays, int N,
+                                                                     float* __restrict__ sigma) {
+    __shared__ EdRec recs_all[EDR_WAVES][3][64];
+    __shared__ float sig_all[EDR_WAVES][64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nsw = (m.S + 63) / 64;                         // sweeps per ray
+    const long item = (long)blockIdx.x * EDR_WAVES + wave;
+    if (item >= (long)N * nsw) return;
+    const int r = (int)(item / nsw);
+    EdRec (*recs)[64] = recs_all[wave];
+    float* sig = sig_all[wave];
+    const RayG g = load_ray(rays, r, m);
+    const int C = t.comps;
+    float* out = sigma + (size_t)r * m.S;
+    const int k = (int)(item - (long)r * nsw) * 64 + lane;
+    float xn[3];
+    bool on = false;
+    if (k < m.S) {
+        const EditS s = edit_sample(g, m, e, sample_z(g, m, k, 0.f), xn);
+        on = s.in && !s.kill;
+    }
+    const unsigned long long onmask = __ballot(on);
+    if (onmask == 0) {                                       // wave-uniform
+        if (k < m.S) out[k] = 0.f;
+        return;
+    }
+    if (on) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const VmTaps tp = vm_taps(t, i, xn);
+            int a_, b_, v_;
+            vm_axes(i, a_, b_, v_);
+            const int W = t.res[a_];
+            int4* dst = reinterpret_cast<int4*>(&recs[i][lane]);
+            dst[0] = make_int4((tp.ty.i0 * W + tp.tx.i0) * C, (tp.ty.i0 * W + tp.tx.i1) * C, (tp.ty.i1 * W + tp.tx.i0) * C, (tp.ty.i1 * W + tp.tx.i1) * C);
+            dst[1] = make_int4(__float_as_int(tp.tx.w0 * tp.ty.w0), __float_as_int(tp.tx.w1 * tp.ty.w0), __float_as_int(tp.tx.w0 * tp.ty.w1),
+                               __float_as_int(tp.tx.w1 * tp.ty.w1));
+            dst[2] = make_int4(tp.tz.i0 * C, tp.tz.i1 * C, __float_as_int(tp.tz.w0), __float_as_int(tp.tz.w1));
+        }
+    }
+    sig[lane] = 0.f;
+    __builtin_amdgcn_wave_barrier();
+    const int q = lane & 3;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int sl = pass * 16 + (lane >> 2);
+        const bool mine = (onmask >> sl) & 1ull;
+        if ((onmask >> (pass * 16)) & 0xffffull) {           // wave-uniform: some sample of this pass is looked up
+            float acc = 0.f;
+            if (mine) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const int4* rp = reinterpret_cast<const int4*>(&recs[i][sl]);
+                    const int4 o = rp[0], wi = rp[1], zi = rp[2];
+                    for (int c4 = q * 4; c4 < C; c4 += 16) {
+                        const float* pp = t.plane[i] + c4;
+                        const float* lp = t.line[i] + c4;
+                        float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
+                        pa = f4_fma(__int_as_float(wi.x), ld4(pp + (unsigned)o.x), pa);
+                        pa = f4_fma(__int_as_float(wi.y), ld4(pp + (unsigned)o.y), pa);
+                        pa = f4_fma(__int_as_float(wi.z), ld4(pp + (unsigned)o.z), pa);
+                        pa = f4_fma(__int_as_float(wi.w), ld4(pp + (unsigned)o.w), pa);
+                        float4 la = make_float4(0.f, 0.f, 0.f, 0.f);
+                        la = f4_fma(__int_as_float(zi.z), ld4(lp + (unsigned)zi.x), la);
+                        la = f4_fma(__int_as_float(zi.w), ld4(lp + (unsigned)zi.y), la);
+                        acc += f4_hsum(f4_mul(pa, la));
+                    }
+                }
+            }
+            acc += __shfl_xor(acc, 1);
+            acc += __shfl_xor(acc, 2);
+            if (q == 0 && mine) {
+                const float x = acc + m.shift;
+                sig[sl] = (x > 20.f) ? x : log1pf(expf(x));
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (k < m.S) out[k] = sig[lane];
+}
+
+extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit, const clift_vm_t* h_dens, const float* rays, int N,
+                                      float* sigma, clift_stream_t s) {
+    if (edit_check(h_edit, "clift_edit_density_fwd")) return 1;
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
+    if (N <= 0) return 0;
+    k_edit_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), EDR_WAVES), 64 * EDR_WAVES, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_edit), to_dev(h_dens),
+                                                                                                                 rays, N, sigma);
+    return clift_check_launch("clift_edit_density_fwd");
+}
+
+// ============================================================================ positions and view directions of the active samples
+// The same classification, recomputed (not stored: (N, S) flags would cost more traffic than the few dozen ops).  xa feeds the xyz heads and
+// clift_vm_products_points, dirs feeds clift_app_encode_points.
+__global__ __launch_bounds__(256) void k_edit_active(MarchP m, EditP e, const float* __restrict__ rays, const int* __restrict__ act, int M,
+                                                      float* __restrict__ xa, float* __restrict__ dirs) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= limit_rows(M)) return;
+    const int sid = act[s];
+    const int r = sid / m.S, k = sid - r * m.S;
+    const RayG g = load_ray(rays, r, m);
+    float xn[3];
+    const EditS es = edit_sample(g, m, e, sample_z(g, m, k, 0.f), xn);
+    float d[3] = {g.d[0], g.d[1], g.d[2]};
+    if (es.moved) {
+        const float v[3] = {row3(e.Dinv, g.d), row3(e.Dinv + 3, g.d), row3(e.Dinv + 6, g.d)};
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2];
+    }
+    *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
+    *reinterpret_cast<float4*>(dirs + (size_t)s * 4) = make_float4(d[0], d[1], d[2], 0.f);
+}
+
+extern "C" int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h_edit, const float* rays, const int* act_idx, int M, float* xa,
+                                 float* dirs, clift_stream_t s) {
+    if (edit_check(h_edit, "clift_edit_active")) return 1;
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_active: n_samples must be positive (got %d)", h_m->n_samples);
+    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_active: xa and dirs are both written");
+    if (M <= 0) return 0;
+    k_edit_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_edit), rays, act_idx, M, xa, dirs);
+    return clift_check_launch("clift_edit_active");
+}

@@ -1,0 +1,201 @@
+"""Scene edits: oriented boxes and the host-side resolution of one edit to the plain record the edit kernels read (``clift_edit_t`` in
+include/clift.h; csrc/edit.hip; ``engine.edit_forward``).
+
+A box has axes ``A`` (3x3, ROWS are the axes), a centre ``c`` and bounds ``lo``, ``hi``: a world point p is inside iff
+``lo <= A (p - c) <= hi`` component-wise, faces inclusive.  That one form covers the boxes ``points3d.fit_instance_boxes`` writes
+(``EditBox.from_fitted``) and the reference's ``{"extent", "position", "orientation"}`` dictionaries (``EditBox.from_reference``).
+
+Two families of edits:
+
+* reference-faithful -- ``reference_delete`` / ``reference_extract`` / ``reference_duplicate`` / ``reference_manipulate`` restate the
+  arithmetic of the reference's ``forward_delete`` / ``forward_extract`` / ``forward_duplicate`` / ``forward_manipulate``
+  (model/renderer/panopli_tensoRF_renderer.py:303-623) exactly as it is written there, including its quirk: once the rotation is not the
+  identity its maps are no rigid motion (the content is turned one way and the box the other, and the translation is subtracted after the
+  rotation).  ``TensoRFRenderer.forward_*`` use these.
+* rigid -- ``copy`` / ``move``: the object undergoes x -> R (x - pos) + pos + t.  The command-line tool uses these.  For R = I, ``move``
+  resolves to the same record as ``reference_manipulate``.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+DELETE, EXTRACT, DUPLICATE, MANIPULATE = 0, 1, 2, 3          # CLIFT_EDIT_* of include/clift.h
+_MODE_NAMES = {DELETE: "delete", EXTRACT: "extract", DUPLICATE: "duplicate", MANIPULATE: "manipulate"}
+
+
+def _np(x, shape):
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"expected shape {shape}, got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError("edit: values must be finite")
+    return a
+
+
+def _f32(a):
+    """fp32 values of an fp64 array as a flat list (-0.0 stored as 0.0, so that equal edits pack to equal bytes)."""
+    return (np.asarray(a, dtype=np.float64).astype(np.float32).reshape(-1) + np.float32(0.0)).tolist()
+
+
+class EditBox:
+    """Oriented box: inside iff ``lo <= axes @ (p - centre) <= hi`` (rows of ``axes`` are the box axes; faces inclusive).  fp64 on the host."""
+
+    def __init__(self, axes, centre, lo, hi):
+        self.axes, self.centre, self.lo, self.hi = _np(axes, (3, 3)), _np(centre, (3,)), _np(lo, (3,)), _np(hi, (3,))
+
+    @classmethod
+    def from_fitted(cls, entry, pad=0.0):
+        """A ``bboxes.pkl`` entry of inference/fit_bboxes.py (``points3d.fit_instance_boxes``): axes = ``orientation`` (rows), centre =
+        ``position``, (lo, hi) = ``bbox``.  Fitted boxes hug the filtered points: ``pad`` grows them on every side."""
+        lo, hi = entry["bbox"]
+        return cls(entry["orientation"], entry["position"], lo, hi).padded(pad)
+
+    @classmethod
+    def from_reference(cls, d, pad=0.0):
+        """The reference's ``{"extent", "position", "orientation"}``: axes are the COLUMNS of ``orientation`` (split_points_minimal,
+        renderer.py:785-797), so A = orientation^T, lo = -extent / 2, hi = +extent / 2."""
+        ext = _np(d["extent"], (3,))
+        return cls(_np(d["orientation"], (3, 3)).T, d["position"], -ext / 2, ext / 2).padded(pad)
+
+    def padded(self, pad):
+        pad = float(pad)
+        return self if pad == 0.0 else EditBox(self.axes, self.centre, self.lo - pad, self.hi + pad)
+
+    def local(self, points):
+        """Box-frame coordinates A (p - c) of (n, 3) world points, fp64."""
+        return (np.asarray(points, dtype=np.float64) - self.centre) @ self.axes.T
+
+    def contains(self, points):
+        q = self.local(points)
+        return np.all((self.lo <= q) & (q <= self.hi), axis=-1)
+
+    def _fill(self, rec):
+        rec.axes[:] = _f32(self.axes)
+        rec.centre[:] = _f32(self.centre)
+        rec.lo[:] = _f32(self.lo)
+        rec.hi[:] = _f32(self.hi)
+
+
+class Edit:
+    """One resolved edit: kill rule (``mode``), source and destination box, the affine map p' = M p + t of samples inside the destination
+    box and the matrix ``dir_inv`` applied to their view directions.  ``record()`` packs it as ``clift_edit_t``."""
+
+    def __init__(self, mode, src, dst=None, M=None, t=None, dir_inv=None):
+        if mode not in _MODE_NAMES:
+            raise ValueError(f"unknown edit mode {mode!r}")
+        self.mode, self.src = mode, src
+        self.dst = dst if dst is not None else src
+        self.M = _np(M if M is not None else np.eye(3), (3, 3))
+        self.t = _np(t if t is not None else np.zeros(3), (3,))
+        self.dir_inv = _np(dir_inv if dir_inv is not None else np.eye(3), (3, 3))
+
+    @property
+    def name(self):
+        return _MODE_NAMES[self.mode]
+
+    def record(self):
+        rec = _lib.EditRec()
+        rec.mode = int(self.mode)
+        self.src._fill(rec.src)
+        self.dst._fill(rec.dst)
+        rec.map_m[:] = _f32(self.M)
+        rec.map_t[:] = _f32(self.t)
+        rec.dir_inv[:] = _f32(self.dir_inv)
+        return rec
+
+    def record_bytes(self):
+        return C.string_at(C.byref(self.record()), C.sizeof(_lib.EditRec))
+
+    def source_points(self, points):
+        """Where (n, 3) world points are looked up: M p + t inside the destination box of a remapping edit, p elsewhere (fp64)."""
+        p = np.asarray(points, dtype=np.float64)
+        if self.mode < DUPLICATE:
+            return p
+        return np.where(self.dst.contains(p)[:, None], p @ self.M.T + self.t, p)
+
+    def killed(self, points):
+        src = self.src.contains(points)
+        if self.mode == DELETE:
+            return src
+        if self.mode == EXTRACT:
+            return ~src
+        if self.mode == MANIPULATE:
+            return src & ~self.dst.contains(points)
+        return np.zeros(src.shape, dtype=bool)
+
+
+def _box(b, pad=0.0):
+    return b.padded(pad) if isinstance(b, EditBox) else EditBox.from_reference(b, pad)
+
+
+# ----------------------------------------------------------------------------- reference-faithful
+def reference_delete(bbox):
+    """forward_delete (renderer.py:303-376): kill the samples inside the box."""
+    return Edit(DELETE, _box(bbox))
+
+
+def reference_extract(bbox):
+    """forward_extract (renderer.py:379-453): kill the samples outside the box."""
+    return Edit(EXTRACT, _box(bbox))
+
+
+def reference_duplicate(bbox, translation, rotation):
+    """forward_duplicate (renderer.py:456-536), the reference's arithmetic as written (O = orientation, R = rotation, pos = position):
+    the destination box has centre R pos + t, axes = columns of R O and the same extent; samples inside it are looked up at p - t with the
+    view direction R^-1 d; nothing is killed.  For R != I this is no rigid copy (the content is not turned, the box is, and it is turned
+    about the origin): the quirk is reproduced on purpose."""
+    O, pos, ext = _np(bbox["orientation"], (3, 3)), _np(bbox["position"], (3,)), _np(bbox["extent"], (3,))
+    R, t = _np(rotation, (3, 3)), _np(translation, (3,))
+    dst = EditBox((R @ O).T, R @ pos + t, -ext / 2, ext / 2)
+    return Edit(DUPLICATE, _box(bbox), dst, np.eye(3), -t, np.linalg.inv(R))
+
+
+def reference_manipulate(bbox, translation, rotation):
+    """forward_manipulate (renderer.py:539-623), the reference's arithmetic as written: the destination box has centre pos + t and axes =
+    columns of R O; samples inside it are looked up at R (p - pos) + pos - t with the view direction R^-1 d; samples inside the source box
+    and outside the destination box are killed.  For R != I this is no rigid motion (a rigid one looks up R^-1 (p - pos - t) + pos): the
+    quirk is reproduced on purpose -- ``move`` is the rigid form."""
+    O, pos, ext = _np(bbox["orientation"], (3, 3)), _np(bbox["position"], (3,)), _np(bbox["extent"], (3,))
+    R, t = _np(rotation, (3, 3)), _np(translation, (3,))
+    dst = EditBox((R @ O).T, pos + t, -ext / 2, ext / 2)
+    return Edit(MANIPULATE, _box(bbox), dst, R, (pos - R @ pos) - t, np.linalg.inv(R))
+
+
+# ----------------------------------------------------------------------------- rigid
+def _rigid(mode, box, translation, rotation):
+    """The object undergoes x -> R (x - pos) + pos + t (pos = the box centre): the destination box has centre pos + t and axes A R^-1 (for
+    a reference box: the columns of R O), a destination sample p comes from R^-1 (p - pos - t) + pos, its view direction from R^-1 d."""
+    R = _np(rotation if rotation is not None else np.eye(3), (3, 3))
+    t = _np(translation if translation is not None else np.zeros(3), (3,))
+    Rinv = np.linalg.inv(R)
+    pos = box.centre
+    dst = EditBox(box.axes @ Rinv, pos + t, box.lo, box.hi)
+    return Edit(mode, box, dst, Rinv, (pos - Rinv @ pos) - Rinv @ t, Rinv)
+
+
+delete, extract = reference_delete, reference_extract          # (no motion in them: the rigid family shares the reference's forms)
+
+
+def copy(box, translation=None, rotation=None):
+    """A rigid copy of the box's content at x -> R (x - pos) + pos + t; the original stays (nothing is killed)."""
+    return _rigid(DUPLICATE, _box(box), translation, rotation)
+
+
+def move(box, translation=None, rotation=None):
+    """The box's content moved rigidly by x -> R (x - pos) + pos + t; what it leaves behind (in the source, not in the destination box) is
+    killed."""
+    return _rigid(MANIPULATE, _box(box), translation, rotation)
+
+
+def rotation_from_euler_deg(rx, ry, rz):
+    """R = Rz Ry Rx for rotations of rx, ry, rz degrees about the world x, y, z axes."""
+    ax, ay, az = np.deg2rad([rx, ry, rz])
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx

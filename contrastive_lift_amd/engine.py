@@ -1026,6 +1026,116 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
     return out, ctx
 
 
+# ----------------------------------------------------------------------------- scene-editing forward
+@torch.no_grad()
+def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
+    """The reference's edit renders (renderer.py:303-623: forward_delete / _extract / _duplicate / _manipulate) for one resolved edit
+    (``edit.Edit``): samples the kill rule names get sigma = 0, samples inside the destination box are looked up at the remapped position
+    with the turned view direction.  No jitter (the reference samples with perturb 0, is_train False), no activations kept, no backward, no
+    distortion-loss value.  Returns (dict of outputs, context) like ``render_forward``.
+
+      edit_density_fwd -> march_fwd -> scan / compact at ``weight_thres`` -> edit_active (xa, dirs) ->
+      vm_products_points -> basis GEMM -> app_encode_points -> appearance layers;  xyz heads on xa;  composite.
+
+    ``weight_thres`` defaults to 0, not to ``renderer.raymarch_weight_thres``: the reference's edit forwards evaluate every head at every
+    in-box sample instead of only where w > 1e-4, and a sample with w == 0 adds nothing to any sum, so "w > 0" reproduces them exactly.
+    Pass the renderer's threshold to trade that for fewer active samples."""
+    rays, _ = _check_rays(rays, None)
+    if model.semantic_plane is not None or model.instance_plane is not None:
+        raise NotImplementedError("edit_forward: a semantic / instance head on its own VM grid is not supported (xyz MLP heads only)")
+    views = model.named_views()
+    N, S, dev, st = rays.shape[0], int(renderer.n_samples), rays.device, stream()
+    global _limit_owner
+    lim_t = _rows_limit.get((dev.type, dev.index))
+    if lim_t is not None and _limit_owner is not None:      # (as in _density_march: a synchronising pass after a sync-free one)
+        lim_t[0:1].fill_(INT_MAX)
+        _limit_owner = None
+    rec = edit.record()
+    ms = march_struct(renderer, model)
+    ms.weight_thres = float(weight_thres)                   # clift_march_fwd counts, clift_compact_fill lists: the same threshold
+    ctx = RenderCtx()
+    ctx.ms, ctx.res, ctx.N, ctx.S, ctx.rays = ms, grid_res(views), N, S, rays
+    vd = vm_struct(views, "density", ctx.res)
+    ctx.sigma = torch.empty((N, S), dtype=torch.float32, device=dev)
+    ctx.alpha, ctx.T, ctx.w = torch.empty_like(ctx.sigma), torch.empty_like(ctx.sigma), torch.empty_like(ctx.sigma)
+    ctx.ray_out = torch.empty((N, 8), dtype=torch.float32, device=dev)
+    n_active = torch.empty((N,), dtype=torch.int32, device=dev)
+    ctx.ray_start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    call("clift_edit_density_fwd", C.byref(ms), C.byref(rec), C.byref(vd), ptr(rays), N, ptr(ctx.sigma), st)
+    call("clift_march_fwd", C.byref(ms), ptr(rays), None, N, ptr(ctx.sigma), ptr(ctx.alpha), ptr(ctx.T), ptr(ctx.w), ptr(ctx.ray_out), ptr(n_active), st)
+    call("clift_scan_counts", ptr(n_active), N, ptr(ctx.ray_start), st)
+    M = ctx.M = int(ctx.ray_start[N].item())
+    ctx.act_idx = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
+    call("clift_compact_fill", ptr(ctx.w), ptr(ctx.ray_start), N, S, float(weight_thres), ptr(ctx.act_idx), st)
+    Ccls = model.num_semantic_classes
+    D = model.dim_feature_instance if model.render_instance_mlp is not None else 0
+    ctx.softmax_mode = 1 if renderer.semantic_weight_mode == "softmax" else 0
+    ctx.white_bg, ctx.stop_grad = int(bool(white_bg)), int(bool(renderer.stop_semantic_grad))
+    ctx.C, ctx.D, ctx.want = Ccls, D, (True, True, D > 0)
+    if M > 0:
+        params = _head_params(views)
+        ctx.xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        dirs = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        call("clift_edit_active", C.byref(ms), C.byref(rec), ptr(rays), ptr(ctx.act_idx), M, ptr(ctx.xa), ptr(dirs), st)
+        va = vm_struct(views, "appearance", ctx.res)
+        nc = 3 * va.comps
+        F = torch.empty((M, nc), dtype=torch.float32, device=dev)
+        call("clift_vm_products_points", C.byref(va), ptr(ctx.xa), 4, M, ptr(F), st)
+
+        def app_chain(keep):
+            # the un-fused front end (the fused one recomputes positions from the rays), then render_forward's appearance layers with
+            # fp32-stored activations
+            with _app_precision():
+                Wb = views["appearance_basis_mat.weight"]
+                nf = Wb.shape[0]
+                (W1, b1), (W2, b2), (W3, b3) = params["app"]
+                ldx, ldf = _pitch(W1), (nf + 3) // 4 * 4
+                feat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
+                with exact_fp32():
+                    gemm(M, nf, nc, F, nc, Wb, _pitch(Wb), feat, ldf)
+                X = torch.empty((M, ldx), dtype=torch.float32, device=dev)
+                call("clift_app_encode_points", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(dirs), 4, M, ptr(X), ldx, stream())
+                H1 = torch.empty((M, W1.shape[0]), dtype=torch.float32, device=dev)
+                gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
+                rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
+                if MLP_PRECISION in (0, 2) and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128 and persistent_ok():
+                    if MLP_PRECISION == 2 and persistent_x6_ok():
+                        call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
+                             None, 128, ptr(rgb_s), 3, 1, stream())
+                    else:
+                        app_last2(M, H1, W2, b2, W3, b3, None, rgb_s)
+                else:
+                    H2 = torch.empty((M, W2.shape[0]), dtype=torch.float32, device=dev)
+                    gemm(M, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
+                    pre = torch.empty((M, 3), dtype=torch.float32, device=dev)
+                    gemm(M, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
+                    call("clift_rows_act_fwd", ptr(pre), 3, M, 3, 1, ptr(rgb_s), 3, stream())
+                    keep.extend([H2, pre])
+                keep.extend([feat, X, H1, F, dirs])
+                ctx.rgb_s = rgb_s
+
+        br = Branches(model=model)
+        br.run(0, app_chain)
+        for slot, chain in _head_chains(model, views, ctx, params, (), True):
+            br.run(slot, chain)
+        br.join()
+    fresh = torch.empty if M > 0 else torch.zeros
+    rgb_raw = fresh((N, 3), dtype=torch.float32, device=dev)
+    rgb_map = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    sem_raw = fresh((N, Ccls), dtype=torch.float32, device=dev)
+    sem_map = torch.empty((N, Ccls), dtype=torch.float32, device=dev)
+    inst_map = fresh((N, D), dtype=torch.float32, device=dev) if D > 0 else None
+    out = (rgb_raw, rgb_map, sem_raw, sem_map, inst_map)
+    if M > 0 and renderer.semantic_weight_mode == "argmax":         # exactly as render_forward: one-hot of each ray's heaviest sample
+        ctx.w_feat = torch.zeros_like(ctx.w).scatter_(1, ctx.w.argmax(dim=1, keepdim=True), 1.0)
+        _composite_fwd(ctx, ctx.w, out, feats=False)
+        _composite_fwd(ctx, ctx.w_feat, out, colour=False)
+    else:
+        _composite_fwd(ctx, ctx.w if M > 0 else None, out)
+    ctx.rgb_raw, ctx.sem_raw = rgb_raw, sem_raw
+    return dict(rgb=rgb_map, semantics=sem_map, instances=inst_map, depth=ctx.ray_out[:, 1], opacity=ctx.ray_out[:, 0]), ctx
+
+
 # ----------------------------------------------------------------------------- backward
 def _composite_bwd(ctx, w, grads, rows, colour=True, feats=True, wgrad=True):
     """One clift_composite_bwd launch over the weight array ``w``: per-sample gradients w.r.t. the heads' ACTIVATED outputs into

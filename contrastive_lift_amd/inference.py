@@ -22,6 +22,22 @@ def render_rays(model, renderer, rays, chunk, white_bg=False):
     return tuple(torch.cat(x, 0) for x in outs)
 
 
+@torch.no_grad()
+def render_rays_edit(model, renderer, rays, chunk, white_bg=False, edit=None, weight_thres=0.0):
+    """``render_rays`` under one scene edit (``edit.Edit``; engine.edit_forward): the same chunking and the same outputs.  With ``edit``
+    and ``weight_thres`` bound (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``, which then cuts an edited
+    frame into row-tiles over the ranks like a plain one."""
+    if edit is None:
+        raise ValueError("render_rays_edit: an edit is required")
+    outs = [[], [], [], []]
+    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
+    for i in range(0, rays.shape[0], chunk):
+        o, ctx = engine.edit_forward(model, renderer, rays[i:i + chunk], edit, bool(white_bg), weight_thres=weight_thres)
+        outs[0].append(o["rgb"]); outs[1].append(o["semantics"]); outs[2].append(o["instances"]); outs[3].append(o["depth"].clone())
+        del ctx
+    return tuple(torch.cat(x, 0) for x in outs)
+
+
 def tile_bounds(n, world):
     """Contiguous row-tile boundaries of n rays over `world` ranks (sizes differ by at most one)."""
     return [(n * r) // world for r in range(world + 1)]

@@ -8,7 +8,7 @@ backward kernels; the trainer (trainer.py) bypasses autograd and drives engine.p
 import torch
 from torch import nn
 
-from . import engine
+from . import edit, engine
 
 
 class _RenderFn(torch.autograd.Function):
@@ -173,6 +173,34 @@ class TensoRFRenderer(nn.Module):
         names = [s.name for s in tensorf.arena.slots]
         params = [tensorf.get_parameter(n) for n in names]
         return _FeatureFn.apply(tensorf, self, rays, jitter, "semantic", names, *params)
+
+    # ------------------------------------------------------------------ scene edits (renderer.py:303-623)
+    def _forward_edit(self, tensorf, rays, white_bg, resolved):
+        out, _ = engine.edit_forward(tensorf, self, rays, resolved, white_bg)
+        inst = out["instances"]
+        if inst is None:
+            inst = torch.zeros((rays.shape[0], 0), dtype=torch.float32, device=rays.device)
+        return out["rgb"], out["semantics"], inst, out["depth"]
+
+    def forward_delete(self, tensorf, rays, white_bg, bbox_deletion):
+        """renderer.py:303-376: the scene without what is inside ``bbox_deletion`` ({"extent", "position", "orientation"}, axes = columns
+        of orientation).  Returns (rgb_map, semantic_map, instance_map, depth_map); no gradient."""
+        return self._forward_edit(tensorf, rays, white_bg, edit.reference_delete(bbox_deletion))
+
+    def forward_extract(self, tensorf, rays, white_bg, bbox_extraction):
+        """renderer.py:379-453: only what is inside ``bbox_extraction``."""
+        return self._forward_edit(tensorf, rays, white_bg, edit.reference_extract(bbox_extraction))
+
+    def forward_duplicate(self, tensorf, rays, white_bg, bbox_instance, translation, rotation):
+        """renderer.py:456-536, the reference's arithmetic as it is written: samples inside the box with centre R pos + t and axes R O are
+        looked up at p - t with the view direction R^-1 d.  For ``rotation`` != I that is no rigid copy (``edit.copy`` is one)."""
+        return self._forward_edit(tensorf, rays, white_bg, edit.reference_duplicate(bbox_instance, translation, rotation))
+
+    def forward_manipulate(self, tensorf, rays, white_bg, bbox_instance, translation, rotation):
+        """renderer.py:539-623, the reference's arithmetic as it is written: samples inside the box with centre pos + t and axes R O are
+        looked up at R (p - pos) + pos - t with the view direction R^-1 d; source-box samples outside that box are removed.  For
+        ``rotation`` != I that is no rigid motion -- the content turns one way and the box the other (``edit.move`` is the rigid form)."""
+        return self._forward_edit(tensorf, rays, white_bg, edit.reference_manipulate(bbox_instance, translation, rotation))
 
     # ------------------------------------------------------------------ alpha-mask shrink (renderer.py:669-754)
     @torch.no_grad()

@@ -115,6 +115,45 @@ int clift_vm_products_points(const clift_vm_t* h_vm, const float* xn, int ldx, l
 int clift_app_encode_points(const float* feat, int ldf, int nf, int pe_feat, int pe_view, const float* dirs, int ldd,
                             long n, float* X, int ldx, clift_stream_t s);
 
+/* ---- scene-editing renders (ABI 23): renderer.py:303-623 (forward_delete / forward_extract / forward_duplicate / forward_manipulate) on
+ * split_points_minimal (:785-797).  One edit, resolved on the host to a plain record (contrastive_lift_amd/edit.py).
+ * A box: world point p is inside iff lo <= axes (p - centre) <= hi component-wise, faces inclusive; axes is row-major and its ROWS are
+ * the box axes.  Samples inside the destination box are looked up at p' = map_m p + map_t (row-major 3x3, then the offset) and their view
+ * direction becomes dir_inv d; samples the kill rule names get sigma = 0 after the density lookup (:346,423,594).  Classification uses
+ * the UNEDITED sample position in fp32, every multiply / add rounded separately.  All values of the record must be finite; the fields a
+ * mode does not use (dst, map_*, dir_inv for delete / extract; src for duplicate) are ignored but still checked. */
+enum {
+    CLIFT_EDIT_DELETE = 0,      /* kill samples in src */
+    CLIFT_EDIT_EXTRACT = 1,     /* kill samples not in src */
+    CLIFT_EDIT_DUPLICATE = 2,   /* kill nothing; remap samples in dst */
+    CLIFT_EDIT_MANIPULATE = 3   /* kill samples in src and not in dst; remap samples in dst */
+};
+typedef struct {
+    float axes[9];
+    float centre[3];
+    float lo[3];
+    float hi[3];
+} clift_edit_box_t;
+typedef struct {
+    int mode; /* CLIFT_EDIT_* */
+    clift_edit_box_t src;
+    clift_edit_box_t dst;
+    float map_m[9];
+    float map_t[3];
+    float dir_inv[9];
+} clift_edit_t;
+/* The edit form of clift_density_fwd, without jitter (edits render with perturb = 0, is_train = False): sigma (N, S), 0 outside the box
+ * (the in-box test is taken BEFORE the remap, as the reference's mask_xyz is) and where the sample is killed; a remapped point that
+ * leaves the box reads zero padding, like clift_density_points.  A sample that is neither remapped nor killed gets the bits of
+ * clift_density_fwd. */
+int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit, const clift_vm_t* h_dens, const float* rays, int N,
+                           float* sigma, clift_stream_t s);
+/* For the compacted samples of such a pass: xa (M, 4) = the remapped normalised position [xn.x, xn.y, xn.z, 0] (input of the xyz heads and
+ * of clift_vm_products_points with ldx = 4) and dirs (M, 4) = the ray direction, times dir_inv where the sample is in dst (input of
+ * clift_app_encode_points with ldd = 4). */
+int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h_edit, const float* rays, const int* act_idx, int M, float* xa,
+                      float* dirs, clift_stream_t s);
+
 /* ---- a7-a8: renderer.py:83-84,100-103,137,173-174,626-631 + eff_distloss (renderer.py:101).
  * Per sample alpha, T (transmittance before the sample), w = alpha*T, all (N, S).
  * ray_out (N, 8) = [opacity, depth, bg, w_total, wm_total, dist_loss, t_min, 0]; n_active (N) = #(w > thres). */

@@ -82,13 +82,9 @@ def glasbey(n):
     return c
 
 
-def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
-                              cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
-                              meanshift="sklearn", save_pointcloud=False):
-    out = output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise)
-    out.mkdir(exist_ok=True, parents=True)
-    # launched under torch.distributed.run: one process per GPU, every frame rendered as row-tiles (one per rank) and
-    # assembled with one all-gather (inference.render_rays_sharded); clustering and file output happen on rank 0
+def distributed_device(device):
+    """Launched under torch.distributed.run: one process per GPU, every frame rendered as row-tiles (one per rank) and assembled with one
+    all-gather (inference.render_rays_sharded); clustering and file output happen on rank 0.  Returns (this rank's device, rank)."""
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -96,23 +92,38 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
         torch.cuda.set_device(local)
         device = f"cuda:{local}"
         dist.init_process_group(os.environ.get("CLIFT_DIST_BACKEND", "nccl"))
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    device = torch.device(device)
+    return torch.device(device), (dist.get_rank() if dist.is_initialized() else 0)
+
+
+def load_for_inference(config, device):
+    """The test scene, the field and the renderer of a checkpoint, the step ratio halved (RP:104)."""
     scene = get_scene(config, "test", device)
-    H, W = scene.image_dim
     model, renderer, _ = build_from_checkpoint(config, scene, device)
-    renderer.update_step_ratio(renderer.step_ratio * 0.5)                                    # RP:104
+    renderer.update_step_ratio(renderer.step_ratio * 0.5)
+    return scene, model, renderer
+
+
+def scene_frames(scene, trajectory_name, test_only):
+    """(name, rays, intrinsics) per frame -- RP:67-72: the test split, or the predefined trajectory trajectories/<trajectory_name>.pkl
+    (frames named by index, all with the intrinsics of frame 0)."""
+    if test_only:
+        return ((scene.all_frame_names[i], scene.rays_for(i), scene.intrinsics[i]) for i in scene.val_indices)
+    return ((n, r, scene.intrinsics[0]) for n, r in scene.trajectory_set(trajectory_name))
+
+
+def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
+                              cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
+                              meanshift="sklearn", save_pointcloud=False):
+    out = output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise)
+    out.mkdir(exist_ok=True, parents=True)
+    device, rank = distributed_device(device)
+    scene, model, renderer = load_for_inference(config, device)
+    H, W = scene.image_dim
     fg = scene.segmentation_data.fg_classes
     rgbs, sems, depths, inst_feats, thing_feats, slow_feats, points = [], [], [], [], [], [], []
-    # RP:67-72: the test split, or the predefined trajectory trajectories/<trajectory_name>.pkl (frames named by index, all
-    # with the intrinsics of frame 0)
-    if test_only:
-        frames = ((scene.all_frame_names[i], scene.rays_for(i), scene.intrinsics[i]) for i in scene.val_indices)
-    else:
-        frames = ((n, r, scene.intrinsics[0]) for n, r in scene.trajectory_set(trajectory_name))
     names = []
     with torch.no_grad():
-        for name, rays, K_frame in frames:
+        for name, rays, K_frame in scene_frames(scene, trajectory_name, test_only):
             names.append(name)
             p_rgb, p_sem, p_inst, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg)
             depths.append(inf.distance_to_depth(K_frame, p_dist.view(H, W)))
