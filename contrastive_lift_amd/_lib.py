@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIFT_LIB_PATH") or os.path.join(_HERE, "libclift.so")      # (the override: timing probes of variant builds, tools/jobs)
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
@@ -76,6 +76,8 @@ _SIGNATURES = {
     "clift_density_fwd": ([_P, _P, _P, _P, _I, _P, _P], C.c_int),
     "clift_edit_density_fwd": ([_P, _P, _P, _P, _I, _P, _P], C.c_int),
     "clift_edit_active": ([_P, _P, _P, _P, _I, _P, _P, _P], C.c_int),
+    "clift_edit_list_density_fwd": ([_P, _P, _I, _P, _P, _I, _P, _P], C.c_int),
+    "clift_edit_list_active": ([_P, _P, _I, _P, _P, _I, _P, _P, _P], C.c_int),
     "clift_density_points": ([_P, _P, _I, _L, _F, _I, _P, _P], C.c_int),
     "clift_xyz_head_first2_fwd": ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P], C.c_int),
     "clift_xyz_head_first2_x6_fwd": ([_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P], C.c_int),

@@ -4,6 +4,9 @@
 // coordinate remap cannot be injected between them from outside: an edit render has these two kernels in their place and then runs on
 // the point-wise kernels (clift_vm_products_points, clift_app_encode_points), the MLP chains and the march / compaction / compositing
 // kernels unchanged.  Edits render without jitter (perturb = 0, is_train = False in the reference's four methods).
+// An edit PROGRAM (clift_edit_list_*) is an ordered list e_1 .. e_n of up to CLIFT_EDIT_MAX such edits in one render: scene_i is e_i applied
+// to scene_{i-1}, and a sample is evaluated in scene_n by walking the list backwards (edit_walk).  The program is a by-value kernel
+// argument: the records are the same for every lane, the trip count is wave-uniform and the records arrive through scalar loads.
 #include "clift_dev.h"
 #include <math.h>
 #include <stddef.h>
@@ -46,6 +49,22 @@ static int edit_check(const clift_edit_t* e, const char* who) {
     CLIFT_REQUIRE(e != nullptr, "%s: no edit record", who);
     CLIFT_REQUIRE(e->mode >= CLIFT_EDIT_DELETE && e->mode <= CLIFT_EDIT_MANIPULATE, "%s: unknown edit mode %d", who, e->mode);
     CLIFT_REQUIRE(edit_finite(e), "%s: the edit record holds a value that is not finite", who);
+    return 0;
+}
+struct EditL {
+    int n;
+    EditP e[CLIFT_EDIT_MAX];
+};
+static_assert(sizeof(EditL) + sizeof(MarchP) + sizeof(VmP) + 64 < 4096, "the edit program travels as one kernel argument");
+static int edit_list_check(const clift_edit_t* e, int n, const char* who, EditL* out) {
+    CLIFT_REQUIRE(n >= 1 && n <= CLIFT_EDIT_MAX, "%s: a program holds 1 to %d edits (got n_edits = %d)", who, CLIFT_EDIT_MAX, n);
+    CLIFT_REQUIRE(e != nullptr, "%s: no edit records", who);
+    for (int i = 0; i < n; ++i) {
+        CLIFT_REQUIRE(e[i].mode >= CLIFT_EDIT_DELETE && e[i].mode <= CLIFT_EDIT_MANIPULATE, "%s: edit %d: unknown edit mode %d", who, i, e[i].mode);
+        CLIFT_REQUIRE(edit_finite(e + i), "%s: edit %d: the edit record holds a value that is not finite", who, i);
+    }
+    out->n = n;
+    for (int i = 0; i < CLIFT_EDIT_MAX; ++i) out->e[i] = to_dev(e + (i < n ? i : 0));      // (the slots past n are never read)
     return 0;
 }
 
@@ -94,6 +113,43 @@ __device__ __forceinline__ EditS edit_sample(const RayG& g, const MarchP& m, con
     return s;
 }
 
+// One sample under an edit program, walked BACKWARDS from e_n to e_1: every box test and every remap on the CURRENT point with the ops of
+// edit_sample; a killed sample stops (sigma = 0, nothing is looked up); a sample inside edit i's destination box continues at M_i p + t_i with
+// the view direction Dinv_i d.  The in-aabb flag is taken once, from the unedited point.  For n = 1 this is edit_sample, op for op; a sample
+// no edit remaps keeps the bits of sample_xn.  L lives in the kernel-argument segment and i is wave-uniform: scalar loads, no scratch copy.
+struct EditW {
+    bool in;      // inside the aabb (before any remap)
+    bool kill;    // sigma = 0: some edit's kill rule named the sample
+};
+__device__ __forceinline__ EditW edit_walk(const RayG& g, const MarchP& m, const EditL& L, float z, float xn[3], float d[3]) {
+    EditW s;
+    float p[3];
+    s.in = true;
+    s.kill = false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+        s.in = s.in && !(m.lo[i] > p[i]) && !(p[i] > m.hi[i]);
+        d[i] = g.d[i];
+    }
+    for (int i = L.n - 1; i >= 0; --i) {
+        const EditP& e = L.e[i];
+        const bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
+        const bool mov = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
+        const bool kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !mov) : false;
+        if (!s.kill && mov) {                               // (a killed sample has stopped: later tests see its last point, and change nothing)
+            const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
+            const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { p[j] = q[j]; d[j] = v[j]; }
+        }
+        s.kill = s.kill || kill;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xn[i] = __fsub_rn(__fmul_rn(__fsub_rn(p[i], m.lo[i]), m.inv2[i]), 1.0f);
+    return s;
+}
+
 // ============================================================================ density forward under an edit
 // The wave-per-sweep form of k_density_fwd_ray (march.hip), restated here because the tap records are built from the EDITED position: lane =
 // sample sets the ray up once, classifies and remaps its sample and writes the tap records of the three planes to the wave's LDS slot; four
@@ -110,8 +166,21 @@ struct alignas(16) EdRec {
 };
 constexpr int EDR_WAVES = 4;
 
-__global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_density_fwd(MarchP m, EditP e, VmP t, const float* __restrict__ rays, int N,
-                                                                     float* __restrict__ sigma) {
+// is the sample looked up (inside the aabb, not killed), and at which normalised position: under one edit, under a program
+__device__ __forceinline__ bool edit_looked_up(const RayG& g, const MarchP& m, const EditP& e, float z, float xn[3]) {
+    const EditS s = edit_sample(g, m, e, z, xn);
+    return s.in && !s.kill;
+}
+__device__ __forceinline__ bool edit_looked_up(const RayG& g, const MarchP& m, const EditL& L, float z, float xn[3]) {
+    float d[3];
+    const EditW s = edit_walk(g, m, L, z, xn, d);
+    return s.in && !s.kill;
+}
+
+// E = EditP (one edit) or EditL (a program): the two kernels differ in edit_looked_up alone
+template <class E>
+__device__ __forceinline__ void edit_density_fwd(const MarchP& m, const E& e, const VmP& t, const float* __restrict__ rays, int N,
+                                                 float* __restrict__ sigma) {
     __shared__ EdRec recs_all[EDR_WAVES][3][64];
     __shared__ float sig_all[EDR_WAVES][64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -126,11 +195,7 @@ __global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_density_fwd(MarchP m, E
     float* out = sigma + (size_t)r * m.S;
     const int k = (int)(item - (long)r * nsw) * 64 + lane;
     float xn[3];
-    bool on = false;
-    if (k < m.S) {
-        const EditS s = edit_sample(g, m, e, sample_z(g, m, k, 0.f), xn);
-        on = s.in && !s.kill;
-    }
+    const bool on = k < m.S && edit_looked_up(g, m, e, sample_z(g, m, k, 0.f), xn);
     const unsigned long long onmask = __ballot(on);
     if (onmask == 0) {                                       // wave-uniform
         if (k < m.S) out[k] = 0.f;
@@ -191,6 +256,15 @@ __global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_density_fwd(MarchP m, E
     if (k < m.S) out[k] = sig[lane];
 }
 
+__global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_density_fwd(MarchP m, EditP e, VmP t, const float* __restrict__ rays, int N,
+                                                                     float* __restrict__ sigma) {
+    edit_density_fwd(m, e, t, rays, N, sigma);
+}
+__global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_list_density_fwd(MarchP m, EditL L, VmP t, const float* __restrict__ rays, int N,
+                                                                          float* __restrict__ sigma) {
+    edit_density_fwd(m, L, t, rays, N, sigma);
+}
+
 extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit, const clift_vm_t* h_dens, const float* rays, int N,
                                       float* sigma, clift_stream_t s) {
     if (edit_check(h_edit, "clift_edit_density_fwd")) return 1;
@@ -200,6 +274,18 @@ extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit
     k_edit_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), EDR_WAVES), 64 * EDR_WAVES, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_edit), to_dev(h_dens),
                                                                                                                  rays, N, sigma);
     return clift_check_launch("clift_edit_density_fwd");
+}
+
+extern "C" int clift_edit_list_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens,
+                                           const float* rays, int N, float* sigma, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_density_fwd", &L)) return 1;
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_list_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
+    if (N <= 0) return 0;
+    k_edit_list_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), EDR_WAVES), 64 * EDR_WAVES, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens), rays,
+                                                                                                                      N, sigma);
+    return clift_check_launch("clift_edit_list_density_fwd");
 }
 
 // ============================================================================ positions and view directions of the active samples
@@ -231,4 +317,29 @@ extern "C" int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h
     if (M <= 0) return 0;
     k_edit_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_edit), rays, act_idx, M, xa, dirs);
     return clift_check_launch("clift_edit_active");
+}
+
+// k_edit_active under an edit program: the walk recomputed, the view direction turned by every edit that remapped the sample
+__global__ __launch_bounds__(256) void k_edit_list_active(MarchP m, EditL L, const float* __restrict__ rays, const int* __restrict__ act, int M,
+                                                           float* __restrict__ xa, float* __restrict__ dirs) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= limit_rows(M)) return;
+    const int sid = act[s];
+    const int r = sid / m.S, k = sid - r * m.S;
+    const RayG g = load_ray(rays, r, m);
+    float xn[3], d[3];
+    edit_walk(g, m, L, sample_z(g, m, k, 0.f), xn, d);
+    *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
+    *reinterpret_cast<float4*>(dirs + (size_t)s * 4) = make_float4(d[0], d[1], d[2], 0.f);
+}
+
+extern "C" int clift_edit_list_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
+                                      float* xa, float* dirs, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_active", &L)) return 1;
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_active: n_samples must be positive (got %d)", h_m->n_samples);
+    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_list_active: xa and dirs are both written");
+    if (M <= 0) return 0;
+    k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
+    return clift_check_launch("clift_edit_list_active");
 }

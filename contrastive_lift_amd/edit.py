@@ -14,6 +14,8 @@ Two families of edits:
   rotation).  ``TensoRFRenderer.forward_*`` use these.
 * rigid -- ``copy`` / ``move``: the object undergoes x -> R (x - pos) + pos + t.  The command-line tool uses these.  For R = I, ``move``
   resolves to the same record as ``reference_manipulate``.
+
+``EditProgram`` is an ordered list of up to ``MAX_EDITS`` such edits applied in one render (``clift_edit_list_*``).
 """
 import ctypes as C
 
@@ -23,6 +25,7 @@ from . import _lib
 
 DELETE, EXTRACT, DUPLICATE, MANIPULATE = 0, 1, 2, 3          # CLIFT_EDIT_* of include/clift.h
 _MODE_NAMES = {DELETE: "delete", EXTRACT: "extract", DUPLICATE: "duplicate", MANIPULATE: "manipulate"}
+MAX_EDITS = 8                                                # CLIFT_EDIT_MAX: edits in one program (EditProgram)
 
 
 def _np(x, shape):
@@ -126,6 +129,67 @@ class Edit:
         if self.mode == MANIPULATE:
             return src & ~self.dst.contains(points)
         return np.zeros(src.shape, dtype=bool)
+
+
+class EditProgram:
+    """An ordered list e_1 ... e_n of resolved edits (1 <= n <= ``MAX_EDITS``) for one render: scene_i is e_i applied to scene_{i-1}, scene_0
+    the trained field.  A point of scene_n is evaluated by walking the list BACKWARDS: edit i tests the current point against its boxes; a
+    point its kill rule names is empty (the walk stops); a point inside its destination box continues at M_i p + t_i with the view direction
+    Dinv_i d; what is left after e_1 is looked up in the field.  A program of one edit is that edit."""
+
+    def __init__(self, edits):
+        edits = tuple(edits)
+        if not 1 <= len(edits) <= MAX_EDITS:
+            raise ValueError(f"an edit program holds 1 to {MAX_EDITS} edits (MAX_EDITS), got {len(edits)}")
+        for e in edits:
+            if not isinstance(e, Edit):
+                raise TypeError(f"an edit program holds edit.Edit objects, got {type(e).__name__}")
+        self.edits = edits
+
+    def __len__(self):
+        return len(self.edits)
+
+    def __iter__(self):
+        return iter(self.edits)
+
+    def __getitem__(self, i):
+        return self.edits[i]
+
+    def records(self):
+        """Contiguous ctypes array of the n ``clift_edit_t`` records, in program order (the ``edits`` argument of the list entry points)."""
+        return (_lib.EditRec * len(self.edits))(*(e.record() for e in self.edits))
+
+    def record_bytes(self):
+        return b"".join(e.record_bytes() for e in self.edits)
+
+    def _walk(self, points, dirs):
+        p = np.array(points, dtype=np.float64)
+        d = None if dirs is None else np.array(dirs, dtype=np.float64)
+        dead = np.zeros(p.shape[0], dtype=bool)
+        for e in reversed(self.edits):
+            dead |= e.killed(p)                           # (a killed point is not walked further: its p stays where the walk stopped)
+            if e.mode >= DUPLICATE:
+                mov = ~dead & e.dst.contains(p)
+                p[mov] = p[mov] @ e.M.T + e.t
+                if d is not None:
+                    d[mov] = d[mov] @ e.dir_inv.T
+        return p, d, dead
+
+    def source_points(self, points, dirs=None):
+        """Where (n, 3) fp64 world points are finally looked up -- and, with ``dirs``, (points, view directions).  Rows of killed points
+        (``killed``) hold the position at which the walk stopped."""
+        p, d, _ = self._walk(points, dirs)
+        return p if dirs is None else (p, d)
+
+    def killed(self, points):
+        return self._walk(points, None)[2]
+
+
+def as_program(x):
+    """An ``EditProgram`` from an ``Edit``, an ``EditProgram`` or a sequence of ``Edit``."""
+    if isinstance(x, EditProgram):
+        return x
+    return EditProgram([x] if isinstance(x, Edit) else x)
 
 
 def _box(b, pad=0.0):

@@ -18,6 +18,7 @@ import os
 import torch
 
 from . import _lib
+from . import edit as _edit
 from ._lib import Gemm, March, VM, VMGrad, call, ptr, stream
 
 
@@ -1031,7 +1032,9 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
 def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     """The reference's edit renders (renderer.py:303-623: forward_delete / _extract / _duplicate / _manipulate) for one resolved edit
     (``edit.Edit``): samples the kill rule names get sigma = 0, samples inside the destination box are looked up at the remapped position
-    with the turned view direction.  No jitter (the reference samples with perturb 0, is_train False), no activations kept, no backward, no
+    with the turned view direction.  ``edit`` may also be an ``edit.EditProgram`` (or a sequence of ``Edit``): its edits are applied in
+    order in this one render -- every sample walks the list backwards (``EditProgram``) in ``clift_edit_list_density_fwd`` /
+    ``clift_edit_list_active``, which take the place of the two single-edit launches; a single ``Edit`` keeps those.  No jitter (the reference samples with perturb 0, is_train False), no activations kept, no backward, no
     distortion-loss value.  Returns (dict of outputs, context) like ``render_forward``.
 
       edit_density_fwd -> march_fwd -> scan / compact at ``weight_thres`` -> edit_active (xa, dirs) ->
@@ -1050,7 +1053,13 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     if lim_t is not None and _limit_owner is not None:      # (as in _density_march: a synchronising pass after a sync-free one)
         lim_t[0:1].fill_(INT_MAX)
         _limit_owner = None
-    rec = edit.record()
+    if isinstance(edit, _edit.Edit):
+        rec = edit.record()
+        edit_kernel, edit_args = "clift_edit_%s", (C.byref(rec),)
+    else:
+        prog = _edit.as_program(edit)
+        rec = prog.records()
+        edit_kernel, edit_args = "clift_edit_list_%s", (rec, len(prog))
     ms = march_struct(renderer, model)
     ms.weight_thres = float(weight_thres)                   # clift_march_fwd counts, clift_compact_fill lists: the same threshold
     ctx = RenderCtx()
@@ -1061,7 +1070,7 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     ctx.ray_out = torch.empty((N, 8), dtype=torch.float32, device=dev)
     n_active = torch.empty((N,), dtype=torch.int32, device=dev)
     ctx.ray_start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
-    call("clift_edit_density_fwd", C.byref(ms), C.byref(rec), C.byref(vd), ptr(rays), N, ptr(ctx.sigma), st)
+    call(edit_kernel % "density_fwd", C.byref(ms), *edit_args, C.byref(vd), ptr(rays), N, ptr(ctx.sigma), st)
     call("clift_march_fwd", C.byref(ms), ptr(rays), None, N, ptr(ctx.sigma), ptr(ctx.alpha), ptr(ctx.T), ptr(ctx.w), ptr(ctx.ray_out), ptr(n_active), st)
     call("clift_scan_counts", ptr(n_active), N, ptr(ctx.ray_start), st)
     M = ctx.M = int(ctx.ray_start[N].item())
@@ -1076,7 +1085,7 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
         params = _head_params(views)
         ctx.xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
         dirs = torch.empty((M, 4), dtype=torch.float32, device=dev)
-        call("clift_edit_active", C.byref(ms), C.byref(rec), ptr(rays), ptr(ctx.act_idx), M, ptr(ctx.xa), ptr(dirs), st)
+        call(edit_kernel % "active", C.byref(ms), *edit_args, ptr(rays), ptr(ctx.act_idx), M, ptr(ctx.xa), ptr(dirs), st)
         va = vm_struct(views, "appearance", ctx.res)
         nc = 3 * va.comps
         F = torch.empty((M, nc), dtype=torch.float32, device=dev)

@@ -24,7 +24,8 @@ def render_rays(model, renderer, rays, chunk, white_bg=False):
 
 @torch.no_grad()
 def render_rays_edit(model, renderer, rays, chunk, white_bg=False, edit=None, weight_thres=0.0):
-    """``render_rays`` under one scene edit (``edit.Edit``; engine.edit_forward): the same chunking and the same outputs.  With ``edit``
+    """``render_rays`` under one scene edit or an ordered program of them (``edit.Edit`` / ``edit.EditProgram``, handed to
+    engine.edit_forward as given): the same chunking and the same outputs.  With ``edit``
     and ``weight_thres`` bound (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``, which then cuts an edited
     frame into row-tiles over the ranks like a plain one."""
     if edit is None:

@@ -153,6 +153,23 @@ int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit,
  * clift_app_encode_points with ldd = 4). */
 int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h_edit, const float* rays, const int* act_idx, int M, float* xa,
                       float* dirs, clift_stream_t s);
+/* Edit programs (ABI 24): an ordered list e_1 .. e_n of such records, 1 <= n <= CLIFT_EDIT_MAX, applied in ONE render: scene_0 is the trained
+ * field, scene_i is e_i applied to scene_{i-1}.  A sample with world position p and view direction d is evaluated in scene_n by walking the
+ * list BACKWARDS:
+ *     in = aabb test of the UNEDITED p (taken once, before any remap)
+ *     for i = n .. 1:  src = mode_i != DUPLICATE && p in src_i;  mov = mode_i >= DUPLICATE && p in dst_i
+ *                      if the kill rule of mode_i names (src, mov): sigma = 0, stop
+ *                      if mov: p = map_m_i p + map_t_i;  d = dir_inv_i d
+ *     look the field up at (p, d)
+ * Every box test and every remap acts on the CURRENT p in fp32 with separately rounded ops.  For n = 1 this is the single edit above, bit
+ * for bit; a sample that no edit remaps or kills gets the bits of clift_density_fwd.  h_edits is a HOST array of n_edits records (it is
+ * copied into the launch: no device buffer, nothing to keep alive).  n_edits outside 1 .. CLIFT_EDIT_MAX, an unknown mode or a non-finite
+ * value in any record is an error whose message names the record's index; nothing is launched then. */
+#define CLIFT_EDIT_MAX 8
+int clift_edit_list_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens,
+                                const float* rays, int N, float* sigma, clift_stream_t s);
+int clift_edit_list_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
+                           float* xa, float* dirs, clift_stream_t s);
 
 /* ---- a7-a8: renderer.py:83-84,100-103,137,173-174,626-631 + eff_distloss (renderer.py:101).
  * Per sample alpha, T (transmittance before the sample), w = alpha*T, all (N, S).

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Render a trained scene with one boxed instance deleted, extracted, copied or moved.
+"""Render a trained scene with one boxed instance deleted, extracted, copied or moved -- or with an ordered list of such edits.
 
     python inference/edit_scene.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt --bboxes bboxes.pkl --instance ID
                                    --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz] [--pad 0.0]
                                    [--render_trajectory] [--image_dim H W] [--weight_thres 0]
+    python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
 undergoes x -> R (x - pos) + pos + t with R = Rz Ry Rx of ``--rotate_deg`` and t = ``--translate`` (contrastive_lift_amd/edit.py; the
@@ -12,9 +13,18 @@ reference's forward_duplicate / forward_manipulate arithmetic, which is not rigi
 side.  Checkpoint loading and the frame loop are those of ``inference/render_panopli.py``; under torch.distributed.run every frame is
 rendered as row-tiles over the ranks.  Writes ``rgb/*.png``, ``pred_semantics/*.png`` (uint8) and ``depth/*.npy`` under
 ``runs/<scene>_<test|trajectory>_<experiment>_edit_<op>_<id>/``.
+
+``--script FILE.json`` applies up to 8 edits in ONE render (``edit.EditProgram``), in file order.  The file holds a list of
+``{"instance": id, "op": "delete|extract|copy|move", "translate": [x, y, z], "rotate_deg": [rx, ry, rz], "pad": p, "at": "moved"}``;
+only ``instance`` and ``op`` are required.  Each entry's box is ``boxes[instance]`` AS FITTED IN THE UNEDITED SCENE, whatever earlier
+entries did: an entry that acts on an object after an earlier entry has moved it still names the same instance, and says
+``"at": "moved"`` -- its box is then the destination box of the most recent earlier ``move`` of that instance, so its motion composes
+with that move ("move it, then turn it where it now stands").  Without the flag a later entry addresses the place where the object
+stood at first.  Output goes to ``..._edit_script_<file stem>/``.
 """
 import argparse
 import functools
+import json
 import os
 import pickle
 import sys
@@ -36,16 +46,45 @@ from contrastive_lift_amd.config import load_run_config               # noqa: E4
 OPS = ("delete", "extract", "copy", "move")
 
 
-def resolve_edit(boxes, instance, op, translate=(0.0, 0.0, 0.0), rotate_deg=(0.0, 0.0, 0.0), pad=0.0):
+def resolve_edit(boxes, instance, op, translate=(0.0, 0.0, 0.0), rotate_deg=(0.0, 0.0, 0.0), pad=0.0, box=None):
+    """One edit of the fitted box of ``instance`` -- or of ``box`` (an ``EditBox``) in its place, where the object no longer stands there."""
     if instance not in boxes:
         raise SystemExit(f"instance {instance} has no box (boxes: {sorted(boxes)})")
-    box = ed.EditBox.from_fitted(boxes[instance], pad=pad)
+    box = ed.EditBox.from_fitted(boxes[instance], pad=pad) if box is None else box.padded(pad)
     if op == "delete":
         return ed.delete(box)
     if op == "extract":
         return ed.extract(box)
     R = ed.rotation_from_euler_deg(*rotate_deg)
     return (ed.copy if op == "copy" else ed.move)(box, np.asarray(translate, dtype=np.float64), R)
+
+
+_ENTRY_KEYS = {"instance", "op", "translate", "rotate_deg", "pad", "at"}
+
+
+def resolve_program(boxes, entries):
+    """The ``EditProgram`` of a ``--script`` list, in list order.  Every entry acts on ``boxes[instance]`` as fitted in the unedited scene;
+    with ``"at": "moved"`` on the destination box of the most recent earlier ``move`` of the same instance."""
+    if not isinstance(entries, list) or not 1 <= len(entries) <= ed.MAX_EDITS:
+        raise SystemExit(f"an edit script is a list of 1 to {ed.MAX_EDITS} entries")
+    edits, moved_to = [], {}
+    for i, entry in enumerate(entries):
+        if not isinstance(entry, dict) or not {"instance", "op"} <= set(entry) <= _ENTRY_KEYS:
+            raise SystemExit(f"entry {i}: needs \"instance\" and \"op\", and may hold {sorted(_ENTRY_KEYS)} only (got {entry!r})")
+        instance, op = entry["instance"], entry["op"]
+        if op not in OPS:
+            raise SystemExit(f"entry {i}: unknown op {op!r} (one of {', '.join(OPS)})")
+        at = entry.get("at", "fitted")
+        if at not in ("fitted", "moved"):
+            raise SystemExit(f"entry {i}: \"at\" is \"fitted\" or \"moved\" (got {at!r})")
+        if at == "moved" and instance not in moved_to:
+            raise SystemExit(f"entry {i}: \"at\": \"moved\" needs an earlier move of instance {instance}")
+        e = resolve_edit(boxes, instance, op, entry.get("translate", (0.0, 0.0, 0.0)), entry.get("rotate_deg", (0.0, 0.0, 0.0)),
+                         float(entry.get("pad", 0.0)), box=moved_to[instance] if at == "moved" else None)
+        if op == "move":
+            moved_to[instance] = e.dst
+        edits.append(e)
+    return ed.EditProgram(edits)
 
 
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0):
@@ -69,12 +108,14 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
     return out
 
 
-if __name__ == "__main__":
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--ckpt_path", type=str, required=True)
     ap.add_argument("--bboxes", type=str, required=True, help="bboxes.pkl of inference/fit_bboxes.py")
-    ap.add_argument("--instance", type=int, required=True, help="instance id (a key of bboxes.pkl)")
-    ap.add_argument("--op", choices=OPS, required=True)
+    ap.add_argument("--instance", type=int, help="instance id (a key of bboxes.pkl); required without --script")
+    ap.add_argument("--op", choices=OPS, help="required without --script")
+    ap.add_argument("--script", type=str, metavar="FILE.json",
+                    help="an ordered list of edits applied in one render (see the doc string); instead of --instance / --op")
     ap.add_argument("--translate", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="copy / move: translation t")
     ap.add_argument("--rotate_deg", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("RX", "RY", "RZ"),
                     help="copy / move: rotation about the box centre, R = Rz Ry Rx (degrees)")
@@ -83,11 +124,24 @@ if __name__ == "__main__":
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384])
     ap.add_argument("--weight_thres", type=float, default=0.0,
                     help="evaluate the heads where w > this (0: every sample with weight, like the reference's edit renders; 1e-4: the plain render's threshold)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.script is not None and (args.instance is not None or args.op is not None):
+        ap.error("--script holds the edits: give it without --instance / --op")
+    if args.script is None and (args.instance is None or args.op is None):
+        ap.error("--instance and --op are required without --script")
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
     cfg.subsample_frames = 1
     cfg.image_dim = list(args.image_dim)
     with open(args.bboxes, "rb") as f:
-        the_edit = resolve_edit(pickle.load(f), args.instance, args.op, args.translate, args.rotate_deg, args.pad)
-    print(edit_scene_checkpoint(cfg, the_edit, f"{args.op}_{args.instance}", test_only=not args.render_trajectory, weight_thres=args.weight_thres))
+        boxes = pickle.load(f)
+    if args.script is not None:
+        with open(args.script) as f:
+            the_edit, tag = resolve_program(boxes, json.load(f)), f"script_{Path(args.script).stem}"
+    else:
+        the_edit, tag = resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad), f"{args.op}_{args.instance}"
+    print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres))
+
+
+if __name__ == "__main__":
+    main()
