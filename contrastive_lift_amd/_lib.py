@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIFT_LIB_PATH") or os.path.join(_HERE, "libclift.so")      # (the override: timing probes of variant builds, tools/jobs)
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
@@ -141,6 +141,7 @@ _SIGNATURES = {
     "clift_knn_kth_dist": ([_P, _L, _P, _I, _I, _P, _P], C.c_int),
     "clift_segment_moments": ([_P, _L, _P, _I, _P, _P, _P, _P], C.c_int),
     "clift_segment_extent": ([_P, _L, _P, _I, _P, _P, _P, _P], C.c_int),
+    "clift_segment_mvee": ([_P, _L, _P, _I, _P, _D, _I, _P, _P, _P], C.c_int),
     "clift_label_overlap": ([_P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P], C.c_int),
     "clift_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P], C.c_int),
     "clift_ema": ([_P, _P, _L, _F, _P], C.c_int),

@@ -13,6 +13,13 @@
 //
 // k_segment_moments / k_segment_extent: one 256-thread block per instance, row lo + t + 256 j on thread t in order of j, an xor butterfly
 // inside the wave and the four wave partials added in wave order: a fixed split, the same bits on every run (no atomics).
+//
+// k_segment_mvee: the minimum-volume enclosing ellipsoid of every instance's kept rows by Khachiyan's algorithm (getMinVolEllipse :135-189,
+// the reference's DEFAULT get_tight_bbox method) with O(N) work and memory per iteration instead of the reference's N x N products.  One
+// 256-thread block per instance runs the whole loop: per iteration one pass over the rows (M_i = |L^-1 q_i|^2 from the 4 x 4 Cholesky factor,
+// the argmax as a wave butterfly + four partials, lowest row on equal values) and a few hundred scalar flops on thread 0 (step, err, the
+// rank-1 update of V, its factor), two barriers.  Thread 0 alone decides whether the loop goes on and says so in ONE LDS word that every
+// thread reads after the second barrier.  The sums (mean, first V, centre and second moment) go through p3_block_sum; no atomics anywhere.
 #include "clift_dev.h"
 
 #define P3_TILE 1024
@@ -223,4 +230,268 @@ extern "C" int clift_segment_extent(const float* pts, long n, const long* seg, i
     CLIFT_REQUIRE(seg != nullptr && frame != nullptr && out != nullptr && (pts != nullptr || n == 0), "clift_segment_extent: NULL buffer");
     k_segment_extent<<<G, P3_THREADS, 0, as_stream(s)>>>(pts, (int)n, seg, keep, frame, out);
     return clift_check_launch("clift_segment_extent");
+}
+
+// ----------------------------------------------------------------------------- minimum-volume enclosing ellipsoid (Khachiyan)
+// Choices (clift.h, ABI 25): the rows are centred on the mean of the instance's kept rows before q = (p - o, 1) is formed (M is affine
+// invariant; V stays well conditioned); V is updated by the rank-1 form (1 - step) V + step q_j q_j^T; err is the closed form
+// |step| sqrt(|u|^2 - 2 u_j + 1) with |u|^2 carried along; M_i = |L^-1 q_i|^2 with V = L L^T.  The scaling u <- (1 - step) u of iteration k is
+// applied to a row when iteration k + 1 visits it (or by the closing pass), so an iteration reads and writes every kept row once.
+#define MVEE_PIVOT_REL 1e-12
+#define MVEE_OUT 14
+
+// V = L L^T (lower), Li = L^-1.  false when a pivot is not above MVEE_PIVOT_REL of its diagonal entry or not finite (NaN compares false).
+__device__ __forceinline__ bool mvee_factor(const double (&V)[4][4], double (&Li)[4][4]) {
+    double L[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double d = V[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d = d - L[j][k] * L[j][k];
+        if (!(d > MVEE_PIVOT_REL * V[j][j] && d < INFINITY)) return false;
+        L[j][j] = sqrt(d);
+#pragma unroll
+        for (int i = j + 1; i < 4; ++i) {
+            double v = V[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        Li[j][j] = 1.0 / L[j][j];
+#pragma unroll
+        for (int i = j + 1; i < 4; ++i) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = j; k < i; ++k) v = v + L[i][k] * Li[k][j];
+            Li[i][j] = -v / L[i][i];
+        }
+    }
+    return true;
+}
+
+enum { MVEE_GO = 0, MVEE_CONVERGED = 1, MVEE_MAX_ITER = 2, MVEE_DEGENERATE = 3 };
+
+__global__ __launch_bounds__(P3_THREADS) void k_segment_mvee(const float* __restrict__ pts, int n, const long* __restrict__ seg,
+                                                             const unsigned char* __restrict__ keep, double tolerance, int max_iter,
+                                                             double* u, double* __restrict__ out) {
+    __shared__ double s_sum[10];         // results of p3_block_sum
+    __shared__ double s_li[10];          // L^-1, lower triangle row by row
+    __shared__ double s_step;            // the step whose scaling of u is still to be applied (0: none)
+    __shared__ int s_j;                  // its row
+    __shared__ int s_state;              // THE word that ends the loop: MVEE_GO or the reason it stopped, written by thread 0 only
+    __shared__ double s_m[4];
+    __shared__ int s_i[4];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lo = p3_clamp_row(seg[g], n), hi = p3_clamp_row(seg[g + 1], n);
+    double* o_g = out + (long)g * MVEE_OUT;
+
+    // kept rows and their mean
+    double a4[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = lo + tid; i < hi; i += P3_THREADS) {
+        if (keep != nullptr && keep[i] == 0) continue;
+        const float* p = pts + (long)i * 3;
+        a4[0] = __dadd_rn(a4[0], 1.0);
+        a4[1] = __dadd_rn(a4[1], (double)p[0]);
+        a4[2] = __dadd_rn(a4[2], (double)p[1]);
+        a4[3] = __dadd_rn(a4[3], (double)p[2]);
+    }
+    p3_block_sum<4>(a4, s_sum);
+    __syncthreads();
+    const double m = s_sum[0];
+    const double inv_m = 1.0 / m;
+    const double ox = s_sum[1] * inv_m, oy = s_sum[2] * inv_m, oz = s_sum[3] * inv_m;
+    __syncthreads();                                             // s_sum is written again below
+
+    // u = 1 / m on the kept rows, 0 elsewhere; V = sum u q q^T
+    double a9[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a9[k] = 0.0;
+    const bool small = !(m >= 4.0);
+    for (int i = lo + tid; i < hi; i += P3_THREADS) {
+        const bool kept = keep == nullptr || keep[i] != 0;
+        u[i] = kept && !small ? inv_m : 0.0;
+        if (!kept || small) continue;
+        const float* p = pts + (long)i * 3;
+        const double x = __dsub_rn((double)p[0], ox), y = __dsub_rn((double)p[1], oy), z = __dsub_rn((double)p[2], oz);
+        a9[0] = __dadd_rn(a9[0], x);
+        a9[1] = __dadd_rn(a9[1], y);
+        a9[2] = __dadd_rn(a9[2], z);
+        a9[3] = __dadd_rn(a9[3], __dmul_rn(x, x));
+        a9[4] = __dadd_rn(a9[4], __dmul_rn(x, y));
+        a9[5] = __dadd_rn(a9[5], __dmul_rn(x, z));
+        a9[6] = __dadd_rn(a9[6], __dmul_rn(y, y));
+        a9[7] = __dadd_rn(a9[7], __dmul_rn(y, z));
+        a9[8] = __dadd_rn(a9[8], __dmul_rn(z, z));
+    }
+    if (small) {                                                 // fewer than d + 1 points (m is block-uniform: read from LDS)
+        if (tid < MVEE_OUT) o_g[tid] = tid == 0 ? m : (tid == 3 ? 2.0 : 0.0);
+        return;
+    }
+    p3_block_sum<9>(a9, s_sum);
+    __syncthreads();
+
+    // thread 0's state of the iteration
+    double V[4][4], Li[4][4], nsq = inv_m, err = 0.0;            // |u|^2 = m (1 / m)^2
+    int iters = 0;
+    if (tid == 0) {
+        V[0][0] = s_sum[3] * inv_m; V[1][0] = s_sum[4] * inv_m; V[2][0] = s_sum[5] * inv_m; V[3][0] = s_sum[0] * inv_m;
+        V[1][1] = s_sum[6] * inv_m; V[2][1] = s_sum[7] * inv_m; V[3][1] = s_sum[1] * inv_m;
+        V[2][2] = s_sum[8] * inv_m; V[3][2] = s_sum[2] * inv_m;
+        V[3][3] = 1.0;
+        const bool ok = mvee_factor(V, Li);
+        s_state = ok ? MVEE_GO : MVEE_DEGENERATE;
+        s_step = 0.0;
+        s_j = -1;
+        if (ok) {
+            int k = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c <= r; ++c) s_li[k++] = Li[r][c];
+        }
+    }
+    __syncthreads();
+
+    int state = s_state;
+    while (state == MVEE_GO) {                                   // (thread 0 leaves MVEE_GO at iters == max_iter at the latest)
+        const double step = s_step, keep1 = 1.0 - step;
+        const int jp = s_j;
+        const double l00 = s_li[0], l10 = s_li[1], l11 = s_li[2], l20 = s_li[3], l21 = s_li[4], l22 = s_li[5], l30 = s_li[6], l31 = s_li[7],
+                     l32 = s_li[8], l33 = s_li[9];
+        double bm = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int i = lo + tid; i < hi; i += P3_THREADS) {
+            if (keep != nullptr && keep[i] == 0) continue;
+            if (step != 0.0) {                                   // the previous iteration's u <- (1 - step) u, u_j += step
+                double ui = __dmul_rn(keep1, u[i]);
+                if (i == jp) ui = __dadd_rn(ui, step);
+                u[i] = ui;
+            }
+            const float* p = pts + (long)i * 3;
+            const double x = __dsub_rn((double)p[0], ox), y = __dsub_rn((double)p[1], oy), z = __dsub_rn((double)p[2], oz);
+            const double y0 = __dmul_rn(l00, x);
+            const double y1 = __dadd_rn(__dmul_rn(l10, x), __dmul_rn(l11, y));
+            const double y2 = __dadd_rn(__dadd_rn(__dmul_rn(l20, x), __dmul_rn(l21, y)), __dmul_rn(l22, z));
+            const double y3 = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(l30, x), __dmul_rn(l31, y)), __dmul_rn(l32, z)), l33);
+            const double mi = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(y0, y0), __dmul_rn(y1, y1)), __dmul_rn(y2, y2)), __dmul_rn(y3, y3));
+            if (mi > bm) { bm = mi; bi = i; }                    // rows ascend on a thread: the first of equal values stays
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double om = __shfl_xor(bm, off);
+            const int oi = __shfl_xor(bi, off);
+            if (om > bm || (om == bm && oi < bi)) { bm = om; bi = oi; }
+        }
+        if (lane == 0) { s_m[wave] = bm; s_i[wave] = bi; }
+        __syncthreads();                                         // partials written; every u row of this pass written
+        if (tid == 0) {
+#pragma unroll
+            for (int w = 1; w < 4; ++w)
+                if (s_m[w] > bm || (s_m[w] == bm && s_i[w] < bi)) { bm = s_m[w]; bi = s_i[w]; }
+            int next = MVEE_GO;
+            double st = 0.0;
+            if (!(bm > -INFINITY && bm < INFINITY) || bi < lo || bi >= hi) {
+                next = MVEE_DEGENERATE;
+            } else {
+                st = (bm - 4.0) / (4.0 * (bm - 1.0));
+                const double uj = u[bi];
+                err = fabs(st) * sqrt(nsq - 2.0 * uj + 1.0);
+                ++iters;
+                if (!(err < INFINITY && err > -INFINITY)) {
+                    next = MVEE_DEGENERATE;
+                    st = 0.0;
+                } else {
+                    const double k1 = 1.0 - st;
+                    nsq = (k1 * k1) * nsq + 2.0 * (st * k1) * uj + st * st;
+                    if (!(err > tolerance)) next = MVEE_CONVERGED;
+                    else if (iters >= max_iter) next = MVEE_MAX_ITER;
+                    else {
+                        const float* p = pts + (long)bi * 3;
+                        const double q[4] = {__dsub_rn((double)p[0], ox), __dsub_rn((double)p[1], oy), __dsub_rn((double)p[2], oz), 1.0};
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int c = 0; c <= r; ++c) V[r][c] = k1 * V[r][c] + st * (q[r] * q[c]);
+                        if (mvee_factor(V, Li)) {
+                            int k = 0;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                                for (int c = 0; c <= r; ++c) s_li[k++] = Li[r][c];
+                        } else {
+                            next = MVEE_DEGENERATE;
+                        }
+                    }
+                }
+            }
+            s_step = st;
+            s_j = bi;
+            s_state = next;
+        }
+        __syncthreads();                                         // the decision, read by every thread from the same word
+        state = s_state;
+    }
+
+    // closing pass: the last step's scaling, then c = sum u p and the central second moment; or zeros for a degenerate instance
+    const bool bad = state == MVEE_DEGENERATE;
+    const double step = s_step, keep1 = 1.0 - step;
+    const int jp = s_j;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a9[k] = 0.0;
+    for (int i = lo + tid; i < hi; i += P3_THREADS) {
+        if (keep != nullptr && keep[i] == 0) continue;
+        if (bad) { u[i] = 0.0; continue; }
+        double ui = u[i];
+        if (step != 0.0) {
+            ui = __dmul_rn(keep1, ui);
+            if (i == jp) ui = __dadd_rn(ui, step);
+            u[i] = ui;
+        }
+        const float* p = pts + (long)i * 3;
+        const double x = __dsub_rn((double)p[0], ox), y = __dsub_rn((double)p[1], oy), z = __dsub_rn((double)p[2], oz);
+        const double ux = __dmul_rn(ui, x), uy = __dmul_rn(ui, y), uz = __dmul_rn(ui, z);
+        a9[0] = __dadd_rn(a9[0], ux);
+        a9[1] = __dadd_rn(a9[1], uy);
+        a9[2] = __dadd_rn(a9[2], uz);
+        a9[3] = __dadd_rn(a9[3], __dmul_rn(ux, x));
+        a9[4] = __dadd_rn(a9[4], __dmul_rn(ux, y));
+        a9[5] = __dadd_rn(a9[5], __dmul_rn(ux, z));
+        a9[6] = __dadd_rn(a9[6], __dmul_rn(uy, y));
+        a9[7] = __dadd_rn(a9[7], __dmul_rn(uy, z));
+        a9[8] = __dadd_rn(a9[8], __dmul_rn(uz, z));
+    }
+    p3_block_sum<9>(a9, s_sum);
+    __syncthreads();
+    if (tid == 0) {
+        o_g[0] = m;
+        o_g[1] = (double)iters;
+        o_g[2] = bad ? 0.0 : err;
+        o_g[3] = bad ? 2.0 : (state == MVEE_MAX_ITER ? 1.0 : 0.0);
+        const double cx = s_sum[0], cy = s_sum[1], cz = s_sum[2];        // centre relative to the offset o
+        o_g[4] = bad ? 0.0 : ox + cx;
+        o_g[5] = bad ? 0.0 : oy + cy;
+        o_g[6] = bad ? 0.0 : oz + cz;
+        o_g[7] = bad ? 0.0 : s_sum[3] - cx * cx;
+        o_g[8] = bad ? 0.0 : s_sum[4] - cx * cy;
+        o_g[9] = bad ? 0.0 : s_sum[5] - cx * cz;
+        o_g[10] = bad ? 0.0 : s_sum[6] - cy * cy;
+        o_g[11] = bad ? 0.0 : s_sum[7] - cy * cz;
+        o_g[12] = bad ? 0.0 : s_sum[8] - cz * cz;
+        o_g[13] = 0.0;
+    }
+}
+
+extern "C" int clift_segment_mvee(const float* pts, long n, const long* seg, int G, const unsigned char* keep, double tolerance, int max_iter,
+                                  double* u, double* out, clift_stream_t s) {
+    CLIFT_REQUIRE(n >= 0 && n <= 0x7fffffffL - P3_THREADS, "clift_segment_mvee: need 0 <= n < 2^31 - %d (got %ld)", P3_THREADS, n);
+    CLIFT_REQUIRE(G >= 0, "clift_segment_mvee: need G >= 0 (got %d)", G);
+    CLIFT_REQUIRE(max_iter >= 1 && max_iter <= 1000000, "clift_segment_mvee: need 1 <= max_iter <= 1000000 (got %d)", max_iter);
+    CLIFT_REQUIRE(tolerance > 0.0, "clift_segment_mvee: need tolerance > 0 (got %g)", tolerance);
+    if (G == 0) return 0;
+    CLIFT_REQUIRE(seg != nullptr && out != nullptr && ((pts != nullptr && u != nullptr) || n == 0), "clift_segment_mvee: NULL buffer");
+    k_segment_mvee<<<G, P3_THREADS, 0, as_stream(s)>>>(pts, (int)n, seg, keep, tolerance, max_iter, u, out);
+    return clift_check_launch("clift_segment_mvee");
 }

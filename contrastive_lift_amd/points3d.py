@@ -4,7 +4,8 @@
 The reference handles one instance at a time on the host (boolean mask, KD-tree, 10-NN query, percentile, 3-sigma cut, PCA).  Here the
 rows are sorted by instance once and every step runs for all instances of a scene at once: the k-th neighbour distances, the moments and
 the extents in libclift.so (csrc/points3d.hip: clift_knn_kth_dist, clift_segment_moments, clift_segment_extent), the percentile selection,
-the 3 x 3 eigen-decomposition and the sorting in torch / numpy.  ``backend="sklearn"`` is the same function on the host with
+the 3 x 3 eigen-decomposition and the sorting in torch / numpy.  The reference's default method, the minimum-volume enclosing ellipsoid
+(``getMinVolEllipse`` :135-189), is ``fit_instance_ellipsoids``: Khachiyan's loop for all instances in one launch (clift_segment_mvee).  ``backend="sklearn"`` is the same function on the host with
 ``sklearn.neighbors.KDTree`` and numpy, for machines without a GPU; both backends take their statistics in fp64 (the reference takes mean and
 std of a float32 array in float32, so a point lying on the 3-sigma face can fall either way there).
 """
@@ -67,6 +68,23 @@ def segment_extent(pts, seg, frame, keep=None):
     out = torch.empty((G, 6), dtype=torch.float64, device=pts.device)
     _lib.call("clift_segment_extent", _lib.ptr(pts), n, _lib.ptr(seg), G, _lib.ptr(keep), _lib.ptr(frame), _lib.ptr(out), _lib.stream())
     return out
+
+
+MVEE_COLUMNS = 14                                  # m, iters, err, status, c (3), Cxx Cxy Cxz Cyy Cyz Czz, 0
+MVEE_PIVOT_REL = 1e-12                             # csrc/points3d.hip: a Cholesky pivot not above this share of its diagonal entry = not positive definite
+
+
+def segment_mvee(pts, seg, keep=None, tolerance=0.01, max_iter=10000):
+    """clift_segment_mvee: Khachiyan's minimum-volume enclosing ellipsoid of every instance's kept rows, the whole loop in one launch.
+    Returns (out (G, 14) fp64 = m, iters, err, status, centre (3), Cxx Cxy Cxz Cyy Cyz Czz, 0; u (n,) fp64 weights).  status 0 converged,
+    1 stopped at max_iter, 2 degenerate (fewer than 4 kept rows, coplanar / collinear rows: centre, C and the instance's u are 0)."""
+    n, G = _check_sorted_input(pts, seg)
+    keep = _keep_arg(keep, n, pts.device)
+    out = torch.empty((G, MVEE_COLUMNS), dtype=torch.float64, device=pts.device)
+    u = torch.zeros((n,), dtype=torch.float64, device=pts.device)
+    _lib.call("clift_segment_mvee", _lib.ptr(pts), n, _lib.ptr(seg), G, _lib.ptr(keep), float(tolerance), int(max_iter), _lib.ptr(u), _lib.ptr(out),
+              _lib.stream())
+    return out, u
 
 
 # ----------------------------------------------------------------------------------------------------------------- grouping
@@ -236,12 +254,14 @@ def fit_instance_boxes(points, labels, method="pca", max_points=50000, generator
 
     "simple": centre = mean of the kept points, box = their min / max minus the centre, identity orientation.  "pca": centre = mean,
     axes = eigenvectors of the covariance by descending eigenvalue, each signed so that its largest component is positive, box = extent of
-    the kept points along the axes.  "ellipsoid" and "oriented" of the reference are not built (its Khachiyan loop forms an N x N matrix,
-    its minimum-volume box returns after the first hull face): ValueError.
+    the kept points along the axes.  "ellipsoid" and "oriented" of the reference are not built HERE: ValueError.  The ellipsoid is
+    ``fit_instance_ellipsoids`` (the reference's Khachiyan loop forms an N x N matrix; that function does not); "oriented" stays refused:
+    the reference's ``getMinVolBox`` returns from inside its loop after the first hull face.
 
     ``return_info=True`` returns ``(boxes, {"kept": {id: n}, "total": {id: n}, "keep": (P,) bool mask of the rows the boxes were fitted to})``."""
     if method not in METHODS:
-        raise ValueError(f"method {method!r} is not built: choose one of {METHODS} (\"pca\" or \"simple\")")
+        raise ValueError(f"method {method!r} is not built: choose one of {METHODS} (\"pca\" or \"simple\")"
+                         + ("; the ellipsoid is fit_instance_ellipsoids" if method == "ellipsoid" else ""))
     pts, lab = _as_inputs(points, labels, backend)
     order, ids, seg = group_by_instance(lab, 0)
     total = (seg[1:] - seg[:-1]).cpu().numpy()
@@ -288,3 +308,130 @@ def fit_instance_boxes(points, labels, method="pca", max_points=50000, generator
     mask = torch.zeros(pts.shape[0], dtype=torch.bool, device=pts.device)
     mask[order] = keep
     return boxes, {"kept": kept, "total": {i: int(t) for i, t in zip(ids.cpu().numpy().tolist(), total)}, "keep": mask}
+
+
+# ----------------------------------------------------------------------------------------------------------------- ellipsoids
+def _mvee_factor(V):
+    """L^-1 of V = L L^T (4 x 4, lower) with the kernel's rule: None when a pivot is not above MVEE_PIVOT_REL of its diagonal entry."""
+    L = np.zeros((4, 4))
+    for j in range(4):
+        d = V[j, j] - L[j, :j] @ L[j, :j]
+        if not (d > MVEE_PIVOT_REL * V[j, j] and d < np.inf):
+            return None
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, 4):
+            L[i, j] = (V[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
+    return np.linalg.solve(L, np.eye(4))
+
+
+def _mvee_host(S, tolerance, max_iter):
+    """One instance of clift_segment_mvee on the host, with the kernel's choices (rows centred on their mean, rank-1 update of V, Cholesky
+    factor, closed-form err): O(rows) per iteration, never the reference's N x N products.  S (m, 3) fp64.  Returns (row of MVEE_COLUMNS
+    numbers, u (m,))."""
+    m = S.shape[0]
+    row = np.zeros(MVEE_COLUMNS)
+    row[0], row[3] = m, 2
+    if m < 4:
+        return row, np.zeros(m)
+    o = S.sum(0) / m
+    q = np.concatenate([S - o, np.ones((m, 1))], 1)
+    u = np.full(m, 1.0 / m)
+    V = (q.T @ q) / m
+    V[3, 3] = 1.0
+    nsq, iters, err, status = 1.0 / m, 0, 0.0, 2
+    with np.errstate(all="ignore"):
+        while True:
+            Li = _mvee_factor(V)
+            if Li is None:
+                break
+            y = q @ Li.T
+            M = (y * y).sum(1)
+            j = int(np.argmax(M))                                                  # the lowest row on equal values
+            Mj = M[j]
+            if not np.isfinite(Mj):
+                break
+            step = (Mj - 4.0) / (4.0 * (Mj - 1.0))
+            uj = u[j]
+            err = abs(step) * np.sqrt(nsq - 2.0 * uj + 1.0)
+            iters += 1
+            if not np.isfinite(err):
+                break
+            k1 = 1.0 - step
+            nsq = (k1 * k1) * nsq + 2.0 * (step * k1) * uj + step * step
+            u = k1 * u
+            u[j] += step
+            if not err > tolerance:
+                status = 0
+                break
+            if iters >= max_iter:
+                status = 1
+                break
+            V = k1 * V + step * np.outer(q[j], q[j])
+    row[1] = iters
+    if status == 2:
+        return row, np.zeros(m)
+    p = q[:, :3]
+    c = u @ p
+    C = (p * u[:, None]).T @ p - np.outer(c, c)
+    row[2], row[3], row[4:7] = err, status, o + c
+    row[7:13] = C[[0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]]
+    return row, u
+
+
+def fit_instance_ellipsoids(points, labels, tolerance=0.01, max_iter=10000, max_points=50000, generator=None, backend="device", k=10,
+                            keep_percentile=70, n_sigma=3, return_info=False):
+    """The reference's ``get_tight_bbox(..., method="ellipsoid")`` (visualize_bboxes.py:101-107, its default): per instance the
+    minimum-volume enclosing ellipsoid of the filtered points by Khachiyan's algorithm (``getMinVolEllipse`` :135-189) and the box that
+    circumscribes it, ``{instance_id: {"bbox": ((-r0, -r1, -r2), (r0, r1, r2)), "orientation": rotation (3, 3), "position": centre (3,)}}``
+    with numpy fp64 values.  Rows of ``rotation`` are the ellipsoid's axes (ascending radius, from ``svd(inv(C) / 3)`` as :180-187), so the
+    record is in the box frame ``orientation @ (p - position)`` like the boxes of ``fit_instance_boxes``.
+
+    Grouping, subsample (``max_points``, ``generator``) and filter (``k``, ``keep_percentile``, ``n_sigma``) are those of
+    ``fit_instance_boxes``.  The loop needs a 4 x 4 moment matrix, its Cholesky factor, one quadratic form per point and an argmax per
+    iteration -- the reference builds ``np.diag(u)`` and ``QT V^-1 Q``, N x N each (10 GB at its own cap of 50 000 points).  As in the
+    reference the loop ends when the weights move by no more than ``tolerance`` (at least one iteration), so the ellipsoid need not strictly
+    enclose: at 0.01 the worst point lies at about 1.05 in the ellipsoid's norm.  ``max_iter`` bounds the loop, which the reference does not.
+
+    ``backend="device"``: all instances in one launch of clift_segment_mvee.  ``backend="sklearn"``: the same loop in numpy per instance.
+    Label 0, instances with fewer than k points and DEGENERATE instances (fewer than 4 kept points, or coplanar / collinear kept points: the
+    moment matrix is not positive definite) are left out; the reference raises ``numpy.linalg.LinAlgError`` for singular ones or returns
+    what the inverse of a near-singular matrix gives.  Instances stopped at ``max_iter`` are returned and listed in
+    ``info["not_converged"]``.
+
+    ``return_info=True`` returns ``(boxes, {"iters": {id: n}, "err": {id: x}, "kept": {id: n}, "total": {id: n}, "not_converged": [ids],
+    "keep": (P,) bool mask of the rows the ellipsoids were fitted to})``."""
+    pts, lab = _as_inputs(points, labels, backend)
+    order, ids, seg = group_by_instance(lab, 0)
+    total = (seg[1:] - seg[:-1]).cpu().numpy()
+    order, seg = _subsample(order, seg, int(max_points), generator)
+    ps = pts[order].contiguous()
+    G = ids.numel()
+    _, _, keep = _filter_sorted(ps, seg, int(k), keep_percentile, n_sigma, backend)
+    keep = keep.to(pts.device).contiguous()
+    if backend == "device":
+        rows = segment_mvee(ps, seg, keep, tolerance, max_iter)[0].cpu().numpy()
+    else:
+        if not (tolerance > 0 and 1 <= int(max_iter) <= 1000000):
+            raise ValueError(f"need tolerance > 0 and 1 <= max_iter <= 1000000, got {tolerance} and {max_iter}")
+        P_all, keep_np, edges = ps.numpy(), keep.numpy(), seg.numpy()
+        rows = np.zeros((G, MVEE_COLUMNS))
+        for g in range(G):
+            S = P_all[edges[g]:edges[g + 1]][keep_np[edges[g]:edges[g + 1]]].astype(np.float64)
+            rows[g] = _mvee_host(S, float(tolerance), int(max_iter))[0]
+    boxes, kept, iters, err, not_converged = {}, {}, {}, {}, []
+    for g, inst_id in enumerate(ids.cpu().numpy().tolist()):
+        kept[inst_id], iters[inst_id], err[inst_id] = int(rows[g, 0]), int(rows[g, 1]), float(rows[g, 2])
+        if rows[g, 3] == 2:
+            continue
+        if rows[g, 3] == 1:
+            not_converged.append(inst_id)
+        A = np.linalg.inv(rows[g, [7, 8, 9, 8, 10, 11, 9, 11, 12]].reshape(3, 3)) / 3.0
+        _, sv, rotation = np.linalg.svd(A)
+        radii = 1.0 / np.sqrt(sv)
+        boxes[inst_id] = {"bbox": (-radii, radii.copy()), "orientation": rotation, "position": rows[g, 4:7].copy()}
+    if not return_info:
+        return boxes
+    mask = torch.zeros(pts.shape[0], dtype=torch.bool, device=pts.device)
+    mask[order] = keep
+    return boxes, {"iters": iters, "err": err, "kept": kept, "total": {i: int(t) for i, t in zip(ids.cpu().numpy().tolist(), total)},
+                   "not_converged": not_converged, "keep": mask}

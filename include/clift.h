@@ -594,6 +594,26 @@ int clift_segment_moments(const float* pts, long n, const long* seg, int G, cons
  * An instance without kept rows gets +inf / -inf. */
 int clift_segment_extent(const float* pts, long n, const long* seg, int G, const unsigned char* keep, const double* frame, double* out,
                          clift_stream_t s);
+/* clift_segment_mvee (ABI 25): the minimum-volume enclosing ellipsoid of every instance's kept rows by Khachiyan's algorithm (the reference's
+ * getMinVolEllipse, visualize_bboxes.py:135-189, its default get_tight_bbox method) in O(rows) work and memory per iteration, all instances in
+ * ONE launch, one workgroup per instance, the loop inside the kernel.  With m = the number of kept rows of instance g, d = 3, q_i = (p_i, 1),
+ * u_i = 1 / m:  repeat  V = sum u_i q_i q_i^T,  M_i = q_i^T V^-1 q_i,  j = argmax M (the LOWEST row on equal values),
+ * step = (M_j - d - 1) / ((d + 1) (M_j - 1)),  u <- (1 - step) u,  u_j += step,  err = |u_new - u_old|_2  while err > tolerance (at least once)
+ * and fewer than max_iter iterations were made.  Then c = sum u_i p_i and C = sum u_i p_i p_i^T - c c^T.
+ * u (n) fp64: the weights; 0 on rows that are not kept and on every row of a status-2 instance.  Rows outside [seg[0], seg[G]) are not written.
+ * out (G, 14) fp64 = m, iters, err, status, c (3), Cxx Cxy Cxz Cyy Cyz Czz, 0.
+ * status 0: converged.  1: stopped at max_iter (c and C of the last iterate).  2: degenerate -- m < 4 (an empty instance included), or V not
+ * positive definite at some iteration (a Cholesky pivot not above 1e-12 of its diagonal entry: coplanar or collinear points), or a non-finite
+ * pivot, M_j or err; c, C and err are then 0.  One instance's failure touches no other instance's output.
+ * Choices taken: the rows are centred on the fp64 mean of the instance's kept rows before q is formed (M is affine invariant; V stays well
+ * conditioned); V follows the rank-1 form (1 - step) V + step q_j q_j^T after the first sum; M_i = |L^-1 q_i|^2 with V = L L^T (Cholesky);
+ * err is the closed form |step| sqrt(|u|^2 - 2 u_j + 1) with |u|^2 carried by its own recurrence.  All arithmetic fp64, products and sums
+ * rounded separately; the sums run over the fixed split of clift_segment_moments and the argmax is exact, so two runs give the same bits, u
+ * included (no atomics).  Whether the loop goes on is decided by one thread per iteration and read by all from one LDS word; max_iter bounds
+ * the loop unconditionally.  Errors: n or G out of range as above, max_iter outside [1, 1000000], tolerance <= 0 (or NaN), a NULL required
+ * buffer.  G == 0 returns 0 before any launch. */
+int clift_segment_mvee(const float* pts, long n, const long* seg, int G, const unsigned char* keep, double tolerance, int max_iter, double* u,
+                       double* out, clift_stream_t s);
 
 /* ---- scoring (ABI 22; csrc/overlap.hip): the joint histogram of two label maps, per frame, after a per-frame class remapping -- the table under
  * panoptic quality, the confusion matrix and the robust-class shares (contrastive_lift_amd/overlap.py).  Everything is DEVICE memory.  a_cls,
