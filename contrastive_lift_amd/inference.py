@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine
+from .hdbscan import DeviceHDBSCAN
 
 
 @torch.no_grad()
@@ -133,21 +134,32 @@ def assign_clusters(all_thing_features, all_points_semantics, all_centroids, dev
     return _one_hot(labels, num_images, device)
 
 
-def _hdbscan_fit(pts, cluster_size):
+def _check_hdbscan(hdbscan):
+    if hdbscan not in ("sklearn", "device"):
+        raise ValueError(f"hdbscan must be 'sklearn' or 'device' (got {hdbscan!r})")
+    return hdbscan
+
+
+def _hdbscan_fit(pts, cluster_size, hdbscan="sklearn", device=None):
     """RP:236-241 / 321-326: HDBSCAN(min_cluster_size, min_samples=1, allow_single_cluster=True) on the rescaled subsample; returns
     (labels, centroids (K, d) or None when every point is noise).  centroid k = the membership-probability-weighted mean of cluster k's
     points -- the ``weighted_cluster_centroid`` of the hdbscan package the reference imports.  That package is not in this image: the fit
     comes from the package when it is importable and otherwise from ``sklearn.cluster.HDBSCAN`` (scikit-learn >= 1.3: the same algorithm,
     adopted from that package -- mutual-reachability MST, condensed tree, excess-of-mass selection; PARITY UNPINNED against the package
-    itself)."""
-    try:
-        import hdbscan as _pkg                                     # the reference's dependency (requirements.txt)
-        cl = _pkg.HDBSCAN(min_cluster_size=cluster_size, min_samples=1, prediction_data=True, allow_single_cluster=True).fit(pts)
+    itself).  ``hdbscan="device"`` runs the same fit as DeviceHDBSCAN (hdbscan.py: the minimum spanning tree by
+    clift_emst on ``device``, the tree pass on the host), pinned to sklearn's estimator: equal labels, probabilities to rounding."""
+    if _check_hdbscan(hdbscan) == "device":
+        cl = DeviceHDBSCAN(cluster_size, min_samples=1, allow_single_cluster=True, device="cuda" if device is None else device).fit(pts)
         labels, prob = cl.labels_, cl.probabilities_
-    except ImportError:
-        from sklearn.cluster import HDBSCAN
-        cl = HDBSCAN(min_cluster_size=cluster_size, min_samples=1, allow_single_cluster=True, copy=True).fit(pts)
-        labels, prob = cl.labels_, cl.probabilities_
+    else:
+        try:
+            import hdbscan as _pkg                                 # the reference's dependency (requirements.txt)
+            cl = _pkg.HDBSCAN(min_cluster_size=cluster_size, min_samples=1, prediction_data=True, allow_single_cluster=True).fit(pts)
+            labels, prob = cl.labels_, cl.probabilities_
+        except ImportError:
+            from sklearn.cluster import HDBSCAN
+            cl = HDBSCAN(min_cluster_size=cluster_size, min_samples=1, allow_single_cluster=True, copy=True).fit(pts)
+            labels, prob = cl.labels_, cl.probabilities_
     ids = [k for k in np.unique(labels) if k != -1]
     if not ids:
         return labels, None
@@ -253,13 +265,14 @@ def _meanshift(pts, bandwidth, meanshift, device):
 
 
 def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000, use_silverman=False, use_dbscan=False, cluster_size=500,
-            meanshift="sklearn"):
+            meanshift="sklearn", hdbscan="sklearn"):
     """RP:196-263: 3-sigma outlier filter, per-axis rescale to the
     unit box, a 50000-point subsample drawn with ``np.random.choice`` from numpy's GLOBAL generator exactly as the reference
     does (seed it with ``np.random.seed`` for reproducible runs), sklearn MeanShift (optionally with Silverman's bandwidth) or, with
     ``use_dbscan``, HDBSCAN (``_hdbscan_fit``), then every pixel is assigned to its nearest cluster.  Returns (one-hot (num_images, P, K+1) float64, centroids in feature
     units).  Scenes with fewer thing pixels than ``num_points`` use all of them (the reference raises there).  ``meanshift="device"`` runs
-    the MeanShift fit as DeviceMeanShift (GPU) instead of sklearn."""
+    the MeanShift fit as DeviceMeanShift (GPU) instead of sklearn, ``hdbscan="device"`` the HDBSCAN fit as DeviceHDBSCAN."""
+    _check_hdbscan(hdbscan)
     feats = np.asarray(all_thing_features)
     thing = feats[..., 0] == -float("inf")
     f_th = feats[thing][:, 1:]
@@ -276,7 +289,7 @@ def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000,
         from scipy.stats import gaussian_kde
         bandwidth = gaussian_kde(pts.T, bw_method="silverman").covariance_factor()
     if use_dbscan:                                                # RP:236-255: HDBSCAN on the subsample, then EVERY point to its nearest centroid
-        _, centers = _hdbscan_fit(pts, cluster_size)
+        _, centers = _hdbscan_fit(pts, cluster_size, hdbscan, device)
         if centers is None:
             raise _lib.CliftError("HDBSCAN found no cluster (every sampled point is noise); the reference fails here too (np.stack of an empty list)")
         all_labels = _nearest_centroid((f_all.reshape(-1, f_all.shape[-1]) - bias) * factor, centers, device)
@@ -293,15 +306,16 @@ def cluster(all_thing_features, bandwidth, device, num_images, num_points=50000,
 
 
 def cluster_segmentwise(all_thing_features, all_points_semantics, bandwidth, device, num_images, num_points=50000, use_silverman=False,
-                        use_dbscan=False, cluster_size=500, meanshift="sklearn", return_dict=False):
+                        use_dbscan=False, cluster_size=500, meanshift="sklearn", return_dict=False, hdbscan="sklearn"):
     """RP:265-368: the clustering of ``cluster`` (MeanShift, or HDBSCAN with ``use_dbscan``) run separately inside every predicted thing class, labels of
     successive classes offset so they stay disjoint; classes with fewer than 100 (filtered) points get no instances (-1).
     Returns (one-hot (num_images, P, max label + 2) float64, concatenated centroids in feature units).  Like the reference,
     a class that is skipped for having too few points still appends the previous class's centroids (rescaled with its own
     statistics) to the returned list -- only the one-hot output is consumed by the render script.  ``meanshift="device"`` runs the fits
-    as DeviceMeanShift.  With ``return_dict`` the centroids come back as the reference's per-class cache (extract_train_centroids.py:211-313):
+    as DeviceMeanShift, ``hdbscan="device"`` the HDBSCAN fits as DeviceHDBSCAN.  With ``return_dict`` the centroids come back as the reference's per-class cache (extract_train_centroids.py:211-313):
     ``{thing class (np.int64): centroids in feature units}``, incl. that stale entry for a skipped class; this is the mapping that
     ``assign_clusters`` (--cached_centroids_path) reads."""
+    _check_hdbscan(hdbscan)
     sem = torch.cat([s_.cpu() for s_ in all_points_semantics], 0).argmax(-1).numpy()
     feats = np.asarray(all_thing_features)
     thing = feats[..., 0] == -float("inf")
@@ -326,7 +340,7 @@ def cluster_segmentwise(all_thing_features, all_points_semantics, bandwidth, dev
         idx = np.arange(cr.shape[0]) if cr.shape[0] < num_points else np.random.choice(cr.shape[0], num_points, replace=False)
         pts = cr[idx]
         if use_dbscan:                                              # RP:320-342
-            _, cents = _hdbscan_fit(pts, cluster_size)
+            _, cents = _hdbscan_fit(pts, cluster_size, hdbscan, device)
             if cents is not None:
                 centroids = cents
                 lab = _nearest_centroid((fc.reshape(-1, fc.shape[-1]) - bias) * factor, cents, device).astype(np.int32)

@@ -571,6 +571,33 @@ int clift_nearest_centroid(const float* feat, int ldf, int E, const float* centr
 int clift_meanshift(const float* X, long n, int ldx, int d, const float* seeds, int S, double bandwidth, int max_iter,
                     float* centers, int* counts, int* iters, clift_stream_t s);
 
+/* ---- Euclidean minimum spanning tree (ABI 26; csrc/emst.hip): the tree under HDBSCAN(min_samples = 1), which the reference fits on the CPU for
+ * every --use_dbscan clustering (inference/render_panopli.py:236-241, 321-326).  With min_samples = 1 all core distances are 0 and the
+ * mutual-reachability graph is the plain Euclidean graph.  X (n, ldx) fp32 device rows, the first d columns used.  Writes the n - 1 edges of a
+ * minimum spanning tree of the complete graph: edge_a[e] < edge_b[e] point indices, edge_w[e] = sqrt(d2) in fp64, correctly rounded, with
+ * d2 = sum_k (double(x_ak) - double(x_bk))^2 added in dimension order, every product and sum rounded separately (no contraction) -- the
+ * arithmetic of clift_knn_kth_dist, and the number sklearn's fp64 tree computes.  Brute-force Boruvka under the STRICT edge order
+ * (d2, min(i, j), max(i, j)): per round every point finds its smallest-key edge to another component (all comparisons on the fp64 d2), every
+ * component takes the smallest of them (integer atomicMin on the bits of d2, then on min * n + max), hooks to the component the edge leads to
+ * (of a mutual pair the smaller root stays) and writes the edge into the slot of its dying root; the used slots are packed in ascending slot
+ * order.  Two runs give the same bits, edge order included; the weight multiset is that of every minimum spanning tree.  The fixed maximum of
+ * ceil(log2 n) rounds is launched without a host sync (separate launches on the stream, no grid-wide barrier); the kernels of a round return at
+ * once when one component is left.
+ * info (4 ints, device): rounds executed; components left (1 on success); fault flags (0 on success); 0.  Fault flags: 1 = a root chain longer
+ * than n (internal); 2 = NON-FINITE INPUT: some point had no finite d2 to any point of another component (a NaN or infinite coordinate, or a d2
+ * that overflows) -- such candidates are never taken, the components they would join stay apart, components left is then > 1 and the edges past
+ * the n - components written ones are (-1, -1, 0); 4 = an edge key that does not decode (internal).  The call never loops on such input: every
+ * device loop is bounded by n or by its slice.  The caller reads info and treats fault != 0 or components != 1 as an error.
+ * work: a device buffer of at least CLIFT_EMST_WORK_BYTES(n) bytes, 8-byte aligned, contents irrelevant before and undefined after.
+ * Errors (non-zero return, nothing launched): n outside [2, CLIFT_EMST_MAX_N] (the work is O(n^2 log n); the callers subsample to 50 000), d outside
+ * [1, 32], ldx < d, a NULL buffer, a misaligned work, work_bytes too small.  d == 3 is the specialised instantiation. */
+#define CLIFT_EMST_MAX_N 131072
+#define CLIFT_EMST_SPLITS 16
+#define CLIFT_EMST_WORK_BYTES(n) (256L + (long)(n) * (3L * 8 + CLIFT_EMST_SPLITS * 8L + 5L * 4 + CLIFT_EMST_SPLITS * 4L))
+long clift_emst_work_bytes(long n);      /* CLIFT_EMST_WORK_BYTES(n) for callers that cannot see the macro */
+int clift_emst(const float* X, long n, int ldx, int d, int* edge_a, int* edge_b, double* edge_w, int* info, void* work, long work_bytes,
+               clift_stream_t s);
+
 /* ---- instances in 3-D (ABI 20; csrc/points3d.hip): the per-instance steps of the reference's inference/visualize_bboxes.py (filter_pointcloud
  * :52-74, get_tight_bbox :78-131) for ALL instances of a scene per launch.  pts (n, 3) fp32, rows SORTED BY INSTANCE; seg (G + 1) int64 device
  * offsets, non-decreasing, 0 <= seg[g] <= n: instance g owns rows seg[g] .. seg[g+1] (may be empty).  n < 2^31 - 1024.  Entries of seg outside

@@ -3,7 +3,7 @@
 rendered instance features class by class and cache the per-class centroids that ``render_panopli.py --cached_centroids_path`` reads.
 
     python inference/extract_train_centroids.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt --segmentwise [--bandwidth 0.15]
-                                                [--meanshift device|sklearn] [--split train|test] [--use_dbscan] [--subsample 1] ...
+                                                [--meanshift device|sklearn] [--split train|test] [--use_dbscan [--hdbscan sklearn|device]] [--subsample 1] ...
 
 Which frames: like the reference, the ``train`` split of a PanopLi-layout scene but the ``test`` split of a MOS scene (the reference builds
 its MOS dataset with "test", :44-54); ``--split`` overrides that, ``--render_trajectory`` renders trajectories/trajectory_blender.pkl
@@ -12,6 +12,7 @@ instead.  Writes ``instance_features.npy``, ``thing_features.npy``, ``slow_featu
 ``runs/<scene>_<trajectory|train>_<experiment>[_dbscan][_seg]_clust<cluster_size>/``.
 
 The MeanShift fits run on the GPU (``--meanshift device``, contrastive_lift_amd.inference.DeviceMeanShift) unless ``--meanshift sklearn``.
+With ``--use_dbscan`` the per-class HDBSCAN fits run in sklearn on the CPU unless ``--hdbscan device`` (contrastive_lift_amd.hdbscan.DeviceHDBSCAN).
 ``--segmentwise`` is required: the cache is per class, and without it the reference writes the features and then dies (:143-148).
 Under torch.distributed.run every rank renders a row-tile of each frame (as render_panopli.py); rank 0 clusters and writes.
 """
@@ -83,7 +84,7 @@ def output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise, 
 
 
 def extract_train_centroids(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=True, use_silverman=False,
-                            cluster_size=500, meanshift="device", split=None, device="cuda:0"):
+                            cluster_size=500, meanshift="device", split=None, device="cuda:0", hdbscan="sklearn"):
     if not segmentwise:
         raise ValueError("extract_train_centroids: the centroid cache is per thing class and needs --segmentwise "
                          "(without it the reference script fails after writing the features)")
@@ -106,7 +107,8 @@ def extract_train_centroids(config, trajectory_name, test_only=True, bandwidth=0
     if model.slow_fast_mode:
         np.save(out / "slow_features.npy", torch.cat(slows, 0).cpu().numpy())
     _, cents = inf.cluster_segmentwise(all_thing, sems, bandwidth, device, num_images=len(rgbs), use_silverman=use_silverman,
-                                       use_dbscan=use_dbscan, cluster_size=cluster_size, meanshift=meanshift, return_dict=True)
+                                       use_dbscan=use_dbscan, cluster_size=cluster_size, meanshift=meanshift, return_dict=True,
+                                       hdbscan=hdbscan)
     with open(out / "all_centroids.pkl", "wb") as f:
         pickle.dump(cents, f)
     return out
@@ -124,6 +126,9 @@ if __name__ == "__main__":
     ap.add_argument("--use_silverman", action="store_true")
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="reference hard-codes [256, 384] (:338)")
     ap.add_argument("--meanshift", choices=("device", "sklearn"), default="device", help="where the MeanShift fits run")
+    ap.add_argument("--hdbscan", choices=("sklearn", "device"), default="sklearn",
+                    help="where the HDBSCAN fits of --use_dbscan run: sklearn on the CPU (the reference) or the GPU "
+                         "(DeviceHDBSCAN: clift_emst + the host tree pass, pinned to sklearn's estimator)")
     ap.add_argument("--split", choices=("train", "test"), default=None, help="frames to render (default: train; test for MOS scenes, as the reference)")
     args = ap.parse_args()
     if not args.segmentwise:
@@ -134,4 +139,4 @@ if __name__ == "__main__":
     cfg.image_dim = list(args.image_dim)
     print(extract_train_centroids(cfg, "trajectory_blender", test_only=not args.render_trajectory, bandwidth=args.bandwidth,
                                   use_dbscan=args.use_dbscan, segmentwise=True, use_silverman=args.use_silverman,
-                                  cluster_size=args.cluster_size, meanshift=args.meanshift, split=args.split))
+                                  cluster_size=args.cluster_size, meanshift=args.meanshift, split=args.split, hdbscan=args.hdbscan))

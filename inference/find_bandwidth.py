@@ -3,7 +3,7 @@
 min_cluster_size) of a trained scene by panoptic quality against the 2-D pseudo-labels of the training frames.
 
     python inference/find_bandwidth.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt [--segmentwise] [--use_dbscan]
-                                       [--meanshift device|sklearn] [--sweep START STOP STEP] [--subsample 5] ...
+                                       [--meanshift device|sklearn] [--hdbscan sklearn|device] [--sweep START STOP STEP] [--subsample 5] ...
 
 As the reference: renders the ``train`` split, merges every thing class into the first thing class (the predicted semantics here, the
 pseudo-label semantics in the scoring), sweeps sqrt(max_instances)/3.5 * (1..49)/50 for MOS scenes and (1..24)/25 otherwise (HDBSCAN:
@@ -13,7 +13,8 @@ pseudo-label semantics in the scoring), sweeps sqrt(max_instances)/3.5 * (1..49)
 scenes against m2f_semantics / m2f_instance with the ``--things_csv`` list and class 0 void).  Ties go to the later value.
 Writes ``runs/<experiment>/all_thing_features_train.npy``, ``bandwidth_vs_pq.png`` and ``bandwidth_vs_pq.json`` ((value, pq) pairs and
 the best value).  The MeanShift fits run on the GPU (``--meanshift device``) unless ``--meanshift sklearn``; ``--sweep`` replaces the
-reference's range (np.arange(START, STOP, STEP)).
+reference's range (np.arange(START, STOP, STEP)).  With ``--use_dbscan`` the HDBSCAN fits (one per value, times the class count when
+segmentwise) run in sklearn on the CPU unless ``--hdbscan device`` (DeviceHDBSCAN); the JSON records which under ``"hdbscan"``.
 """
 import argparse
 import json
@@ -91,7 +92,7 @@ def read_is_thing(things_csv):
 
 
 def find_bandwidth(config, debug=False, segmentwise=False, use_dbscan=False, meanshift="device", sweep=None,
-                   things_csv="resources/scannet_reduced_things.csv", device="cuda:0"):
+                   things_csv="resources/scannet_reduced_things.csv", device="cuda:0", hdbscan="sklearn"):
     out = Path("runs") / Path(config.experiment)
     out.mkdir(exist_ok=True, parents=True)
     rank, device = init_ranks(device)
@@ -116,7 +117,7 @@ def find_bandwidth(config, debug=False, segmentwise=False, use_dbscan=False, mea
     for val in values:
         val = float(val) if not use_dbscan else int(val)
         try:
-            kw = dict(bandwidth=0.15, cluster_size=val, use_dbscan=True) if use_dbscan else dict(bandwidth=val, meanshift=meanshift)
+            kw = dict(bandwidth=0.15, cluster_size=val, use_dbscan=True, hdbscan=hdbscan) if use_dbscan else dict(bandwidth=val, meanshift=meanshift)
             if segmentwise:
                 insts, _ = inf.cluster_segmentwise(all_thing, sems, device=device, num_images=len(names), **kw)
             else:
@@ -148,7 +149,8 @@ def find_bandwidth(config, debug=False, segmentwise=False, use_dbscan=False, mea
     plt.savefig(out / "bandwidth_vs_pq.png")
     plt.close()
     result = {"values": [[v, p] for v, p in curve], "best": best_val, "best_pq": best_pq, "use_dbscan": bool(use_dbscan),
-              "segmentwise": bool(segmentwise), "meanshift": None if use_dbscan else meanshift}
+              "segmentwise": bool(segmentwise), "meanshift": None if use_dbscan else meanshift,
+              "hdbscan": hdbscan if use_dbscan else None}
     (out / "bandwidth_vs_pq.json").write_text(json.dumps(result, indent=1))
     print(f"Best bandwidth: {best_val}, pq: {best_pq}")
     return result
@@ -162,6 +164,9 @@ if __name__ == "__main__":
     ap.add_argument("--segmentwise", action="store_true", help="segmentwise clustering")
     ap.add_argument("--use_dbscan", action="store_true", help="HDBSCAN for clustering")
     ap.add_argument("--meanshift", choices=("device", "sklearn"), default="device", help="where the MeanShift fits run")
+    ap.add_argument("--hdbscan", choices=("sklearn", "device"), default="sklearn",
+                    help="where the HDBSCAN fits of --use_dbscan run: sklearn on the CPU (the reference) or the GPU "
+                         "(DeviceHDBSCAN: clift_emst + the host tree pass, pinned to sklearn's estimator)")
     ap.add_argument("--sweep", type=float, nargs=3, metavar=("START", "STOP", "STEP"), help="values np.arange(START, STOP, STEP) instead of the reference's range")
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="reference hard-codes [256, 384] (:390)")
     ap.add_argument("--things_csv", default="resources/scannet_reduced_things.csv", help="name,is_thing rows (non-MOS scenes)")
@@ -172,5 +177,5 @@ if __name__ == "__main__":
     cfg.image_dim = list(args.image_dim)
     t0 = time.time()
     find_bandwidth(cfg, args.debug, segmentwise=args.segmentwise, use_dbscan=args.use_dbscan, meanshift=args.meanshift, sweep=args.sweep,
-                   things_csv=args.things_csv)
+                   things_csv=args.things_csv, hdbscan=args.hdbscan)
     print("Total time for finding bandwidth: ", time.time() - t0)

@@ -113,7 +113,7 @@ def scene_frames(scene, trajectory_name, test_only):
 
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
                               cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
-                              meanshift="sklearn", save_pointcloud=False):
+                              meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn"):
     out = output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise)
     out.mkdir(exist_ok=True, parents=True)
     device, rank = distributed_device(device)
@@ -152,10 +152,10 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
     else:
         if not segmentwise:
             insts, _ = inf.cluster(all_thing, bandwidth, device, num_images=len(rgbs), use_silverman=use_silverman, use_dbscan=use_dbscan,
-                                   cluster_size=cluster_size, meanshift=meanshift)
+                                   cluster_size=cluster_size, meanshift=meanshift, hdbscan=hdbscan)
         else:
             insts, _ = inf.cluster_segmentwise(all_thing, sems, bandwidth, device, num_images=len(rgbs), use_silverman=use_silverman,
-                                               use_dbscan=use_dbscan, cluster_size=cluster_size, meanshift=meanshift)
+                                               use_dbscan=use_dbscan, cluster_size=cluster_size, meanshift=meanshift, hdbscan=hdbscan)
     for d in ("vis_semantics_and_surrogate", "pred_semantics", "pred_surrogateid"):
         (out / d).mkdir(exist_ok=True)
     for j, frame_name in enumerate(names):
@@ -196,6 +196,9 @@ if __name__ == "__main__":
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="reference hard-codes [256, 384] (RP:450)")
     ap.add_argument("--meanshift", choices=("sklearn", "device"), default="sklearn",
                     help="where the MeanShift fits run: sklearn on the CPU (the reference) or the GPU (DeviceMeanShift)")
+    ap.add_argument("--hdbscan", choices=("sklearn", "device"), default="sklearn",
+                    help="where the HDBSCAN fits of --use_dbscan run: sklearn on the CPU (the reference) or the GPU "
+                         "(DeviceHDBSCAN: clift_emst + the host tree pass, pinned to sklearn's estimator)")
     ap.add_argument("--save_pointcloud", action="store_true",
                     help="also write pointcloud.pkl (points, instances, semantics, rgb of every rendered pixel) for inference/fit_bboxes.py")
     args = ap.parse_args()
@@ -206,5 +209,5 @@ if __name__ == "__main__":
     print(render_panopli_checkpoint(cfg, "trajectory_blender", test_only=not args.render_trajectory, bandwidth=args.bandwidth,
                                     use_dbscan=args.use_dbscan, segmentwise=args.segmentwise,
                                     cached_centroids_path=args.cached_centroids_path, use_silverman=args.use_silverman,
-                                    cluster_size=args.cluster_size, meanshift=args.meanshift,
+                                    cluster_size=args.cluster_size, meanshift=args.meanshift, hdbscan=args.hdbscan,
                                     save_pointcloud=args.save_pointcloud))
