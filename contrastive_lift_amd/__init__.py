@@ -11,6 +11,6 @@ from ._lib import CliftError, build, load  # noqa: F401
 from .field import TensorVMSplit  # noqa: F401
 from .renderer import TensoRFRenderer  # noqa: F401
 from .loss import (TVLoss, SCELoss, SoftTargetCrossEntropy, get_semantic_weights, contrastive_loss, slow_fast_loss,  # noqa: F401
-                   ema_update)
+                   ema_update, linear_assignment_loss, create_virtual_gt_with_linear_assignment, linear_sum_assignment_device)
 from .rays import (create_grid, get_ray_directions_with_intrinsics, get_rays, rays_intersect_sphere,  # noqa: F401
                    generate_ray_table)

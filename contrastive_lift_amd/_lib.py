@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIFT_LIB_PATH") or os.path.join(_HERE, "libclift.so")      # (the override: timing probes of variant builds, tools/jobs)
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
@@ -140,6 +140,9 @@ _SIGNATURES = {
     "clift_meanshift": ([_P, _L, _I, _I, _P, _I, _D, _I, _P, _P, _P, _P], C.c_int),
     "clift_emst_work_bytes": ([_L], C.c_long),
     "clift_emst": ([_P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P], C.c_int),
+    "clift_lsap": ([_P, _I, _L, _I, _I, _I, _P, _P, _P], C.c_int),
+    "clift_assign_work_bytes": ([_L, _I], C.c_long),
+    "clift_assign_loss": ([_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P], C.c_int),
     "clift_knn_kth_dist": ([_P, _L, _P, _I, _I, _P, _P], C.c_int),
     "clift_segment_moments": ([_P, _L, _P, _I, _P, _P, _P, _P], C.c_int),
     "clift_segment_extent": ([_P, _L, _P, _I, _P, _P, _P, _P], C.c_int),

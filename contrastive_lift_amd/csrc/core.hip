@@ -22,7 +22,7 @@ int clift_check_launch(const char* what) {
     return 0;
 }
 
-extern "C" int clift_version(void) { return 26; }
+extern "C" int clift_version(void) { return 27; }
 
 // Kernel switches (clift.h, CLIFT_SWITCH_*): one word of host state, seeded from the environment on first use -- the library's only read of
 // the environment -- and changed at run time through clift_set_switches.  Kernel files read it through clift_switch_off (clift_dev.h).

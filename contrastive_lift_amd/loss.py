@@ -56,12 +56,94 @@ def slow_fast_loss(instance_features, labels_gt, confidences, return_grad=False)
     return _Scaled.apply(instance_features, loss[0], grad)
 
 
+_ASSIGN_BACKENDS = ("host", "device")
+LSAP_MAX_E = 512          # CLIFT_LSAP_MAX_E of include/clift.h
+
+
+def _check_backend(backend):
+    if backend not in _ASSIGN_BACKENDS:
+        raise ValueError(f"backend must be one of {_ASSIGN_BACKENDS}, got {backend!r}")
+
+
+def _require_device(t, what):
+    """The device backends have no fallback: without a GPU tensor or the library they raise."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise _lib.CliftError(f"{what}: backend='device' needs CUDA tensors (got {getattr(t, 'device', type(t))}); there is no host fallback")
+    _lib.load()
+
+
 @torch.no_grad()
-def create_virtual_gt_with_linear_assignment(labels_gt, predicted_scores):
+def linear_sum_assignment_device(cost):
+    """scipy.optimize.linear_sum_assignment for fp32 matrices on the device (clift_lsap: shortest augmenting paths in fp64, one wave per
+    matrix).  ``cost``: (L, E) or (B, L, E) CUDA float32 with L <= E <= 512 (any row stride, unit column stride); NaN counts as 0, +-inf as
+    +-FLT_MAX (np.nan_to_num).  Returns (col_of_row int32 (..., L), total float64 (...)): row r is matched to column col_of_row[r], total is the
+    optimum summed in row order.  Nothing is read back."""
+    _require_device(cost, "linear_sum_assignment_device")
+    c = _lib.f32(cost, "cost")
+    if c.dim() not in (2, 3):
+        raise ValueError(f"cost must be (L, E) or (B, L, E), got {tuple(c.shape)}")
+    batched = c.dim() == 3
+    c3 = c if batched else c.unsqueeze(0)
+    B, L, E = c3.shape
+    if L > E:
+        raise _lib.CliftError(f"linear_sum_assignment_device: L = {L} rows > E = {E} columns (transpose the problem)")
+    if E > LSAP_MAX_E:
+        raise _lib.CliftError(f"linear_sum_assignment_device: E = {E} exceeds the limit of {LSAP_MAX_E} columns")
+    if B > 0 and L > 0 and (c3.stride(2) != 1 or c3.stride(1) < E or (B > 1 and c3.stride(0) < 0)):
+        c3 = c3.contiguous()
+    col = torch.empty((B, L), dtype=torch.int32, device=c.device)
+    total = torch.zeros((B,), dtype=torch.float64, device=c.device)
+    if B > 0 and L > 0:
+        _lib.call("clift_lsap", _lib.ptr(c3), c3.stride(1), c3.stride(0) if B > 1 else 0, B, L, E, _lib.ptr(col), _lib.ptr(total), _lib.stream())
+    return (col, total) if batched else (col[0], total[0])
+
+
+def _assign_loss_device(scores, labels, conf, want_grad, want_cost=False, out_active=None):
+    """One clift_assign_loss call: ids, matching, virtual labels, active flag, loss and gradient of one image, all left on the device."""
+    _require_device(scores, "linear_assignment_loss")
+    f = _lib.f32(scores, "instance_features")
+    if f.dim() != 2:
+        raise ValueError(f"instance scores must be (n, E), got {tuple(f.shape)}")
+    n, E = f.shape
+    if E > LSAP_MAX_E or E < 2:
+        raise _lib.CliftError(f"linear assignment on the device: E = {E} slots outside the supported range [2, {LSAP_MAX_E}] "
+                              "(use backend='host')")
+    if n < 1 or n > (1 << 20):
+        raise _lib.CliftError(f"linear assignment on the device: n = {n} rays outside [1, 2^20]")
+    if f.stride(1) != 1 or f.stride(0) < E:
+        f = f.contiguous()
+    dev = f.device
+    y = labels.to(device=dev, dtype=torch.int32).contiguous()
+    cf = None if conf is None else _lib.f32(conf.to(dev), "confidences").contiguous()
+    ints = torch.empty((2 * E + 2 + n,), dtype=torch.int32, device=dev)          # ids | slot_of_id | n_ids | active | target
+    ids, slot_of_id, n_ids, active, target = ints[:E], ints[E:2 * E], ints[2 * E:2 * E + 1], ints[2 * E + 1:2 * E + 2], ints[2 * E + 2:]
+    if out_active is not None:
+        active = out_active
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    grad = torch.empty((n, E), dtype=torch.float32, device=dev) if want_grad else None
+    cost = torch.zeros((E, E), dtype=torch.float32, device=dev) if want_cost else None
+    nbytes = int(_lib.load().clift_assign_work_bytes(n, E))
+    work = torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    _lib.call("clift_assign_loss", _lib.ptr(f), f.stride(0), _lib.ptr(y), _lib.ptr(cf), n, E, _lib.ptr(ids), _lib.ptr(n_ids), _lib.ptr(cost),
+              _lib.ptr(slot_of_id), _lib.ptr(target), _lib.ptr(loss), _lib.ptr(grad), E, _lib.ptr(active), _lib.ptr(work), nbytes, _lib.stream())
+    return dict(ids=ids, n_ids=n_ids, slot_of_id=slot_of_id, target=target, active=active, loss=loss, grad=grad, cost=cost)
+
+
+@torch.no_grad()
+def create_virtual_gt_with_linear_assignment(labels_gt, predicted_scores, backend="host"):
     """T:332-344: match the (sorted, first E) 2-D instance ids of an image to the E output slots: cost[id][slot] = -(sum of the slot's softmax
-    probability over the id's rays / (count + 1e-4)), Hungarian method on the HOST like the reference (scipy; an L x E matrix, L <= E), every
-    ray of a matched id gets that slot as its class, every other ray class 0.  The per-id sums are one one-hot product on the device; what crosses
-    the bus is the L x E cost matrix."""
+    probability over the id's rays / (count + 1e-4)), Hungarian method, every ray of a matched id gets that slot as its class, every other ray
+    class 0.
+
+    ``backend="host"`` (default): the Hungarian method on the HOST like the reference (scipy; an L x E matrix, L <= E).  The per-id sums are one
+    one-hot product on the device; what crosses the bus is the L x E cost matrix.
+    ``backend="device"``: one clift_assign_loss call (csrc/assign.hip), nothing leaves the device; 2 <= E <= 512, labels are taken as int32;
+    returns the virtual labels in the labels' dtype.  No fallback: without a GPU or the library, or outside the limits, CliftError.
+    The two differ for NaN scores: the device path sums over the id's rays only (a masked sum, as the reference does), the host path's one-hot
+    product spreads a NaN row to every id."""
+    _check_backend(backend)
+    if backend == "device":
+        return _assign_loss_device(predicted_scores.detach(), labels_gt, None, want_grad=False)["target"].to(labels_gt.dtype)
     import numpy as np
     import scipy.optimize
     E = predicted_scores.shape[-1]
@@ -70,8 +152,10 @@ def create_virtual_gt_with_linear_assignment(labels_gt, predicted_scores):
     slot_of = torch.searchsorted(ids, labels_gt.contiguous())
     slot_of = torch.where((slot_of < ids.numel()) & (ids[slot_of.clamp_max(ids.numel() - 1)] == labels_gt), slot_of, torch.full_like(slot_of, ids.numel()))
     # per-id sums as a float64 one-hot product: a fixed summation order (an index_add_ is a race of atomics on the device, and a near-tie in
-    # the cost matrix could flip the assignment from run to run).  This mode synchronises with the host (the .cpu() below, like the
-    # reference's own scipy call): ``nosync`` steps do not apply to it.
+    # the cost matrix could flip the assignment from run to run).  This backend synchronises with the host three times per image (the unique
+    # above, the .cpu() below like the reference's own scipy call, the caller's "any label off its slot" test).  backend="device" has none of
+    # them; a pass of the trainer then still reads one flag back at its end, because clift_adam takes its step count from the host and an
+    # image set that contributed nothing must not count as a step.
     member = torch.zeros((ids.numel() + 1, slot_of.numel()), dtype=torch.float64, device=prob.device).scatter_(0, slot_of.reshape(1, -1), 1.0)
     sums, cnt = (member @ prob.to(torch.float64)).to(torch.float32), member.sum(1).to(torch.float32)
     cost = (-(sums[:-1] / (cnt[:-1, None] + 1e-4))).cpu().numpy().astype(np.float64)
@@ -81,11 +165,21 @@ def create_virtual_gt_with_linear_assignment(labels_gt, predicted_scores):
     return table.to(labels_gt.device)[slot_of]
 
 
-def linear_assignment_loss(instance_features, labels_gt, confidences, return_grad=False):
+def linear_assignment_loss(instance_features, labels_gt, confidences, return_grad=False, backend="host", out_active=None):
     """The "linear_assignment" branch of calculate_instance_clustering_loss (T:237-241; the template's default instance_loss_mode, the
     Panoptic-Lifting baseline): mean over rays of CrossEntropyLoss(reduction='none')(scores, matched slot) * confidence -- unless every ray's
     argmax already is its slot: then the term is the constant 0 and NO gradient flows ("should never reinforce correct labels").
-    Returns (loss, grad or None) with ``return_grad``; grad None means the inactive case."""
+
+    ``backend="host"``: returns (loss, grad or None) with ``return_grad``; grad None means the inactive case (decided on the host).
+    ``backend="device"``: one clift_assign_loss call and no read-back; with ``return_grad`` returns (loss, grad, active) -- loss a 0-dim and
+    active a 1-element int32 device tensor, grad never None: all zeros in the inactive case.  ``out_active``: a 1-element int32 device tensor
+    to receive the flag (a slot of the caller's per-pass flag array).  2 <= E <= 512; no fallback (CliftError)."""
+    _check_backend(backend)
+    if backend == "device":
+        out = _assign_loss_device(instance_features.detach(), labels_gt, confidences, want_grad=True, out_active=out_active)
+        if return_grad:
+            return out["loss"][0], out["grad"], out["active"]
+        return _Scaled.apply(instance_features, out["loss"][0], out["grad"])
     f = _lib.f32(instance_features, "instance_features").contiguous()
     n, E = f.shape
     y = labels_gt.to(f.device)

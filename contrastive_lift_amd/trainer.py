@@ -37,6 +37,8 @@ def default_config(**over):
                                                      # computes and discards them (T:155) -- same results, ~12 % less work; the train CLI sets it
              host_rng=False,       # extension key: draw the per-ray jitter from torch's CPU generator like the reference's renderer (R:808-810) instead of the
                                    # device generator; the train CLI sets it (the drop-in's random sources are the reference's), the benchmark does not
+             assignment_backend="host",      # extension key: where instance_loss_mode "linear_assignment" matches ids to slots -- "host" (scipy, like the
+                                             # reference: three synchronisations per image) or "device" (clift_assign_loss: one flag read per pass)
              grad_shards=True)     # extension key: MLP gradients accumulate in eight per-XCD copies, folded once per pass (include/clift.h, ABI 12)
     c.update(over)
     return types.SimpleNamespace(**c)
@@ -167,6 +169,9 @@ class HotPathTrainer:
         if unsupported:
             raise NotImplementedError("HotPathTrainer: config options outside the contrastive-lift hot path: " +
                                       ", ".join(f"{k}={getattr(config, k)!r} (only {v!r} is built)" for k, v in unsupported))
+        self.assignment_backend = getattr(config, "assignment_backend", "host")
+        if self.assignment_backend not in ("host", "device"):
+            raise ValueError(f"HotPathTrainer: assignment_backend must be 'host' or 'device', got {self.assignment_backend!r}")
         self.white_bg = bool(white_bg)            # dataset attribute in the reference (train_set.white_bg, T:109)
         engine.set_mlp_precision(getattr(config, "mlp_dtype", None) or engine.DEFAULT_MLP_DTYPE)    # process-wide switch of the matrix-core launches
         self.device = model.param_flat.device
@@ -613,7 +618,9 @@ class HotPathTrainer:
         self._pass_begin(self.inst_range)
         gv = m.named_grad_views()
         contributed = False
-        for img in inst_batch:
+        device_assign = c.instance_loss_mode == "linear_assignment" and self.assignment_backend == "device"
+        flags = torch.zeros((len(inst_batch),), dtype=torch.int32, device=self.device) if device_assign else None
+        for k, img in enumerate(inst_batch):
             rays = img["rays"]
             n = rays.shape[0]
             jit = jitter
@@ -633,6 +640,11 @@ class HotPathTrainer:
                 assert f1 - f0 == s1 - s0, "arena groups inst_fast / inst_slow must have the same layout"
                 _lib.call("clift_ema", _lib.ptr(m.param_flat[s0:s1]), _lib.ptr(m.param_flat[f0:f1]), f1 - f0, 0.9, _lib.stream())
                 loss, g_inst = slow_fast_loss(inst, img["instances"], img["confidences"], return_grad=True)
+            elif device_assign:
+                # T:237-241 in one library call per image, nothing read back: an image whose rays all sit on their slot already yields loss 0 and
+                # an all-zero gradient, and its backward below adds exact zeros.  Its flag is read with the others' after the loop
+                loss, g_inst, _ = linear_assignment_loss(inst, img["instances"], img["confidences"], return_grad=True, backend="device",
+                                                         out_active=flags[k:k + 1])
             elif c.instance_loss_mode == "linear_assignment":
                 # T:237-241: Hungarian-matched slots (host, like the reference), confidence-weighted cross entropy on the device.  An image
                 # whose rays all sit on their slot already contributes the constant 0: no backward for it
@@ -657,8 +669,11 @@ class HotPathTrainer:
         self._pass_fold("inst_fast")
         if c.instance_loss_mode == "linear_assignment":
             # reference: when the loss is the constant 0 every .grad stays None and torch's Adam skips every parameter, step counts and weight
-            # decay included.  In a data-parallel run that holds only if NO rank contributed: one flag is summed over the ranks (this mode
-            # synchronises with the host anyway, loss.create_virtual_gt_with_linear_assignment)
+            # decay included.  In a data-parallel run that holds only if NO rank contributed: one flag is summed over the ranks (the host
+            # backend synchronises with the host anyway, loss.create_virtual_gt_with_linear_assignment; the device backend's one read-back
+            # of the pass is the line below: clift_adam takes its step count from the host)
+            if device_assign:
+                contributed = bool(flags.any().item()) if len(inst_batch) else False
             if self.world > 1:
                 flag = torch.tensor([1.0 if contributed else 0.0], device=self.device if dist.get_backend() == "nccl" else "cpu")
                 dist.all_reduce(flag, op=dist.ReduceOp.SUM)

@@ -598,6 +598,40 @@ long clift_emst_work_bytes(long n);      /* CLIFT_EMST_WORK_BYTES(n) for callers
 int clift_emst(const float* X, long n, int ldx, int d, int* edge_a, int* edge_b, double* edge_w, int* info, void* work, long work_bytes,
                clift_stream_t s);
 
+/* ---- linear assignment (ABI 27; csrc/assign.hip): the Hungarian step of the reference's "linear_assignment" instance loss
+ * (trainer/train_panopli_tensorf.py:237-242, 332-342; scipy.optimize.linear_sum_assignment on the host there) and that loss for one image.
+ *
+ * clift_lsap solves nb independent rectangular problems: minimise sum_r cost[r][col_of_row[r]] over assignments with distinct columns.  cost: fp32,
+ * row-major L x E with leading dimension ld >= E, problem b at cost + b * batch_stride (floats; any value >= 0, 0 = the same matrix nb times).
+ * 0 <= L <= E <= CLIFT_LSAP_MAX_E.  col_of_row (nb, L) int32; total (nb) fp64, nullable: the optimum, summed in row order in fp64.  An entry
+ * counts as np.nan_to_num makes it: NaN = 0, +-inf = +-FLT_MAX.  Shortest augmenting paths (Jonker-Volgenant, scipy's method), duals, path lengths
+ * and the running minimum in fp64: scipy's assignment whenever the optimum is unique.  Ties between columns: a column without a row first, then
+ * the lowest index.  One wave per problem, one workgroup each; the matrix is staged in LDS when L * E * 4 <= 144 KiB, else read through L2.
+ * Errors: a negative size, L > E, E > CLIFT_LSAP_MAX_E, ld < E, batch_stride < 0, a NULL cost / col_of_row.  nb == 0 or L == 0 returns 0 at once.
+ *
+ * clift_assign_loss: one image of the loss.  scores (n, ld) fp32, labels (n) int32 (any values; id 0 is an id like every other), conf (n) fp32
+ * (NULL = all 1).  In this order:
+ *   1. ids (E) = the distinct labels, ascending, the first E of them; n_ids (1) = L <= E; ids[L..E) = 0;
+ *   2. p_i = softmax(scores_i) in fp32; S[l][e] = sum of p_i[e] over the rays with labels_i == ids[l] (a masked sum: other rays are not read),
+ *      fp64, in ray order; cost[l][e] = -(float(S[l][e]) / (float(count_l) + 1e-4f)).  cost (E, E) fp32, rows [0, L) written, nullable;
+ *   3. slot_of_id (E) = the clift_lsap solution of that L x E matrix (the same device code); slot_of_id[L..E) = 0;
+ *   4. target_i (n) = slot_of_id[l] where labels_i == ids[l], l < L, else 0;
+ *   5. active (1) = 1 if any target_i != argmax_e scores_i[e] (lowest index among maxima), else 0;
+ *   6. active: loss (1) = (1/n) sum_i conf_i CE(scores_i, target_i), the rows added in a fixed order; grad (n, ldg; nullable) =
+ *      (conf_i / n)(softmax(scores_i) - onehot(target_i)); the per-ray arithmetic is clift_semantic_loss_rows';
+ *   7. not active: loss = 0 and grad is WRITTEN as zeros ("should never reinforce correct labels": the term is a constant).
+ * No floating-point atomic anywhere: two calls on one input give the same bits in every output.  n <= 8192 sorts the labels in LDS; a larger n
+ * extracts one id per pass over the labels (slow, exact).  2 <= E <= CLIFT_LSAP_MAX_E, 1 <= n <= CLIFT_ASSIGN_MAX_N.  work: a device buffer of at
+ * least CLIFT_ASSIGN_WORK_BYTES(n, E) bytes, 16-byte aligned, contents irrelevant before and undefined after.  Seven launches on the stream, no
+ * synchronisation, no allocation.  Errors: sizes out of range, ld < E, ldg < E with a grad, a NULL required buffer, work misaligned or too small. */
+#define CLIFT_LSAP_MAX_E 512
+#define CLIFT_ASSIGN_MAX_N 1048576
+#define CLIFT_ASSIGN_WORK_BYTES(n, E) (256L + 16L * ((long)(n) + 4) + 4L * (long)(E) * (long)(E))
+int clift_lsap(const float* cost, int ld, long batch_stride, int nb, int L, int E, int* col_of_row, double* total, clift_stream_t s);
+long clift_assign_work_bytes(long n, int E);      /* CLIFT_ASSIGN_WORK_BYTES(n, E) for callers that cannot see the macro */
+int clift_assign_loss(const float* scores, int ld, const int* labels, const float* conf, int n, int E, int* ids, int* n_ids, float* cost,
+                      int* slot_of_id, int* target, float* loss, float* grad, int ldg, int* active, void* work, long work_bytes, clift_stream_t s);
+
 /* ---- instances in 3-D (ABI 20; csrc/points3d.hip): the per-instance steps of the reference's inference/visualize_bboxes.py (filter_pointcloud
  * :52-74, get_tight_bbox :78-131) for ALL instances of a scene per launch.  pts (n, 3) fp32, rows SORTED BY INSTANCE; seg (G + 1) int64 device
  * offsets, non-decreasing, 0 <= seg[g] <= n: instance g owns rows seg[g] .. seg[g+1] (may be empty).  n < 2^31 - 1024.  Entries of seg outside
