@@ -112,13 +112,12 @@ def _one_hot(all_labels, num_images, device):
 
 
 @torch.no_grad()
-def assign_clusters(all_thing_features, all_points_semantics, all_centroids, device, num_images):
-    """RP:371-419: per thing class, nearest cached centroid (clift_nearest_centroid on the device); stuff pixels get
-    label -1; labels of successive classes are offset so they stay disjoint; returns one-hot (num_images, P, K+1)."""
-    feats = torch.as_tensor(all_thing_features, dtype=torch.float32, device=device)
-    sem = torch.cat([s.to(device) for s in all_points_semantics], 0).argmax(-1)
-    thing = feats[:, 0] == -float("inf")
-    f = feats[:, 1:].contiguous()
+def assign_cluster_labels(features, sem, thing, all_centroids):
+    """The labelling of RP:371-419 on device rows: features (P, E) fp32, sem (P) class ids, thing (P) bool.  Per thing class present, in
+    ascending order, the nearest cached centroid (clift_nearest_centroid); labels of successive classes are offset so they stay
+    disjoint; rows that are not things get -1.  -> (P) int64.  ``label + 1`` is the id written to pred_surrogateid (0 = stuff)."""
+    device = features.device
+    f = features.contiguous()
     labels = torch.full((f.shape[0],), -1, dtype=torch.int64, device=device)
     max_label = 0
     for cls in torch.unique(sem[thing]).tolist():
@@ -131,6 +130,16 @@ def assign_clusters(all_thing_features, all_points_semantics, all_centroids, dev
         labels[sel] = lab[sel].long() + max_label
         if bool(sel.any()):
             max_label = int(labels[sel].max()) + 1
+    return labels
+
+
+@torch.no_grad()
+def assign_clusters(all_thing_features, all_points_semantics, all_centroids, device, num_images):
+    """RP:371-419: per thing class, nearest cached centroid (clift_nearest_centroid on the device); stuff pixels get
+    label -1; labels of successive classes are offset so they stay disjoint; returns one-hot (num_images, P, K+1)."""
+    feats = torch.as_tensor(all_thing_features, dtype=torch.float32, device=device)
+    sem = torch.cat([s.to(device) for s in all_points_semantics], 0).argmax(-1)
+    labels = assign_cluster_labels(feats[:, 1:], sem, feats[:, 0] == -float("inf"), all_centroids)
     return _one_hot(labels, num_images, device)
 
 

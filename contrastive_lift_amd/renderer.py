@@ -221,6 +221,61 @@ class TensoRFRenderer(nn.Module):
         alpha = self.compute_alpha(tensorf, dense_xyz.reshape(-1, 3), self.step_size.to(dev)).view(g[0], g[1], g[2])
         return alpha, dense_xyz
 
+    # ------------------------------------------------------------------ the scene as a volume (renderer.py:636-666, 731-748)
+    def lattice_ticks(self, shape):
+        """World coordinates per axis of an (n0, n1, n2) lattice of the current box: lo_a (1 - s) + hi_a s with s = linspace(0, 1, n_a),
+        the two-product blend of R:725 / R:746 -- where ``get_dense_sigma`` evaluated the field."""
+        dev = self.bbox_aabb.device
+        s = [torch.linspace(0, 1, int(n)).to(dev) for n in shape]
+        return [self.bbox_aabb[0][a] * (1 - s[a]) + self.bbox_aabb[1][a] * s[a] for a in range(3)]
+
+    @torch.no_grad()
+    def get_dense_sigma(self, tensorf, upsample=1):
+        """sigma = softplus(density + shift) on the (g0 u, g1 u, g2 u) lattice of the current box (renderer.py:731-748), on the device:
+        one clift_dense_sigma launch, no materialised meshgrid and no loop over x-slabs."""
+        import ctypes as C
+        from . import _lib
+        upsample = int(upsample)
+        if upsample < 1:
+            raise ValueError(f"upsample must be >= 1 (got {upsample})")
+        dev = self.bbox_aabb.device
+        n = [int(x) * upsample for x in self.grid_dim.tolist()]
+        ticks = [torch.linspace(0, 1, k).to(dev) for k in n]
+        views = tensorf.named_views()
+        vd = engine.vm_struct(views, "density", engine.grid_res(views))
+        lo, hi = self.bbox_aabb_host
+        f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+        sigma = torch.empty((n[0], n[1], n[2]), dtype=torch.float32, device=dev)
+        _lib.call("clift_dense_sigma", C.byref(vd), f3(lo), f3(hi), f3(self.inv_box_extent_host), _lib.ptr(ticks[0]), _lib.ptr(ticks[1]),
+                  _lib.ptr(ticks[2]), n[0], n[1], n[2], float(tensorf.splus_density_shift), _lib.ptr(sigma), _lib.stream())
+        return sigma
+
+    @torch.no_grad()
+    def get_instance_clusters(self, tensorf, mode):
+        """renderer.py:636-666: the lattice voxels with their instance label = argmax over the columns ``render_instance_mlp`` returns.
+        ``mode`` 'alpha': the voxels whose (clamped) alpha reaches ``alpha_mask_threshold``, at most 2**18 of them; 'full': every voxel, at
+        most 2**16.  Voxels are listed z-major (the reference's ``transpose(0, 2)``) and drawn with Python's ``random.sample``, so
+        ``random.seed`` reproduces the reference's draw.  The instance head runs on the drawn voxels only.
+        -> (xyz (n, 3) world positions, labels (n) int32), on the device."""
+        import random
+        if mode not in ("alpha", "full"):
+            raise ValueError(f"mode must be 'alpha' or 'full' (got {mode!r})")
+        alpha, dense_xyz = self.get_dense_alpha(tensorf)
+        xyz = dense_xyz.transpose(0, 2).contiguous().view(-1, 3)
+        if mode == "full":
+            cap = 2 ** 16
+        else:
+            cap = 2 ** 18
+            keep = alpha.clamp(0, 1).transpose(0, 2).contiguous().view(-1) >= self.alpha_mask_threshold
+            xyz = xyz[keep]
+        n = xyz.shape[0]
+        picked = torch.tensor(random.sample(range(n), min(cap, n)), dtype=torch.int64, device=xyz.device)
+        xyz = xyz[picked]                        # the draw does not depend on the labels: the head runs on what survives it
+        if xyz.shape[0] == 0:
+            return xyz, torch.zeros(0, dtype=torch.int32, device=xyz.device)
+        labels = tensorf.render_instance_mlp(None, tensorf.compute_instance_feature(self.normalize_coordinates(xyz).contiguous()))
+        return xyz, labels.argmax(dim=1).int()
+
     @torch.no_grad()
     def occupied_index_box(self, tensorf):
         """Index bounding box of the lattice voxels whose 3^3-max-pooled alpha reaches ``alpha_mask_threshold`` (the first half of

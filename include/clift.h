@@ -694,6 +694,46 @@ int clift_label_overlap(const int* a_cls, const int* a_inst, const int* b_cls, c
                         const int* a_base, const int* a_stride, int Ca, const int* b_base, const int* b_stride, int Cb, int NA, int NB,
                         int* counts, int* rejected, clift_stream_t s);
 
+/* ---- the scene as a surface (an ABI 27 addition; csrc/isosurface.hip).
+ *
+ * clift_dense_sigma: out (n0, n1, n2) fp32, x-major = softplus(density + shift) on a lattice of the box: lattice point p_a = lo_a (1 - s) + hi_a s
+ * with s = s_a[i_a] (three device arrays, the caller's torch.linspace(0, 1, n_a)), normalised with inv_ext2 -- the coordinate arithmetic of
+ * clift_alpha_bbox.  With n_a = grid_dim_a * upsample this is the reference's TensoRFRenderer.get_dense_sigma (renderer.py:731-748) in one launch.
+ * Errors: comps not a multiple of 4, a dimension < 1, >= 2^36 lattice points, a NULL buffer.
+ *
+ * Iso-surface of a scalar lattice by MARCHING TETRAHEDRA ON THE KUHN SPLIT.  vol (n0, n1, n2) fp32, x-major: lin(i, j, k) = (i n1 + j) n2 + k.
+ * "Inside" is vol >= level; NaN is outside.  Cell (i, j, k) splits into 6 tetrahedra, one per permutation (a, b, c) of the axes in lexicographic
+ * order: v0 = c000, v1 = v0 + e_a, v2 = v1 + e_b, v3 = c111.  The complex has 7 edge classes per lattice point -- offsets (1,0,0) (0,1,0) (0,0,1)
+ * (1,1,0) (1,0,1) (0,1,1) (1,1,1), in this order; an edge is owned by its lower endpoint and exists when both endpoints are lattice points.  An edge
+ * whose endpoints classify differently carries exactly one vertex, at p = pa + t (pb - pa), t = (level - va) / (vb - va) clamped to [0, 1] (a NaN t
+ * becomes 0), a = the owner, fp32 with one rounding per operation; its INDEX is the rank of the key 7 lin(owner) + class among such edges.  A
+ * tetrahedron with 1 or 3 inside corners gives one triangle; with 2 a quad, split along the diagonal through its smallest vertex index: the cycle
+ * rotated to start there, (q0 q1 q2) then (q0 q2 q3).  The winding comes from a case table and the parity of the permutation, never from computed
+ * positions: the normal points from inside to outside.  Faces are ordered by scan: (cell by lin, tetrahedron, triangle).  The mesh is a closed,
+ * consistently oriented 2-manifold wherever the surface does not meet the lattice boundary.  No atomics: two runs give the same bits.
+ *
+ * Three calls; the caller scans between the first and the others (exclusive prefix sums of n_vert and n_tri over lin, int64, and ONE read of
+ * the two totals V and F, which size verts and faces):
+ *   clift_iso_classify: edge_mask (N) uint8 = the owned active classes of every lattice point (bit = class), n_vert (N) int32 = their number,
+ *     n_tri (N) int32 = the triangles of the cell whose c000 corner the point is (0 where there is no such cell).  N = n0 n1 n2.
+ *   clift_iso_vertices: verts (V, 3) fp32 world positions from the per-axis coordinate arrays x0 (n0), x1 (n1), x2 (n2); normals (V, 3) fp32,
+ *     NULL skips them: minus the central-difference gradient of vol (world units, one-sided at the border) at the two endpoints, interpolated with
+ *     the same t, normalised (0 0 0 where the length is zero or not finite).
+ *   clift_iso_faces: faces (F, 3) int32.
+ * A row outside [0, V) resp. [0, F) -- offsets that do not belong to the mask -- is never written.
+ * Errors, all checked before the device is touched: N, V or F >= CLIFT_ISO_LIMIT = 2^31 (the message names the limit), a negative V or F, a NaN
+ * level, a NULL buffer.  A lattice with a dimension < 2 (n <= 0 included) has no cell: every call returns 0 without a launch; so do
+ * clift_iso_vertices with V == 0 and clift_iso_faces with F == 0 (an all-inside or all-outside lattice). */
+#define CLIFT_ISO_LIMIT 2147483648L
+int clift_dense_sigma(const clift_vm_t* h_dens, const float* h_lo3, const float* h_hi3, const float* h_inv_ext2, const float* s0,
+                      const float* s1, const float* s2, int n0, int n1, int n2, float shift, float* out, clift_stream_t s);
+int clift_iso_classify(const float* vol, int n0, int n1, int n2, float level, unsigned char* edge_mask, int* n_vert, int* n_tri,
+                       clift_stream_t s);
+int clift_iso_vertices(const float* vol, int n0, int n1, int n2, float level, const float* x0, const float* x1, const float* x2,
+                       const unsigned char* edge_mask, const long* vert_off, long V, float* verts, float* normals, clift_stream_t s);
+int clift_iso_faces(const float* vol, int n0, int n1, int n2, float level, const unsigned char* edge_mask, const long* vert_off,
+                    const long* tri_off, long V, long F, int* faces, clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,

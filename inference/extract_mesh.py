@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""Export a trained scene as a labelled surface mesh: every vertex carries colour, semantic class and instance id.
+
+    python inference/extract_mesh.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt [--upsample 2] [--alpha_level 0.5 | --level SIGMA]
+                                     [--cached_centroids_path all_centroids.pkl] [--split_instances] [--save_voxel_cloud]
+
+The checkpoint is loaded exactly as by ``inference/render_panopli.py`` (its ``load_for_inference``).  sigma is evaluated on the
+``upsample``-times refined lattice of the scene box (``TensoRFRenderer.get_dense_sigma``, the reference's renderer.py:731-748, one launch),
+its iso-surface is extracted on the device by marching tetrahedra (``mesh.extract_isosurface``: deterministic, scan ordered, closed and
+consistently oriented wherever the surface stays off the box), and every vertex is labelled by the field's own heads
+(``mesh.label_vertices``): class = argmax of the semantic head, colour = the appearance head seen along minus the normal, instance id =
+the nearest cached centroid of the vertex's class, numbered like ``pred_surrogateid`` (0 = stuff) -- or, without
+``--cached_centroids_path``, 1 + the argmax of the instance head for vertices of thing classes (the reference's per-voxel rule of
+``get_instance_clusters``; meaningful for ``linear_assignment`` models) and 0 for stuff.
+
+Writes ``mesh.ply`` (binary little-endian; x y z nx ny nz red green blue semantic instance, int face lists) into the folder
+``render_panopli.py`` renders to; ``--split_instances`` adds ``mesh_instance_<id>.ply`` per instance id (the faces whose three vertices
+carry that id); ``--save_voxel_cloud`` adds ``voxelcloud.pkl``: the voxels of ``get_instance_clusters(mode='alpha')`` (drawn with seed 0)
+with class and instance id by the same rule as the vertices and a colour from the appearance head at a ZERO view direction (a voxel
+has no normal), in the layout of ``pointcloud.pkl``, so ``inference/fit_bboxes.py --pointcloud`` reads it unchanged -- unlike ``pointcloud.pkl`` it
+holds the whole occupied volume, not only what some test camera saw.  Prints the time of every stage (device events).
+"""
+import argparse
+import math
+import os
+import pickle
+import random
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+import render_panopli as rp                                           # noqa: E402
+from contrastive_lift_amd import mesh as cm                           # noqa: E402
+from contrastive_lift_amd.config import load_run_config               # noqa: E402
+
+
+def default_level(renderer, alpha_level):
+    """The sigma at which ONE sample of a training step would have opacity ``alpha_level``: alpha = 1 - exp(-sigma step distance_scale).
+    ``renderer`` comes from ``load_for_inference``, which halves the step ratio (RP:104): the training step is twice its step."""
+    if not 0.0 < alpha_level < 1.0:
+        raise SystemExit(f"--alpha_level must lie in (0, 1) (got {alpha_level})")
+    train_step = 2.0 * renderer.step_size_host
+    return -math.log(1.0 - alpha_level) / (train_step * float(renderer.distance_scale))
+
+
+class StageTimer:
+    """Device time of consecutive stages (events on the current stream), printed at the end."""
+
+    def __init__(self):
+        self.marks = [("", self._event())]
+
+    @staticmethod
+    def _event():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def done(self, name):
+        self.marks.append((name, self._event()))
+
+    def report(self):
+        torch.cuda.synchronize()
+        times = {name: self.marks[i][1].elapsed_time(e) for i, (name, e) in enumerate(self.marks[1:])}
+        print("stage times (ms): " + ", ".join(f"{k} {v:.3f}" for k, v in times.items()))
+        return times
+
+
+def surrogate_ids(model, renderer, points, normals, thing_classes, centroids, use_delta):
+    """(semantics, instances, rgb) of world points: ``mesh.label_vertices``; without centroids its 0-based head argmax becomes 1 + argmax
+    on thing classes and 0 on stuff, so that 0 means stuff in every file this tool writes."""
+    sem, inst, rgb = cm.label_vertices(model, renderer, points, normals, thing_classes, centroids=centroids, use_delta=use_delta)
+    if centroids is None:
+        thing = torch.isin(sem, torch.tensor(sorted(int(c) for c in thing_classes), dtype=torch.int64, device=sem.device))
+        inst = torch.where(thing, inst + 1, torch.zeros_like(inst))
+    return sem, inst, rgb
+
+
+def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
+                 device="cuda:0"):
+    out = rp.output_dirname(config, "trajectory_blender", True, False, False)
+    out.mkdir(exist_ok=True, parents=True)
+    device = torch.device(device)
+    scene, model, renderer = rp.load_for_inference(config, device)
+    things = list(scene.segmentation_data.fg_classes)
+    centroids = None
+    if cached_centroids_path is not None:
+        with open(cached_centroids_path, "rb") as f:
+            centroids = pickle.load(f)
+    level = default_level(renderer, alpha_level) if level is None else float(level)
+    use_delta = bool(getattr(config, "use_delta", False))
+    timer = StageTimer()
+    sigma = renderer.get_dense_sigma(model, upsample)
+    timer.done("dense_sigma")
+    verts, faces, normals = cm.extract_isosurface(sigma, level, renderer.lattice_ticks(sigma.shape))
+    timer.done("isosurface")
+    sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta)
+    timer.done("label_vertices")
+    times = timer.report()
+    print(f"sigma lattice {tuple(sigma.shape)}, level {level:.6g}: {verts.shape[0]} vertices, {faces.shape[0]} faces, "
+          f"instance ids {sorted(torch.unique(inst).tolist())}")
+    cm.write_ply(out / "mesh.ply", verts, faces, normals, rgb, sem, inst)
+    if split_instances:
+        f_inst = inst[faces.long()]                                   # (F, 3)
+        for i in torch.unique(inst).tolist():
+            sel = faces[(f_inst == i).all(1)].long()
+            if sel.shape[0] == 0:
+                continue
+            used, renum = torch.unique(sel, return_inverse=True)
+            cm.write_ply(out / f"mesh_instance_{int(i)}.ply", verts[used], renum.int(), normals[used], rgb[used], sem[used], inst[used])
+    if save_voxel_cloud:
+        state = random.getstate()                                     # the draw is seeded for a reproducible file; the caller's generator is put back
+        random.seed(0)
+        try:
+            xyz, _ = renderer.get_instance_clusters(model, "alpha")
+        finally:
+            random.setstate(state)
+        v_sem, v_inst, v_rgb = surrogate_ids(model, renderer, xyz, torch.zeros_like(xyz), things, centroids, use_delta)
+        cloud = {"points": xyz.cpu().numpy().astype(np.float32), "instances": v_inst.cpu().numpy().astype(np.uint16),
+                 "semantics": v_sem.cpu().numpy().astype(np.uint8), "rgb": (v_rgb.cpu().numpy().clip(0, 1) * 255).astype(np.uint8)}
+        with open(out / "voxelcloud.pkl", "wb") as f:
+            pickle.dump(cloud, f)
+    return out, times
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Extract a labelled surface mesh (mesh.ply) from a trained checkpoint.")
+    ap.add_argument("--ckpt_path", type=str, required=True)
+    ap.add_argument("--upsample", type=int, default=2, help="sigma lattice = grid x this factor per axis")
+    lv = ap.add_mutually_exclusive_group()
+    lv.add_argument("--alpha_level", type=float, default=0.5,
+                    help="iso level as an opacity: the surface is sigma* = -ln(1 - alpha_level) / (training step size x distance_scale), the sigma "
+                         "at which one training-step sample would have this alpha.  This default is a judgement: nobody has measured it against "
+                         "a real scene -- look at the mesh and set --level if it is too fat or too thin")
+    lv.add_argument("--level", type=float, default=None, help="iso level as a sigma value (overrides --alpha_level)")
+    ap.add_argument("--cached_centroids_path", type=str, required=False,
+                    help="all_centroids.pkl of extract_train_centroids.py: instance id = nearest centroid of the vertex's class, numbered like "
+                         "pred_surrogateid.  Without it: 1 + argmax of the instance head on thing classes, 0 on stuff")
+    ap.add_argument("--split_instances", action="store_true", help="also write mesh_instance_<id>.ply per instance id")
+    ap.add_argument("--save_voxel_cloud", action="store_true",
+                    help="also write voxelcloud.pkl (the occupied voxels, class and id as for the vertices, rgb at a zero view direction, in "
+                         "pointcloud.pkl's layout) for inference/fit_bboxes.py")
+    ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="as render_panopli.py (the scene loader wants it)")
+    return ap
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
+    cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
+    cfg.resume = args.ckpt_path
+    cfg.image_dim = list(args.image_dim)
+    print(extract_mesh(cfg, upsample=args.upsample, alpha_level=args.alpha_level, level=args.level,
+                       cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
+                       save_voxel_cloud=args.save_voxel_cloud)[0])
