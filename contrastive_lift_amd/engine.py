@@ -133,7 +133,7 @@ def _app_precision():
     # mode whose results were disturbed by the other process's fp32x6 launches (profiles/r03_x6_notes.txt).  Exact fp32 there.
     if MLP_PRECISION == 1 and APP_BF16 and persistent_ok():
         return _Precision(1)
-    if MLP_PRECISION == 2 and APP_X6 and persistent_ok() and persistent_x6_ok():
+    if MLP_PRECISION == 2 and APP_X6 and persistent_mode_ok():
         return _Precision(2)
     if MLP_PRECISION in (1, 2):
         return _Precision(0)
@@ -176,6 +176,11 @@ def persistent_ok():
 def persistent_x6_ok():
     """Persistent fp32x6 split kernels allowed (the x6-tiled switch is off)."""
     return not _switch_word() & SWITCH_X6_TILED
+
+
+def persistent_mode_ok():
+    """The persistent kernels of the mode that is set are allowed: persistent_ok() and, in fp32x6 mode, persistent_x6_ok()."""
+    return persistent_ok() and (MLP_PRECISION != 2 or persistent_x6_ok())
 
 
 @contextlib.contextmanager
@@ -433,6 +438,19 @@ def out_layer_fwd(M, h, W, b, out, ldo, col_off, act):
     call("clift_out_layer_fwd", ptr(h), h.shape[1], ptr(W), _pitch(W), ptr(b), W.shape[0], M, C.c_void_p(out.data_ptr() + 4 * col_off), ldo, act, stream())
 
 
+def _out_layer(M, h, W, K, b, out, ldo, col_off, out_act):
+    """The narrow output layer of a head over the K columns of h: out[:, col_off:col_off + n_out] = h W^T + b, then the row softmax when
+    ``out_act`` is 2."""
+    if (MLP_PRECISION in (0, 2) and W.shape[0] <= 32 and K == 256 and h.dtype == torch.float32 and h.shape[1] == 256 and out.dtype == torch.float32
+            and _pitch(W) % 4 == 0 and b is not None and persistent_ok()):
+        # the E <= 32 output layer (+ the row softmax) as one stream over the hidden activation
+        out_layer_fwd(M, h, W, b, out, ldo, col_off, out_act)
+        return
+    gemm(M, W.shape[0], K, h, h.shape[1], W, _pitch(W), out, ldo, bias=b, c_off=col_off)
+    if out_act == 2:
+        _row_softmax_inplace(out, M, W.shape[0], ldo, col_off)
+
+
 class HeadActs(list):
     """The hidden activations an xyz head keeps for its backward (acts[i] = output of layer i, or None where the backward re-derives it), plus
     -- fp32x6 mode -- the sign bytes a persistent forward left for activation i (``signs[i]``, from sign_bits_for): held HERE, next to the tensor
@@ -464,6 +482,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
     W0, b0 = layers[0]
     hdt = act_dtype()                     # bf16 mode stores the hidden activations as bf16 (half the HBM stream of these layers)
     rest = layers[1:-1]
+    out_done = False                      # the output layer has run inside a hidden layer's kernel (logits: a softmax is still to come)
     if (FUSE_HEAD_BF16 and MLP_PRECISION == 1 and hdt == torch.bfloat16 and len(layers) >= 4 and W0.shape[0] == 256
             and tuple(layers[1][0].shape) == (256, 256) and tuple(layers[2][0].shape) == (256, 256) and persistent_ok()):
         # bf16 mode: K = 3 layer + two hidden layers (+ the output layer when it is <= 4 wide and follows directly) in one launch with the
@@ -475,10 +494,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         h3 = mk() if (keep_first or not with_out) else None
         head_bf16(M, xa, layers[0], layers[1], layers[2], (Wo, bo) if with_out else None, h1, h2, h3, out, ldo, col_off)
         acts += [h1, h2, h3]
-        if with_out:
-            if out_act == 2:
-                _row_softmax_inplace(out, M, Wo.shape[0], ldo, col_off)
-            return acts if keep_first else [None]
+        out_done = with_out               # (then layers[3:-1] is empty)
         h = h3
         rest = layers[3:-1]
     elif (MLP_PRECISION == 0 and len(layers) >= 3 and W0.shape[0] == 256 and tuple(layers[1][0].shape) == (256, 256)
@@ -492,8 +508,7 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         acts += [h1, h]
         rest = layers[2:-1]
     elif (MLP_PRECISION == 2 and len(layers) >= 3 and W0.shape[0] == 256 and tuple(layers[1][0].shape) == (256, 256)
-            and (not keep_first or not KEEP_FIRST_ACT) and persistent_ok()
-            and persistent_x6_ok()):
+            and (not keep_first or not KEEP_FIRST_ACT) and persistent_mode_ok()):
         # fp32x6: the same fusion with the 256 x 256 layer on the split kernels; the first activation is never written (the backward, if any,
         # re-derives it: first2_bwd / first2_wgrad)
         W1, b1 = layers[1]
@@ -512,35 +527,28 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
         acts.append(h)
     Wo, bo = layers[-1]
     fuse_out = (MLP_PRECISION in (0, 2) and len(rest) >= 1 and Wo.shape[0] <= 4 and tuple(rest[-1][0].shape) == (256, 256)
-                and h.dtype == torch.float32 and out.dtype == torch.float32 and persistent_ok()
-                and (MLP_PRECISION == 0 or persistent_x6_ok()))
+                and h.dtype == torch.float32 and out.dtype == torch.float32 and persistent_mode_ok())
     for li_, (W, b) in enumerate(rest):
         if fuse_out and li_ == len(rest) - 1:
             # last hidden layer + the narrow output layer in one launch; the hidden activation is written only for a backward
             hn = torch.empty((M, 256), dtype=torch.float32, device=dev) if keep_first else None
             (last2_x6 if MLP_PRECISION == 2 else last2)(M, h, W, b, Wo, bo, hn, out, ldo, col_off)
             acts.append(hn)
-            if out_act == 2:
-                _row_softmax_inplace(out, M, Wo.shape[0], ldo, col_off)
-            return acts if keep_first else [None]
+            out_done = True
+            break
         hn = torch.empty((M, W.shape[0]), dtype=hdt, device=dev)
         # (fp32x6, a backward will run, and this is not the last hidden layer -- whose output the output layer's backward reads as values: sign bytes too)
         sb = (sign_bits_for(M, dev) if (keep_first and MLP_PRECISION == 2 and li_ < len(rest) - 1 and tuple(W.shape) == (256, 256) and h.dtype == torch.float32
-                                        and persistent_x6_ok() and persistent_ok()) else None)
+                                        and persistent_mode_ok()) else None)
         gemm(M, W.shape[0], W.shape[1], h, h.shape[1], W, _pitch(W), hn, hn.shape[1], bias=b, act=1, sign_bits=sb)
         acts.append(hn)
         if sb is not None:
             acts.signs[len(acts) - 1] = sb
         h = hn
-    W, b = Wo, bo
-    if (MLP_PRECISION in (0, 2) and W.shape[0] <= 32 and W.shape[1] == 256 and h.dtype == torch.float32 and h.shape[1] == 256 and out.dtype == torch.float32
-            and _pitch(W) % 4 == 0 and b is not None and persistent_ok()):
-        # the E <= 32 output layer (+ the row softmax) as one stream over the hidden activation
-        out_layer_fwd(M, h, W, b, out, ldo, col_off, out_act)
-        return acts if keep_first else [None]
-    gemm(M, W.shape[0], W.shape[1], h, h.shape[1], W, _pitch(W), out, ldo, bias=b, c_off=col_off)
-    if out_act == 2:
-        _row_softmax_inplace(out, M, W.shape[0], ldo, col_off)
+    if not out_done:
+        _out_layer(M, h, Wo, Wo.shape[1], bo, out, ldo, col_off, out_act)
+    elif out_act == 2:
+        _row_softmax_inplace(out, M, Wo.shape[0], ldo, col_off)
     # no backward through this head: nothing is retained, every hidden activation goes back to the (stream-ordered) allocator as soon
     # as the next layer has been enqueued -- a frame render at 65536 rays per chunk holds ~9 GiB per hidden layer otherwise
     return acts if keep_first else [None]
@@ -584,19 +592,14 @@ def xyz_mlp_bwd(layers, glayers, xa, acts, dpre, M, keep=None):
                  ptr(glayers[0][1]), stream())
             return
         dn = torch.empty((M, ni), dtype=act_dtype(), device=dev)        # bf16 mode: hidden gradients are bf16-stored as well
-        if (li == n - 1 and ni == 256 and no <= 32 and d.shape[1] <= 32 and d.shape[1] % 4 == 0 and M >= 4096 and
-                MLP_PRECISION in (0, 2) and h.dtype == torch.float32 and d.dtype == torch.float32 and dn.dtype == torch.float32):
-            # output layer: weight gradient and masked input gradient in one pass over the hidden activation
-            call("clift_out_layer_bwd", ptr(d), d.shape[1], no, ptr(W), _pitch(W), ptr(h), h.shape[1], M, ptr(dn), ni, ptr(gW), _pitch(gW),
-                 ptr(gb), stream())
-            d = dn
-            keep.append(d)
-            continue
-        if (li == n - 1 and ni == 256 and no <= 32 and d.shape[1] <= 32 and d.shape[1] % 4 == 0 and M >= 4096 and MLP_PRECISION == 1 and OUT_BWD_BF16_FUSED and
-                h.dtype == torch.bfloat16 and d.dtype == torch.float32 and dn.dtype == torch.bfloat16 and h.shape[1] == 256 and _pitch(W) >= 256):
-            # bf16 mode: the same one pass over the (bf16-stored) hidden activation; the input gradient leaves bf16-stored
-            call("clift_out_layer_bwd_nh", ptr(d), d.shape[1], no, ptr(W), _pitch(W), ptr(h), 256, 256, M, ptr(dn), 256, ptr(gW), _pitch(gW),
-                 ptr(gb), 1, stream())
+        nh = MLP_PRECISION == 1
+        if (li == n - 1 and ni == 256 and no <= 32 and d.shape[1] <= 32 and d.shape[1] % 4 == 0 and M >= 4096 and d.dtype == torch.float32 and
+                h.dtype == dn.dtype and (not nh or (OUT_BWD_BF16_FUSED and h.shape[1] == 256 and _pitch(W) >= 256))):
+            # output layer: weight gradient and masked input gradient in one pass over the hidden activation; bf16 mode: the same one pass over
+            # the (bf16-stored) hidden activation -- the _nh entry point, which also takes the layer's width and a bf16 flag -- and the input
+            # gradient leaves bf16-stored
+            call("clift_out_layer_bwd_nh" if nh else "clift_out_layer_bwd", ptr(d), d.shape[1], no, ptr(W), _pitch(W), ptr(h), h.shape[1],
+                 *((ni,) if nh else ()), M, ptr(dn), ni, ptr(gW), _pitch(gW), ptr(gb), *((1,) if nh else ()), stream())
             d = dn
             keep.append(d)
             continue
@@ -632,13 +635,7 @@ def feat_mlp_fwd(layers, X, M, out, ldo, col_off=0, keep=True, out_act=0):
         acts.append(hn)
         h = hn
     Wo, bo = layers[-1]
-    if (Wo.shape[0] <= 32 and h.shape[1] == 256 and _pitch(Wo) % 4 == 0 and _pitch(Wo) >= 256 and MLP_PRECISION in (0, 2)
-            and persistent_ok()):
-        out_layer_fwd(M, h, Wo, bo, out, ldo, col_off, out_act)
-    else:
-        gemm(M, Wo.shape[0], _pitch(Wo), h, h.shape[1], Wo, _pitch(Wo), out, ldo, bias=bo, c_off=col_off)
-        if out_act == 2:
-            _row_softmax_inplace(out, M, Wo.shape[0], ldo, col_off)
+    _out_layer(M, h, Wo, _pitch(Wo), bo, out, ldo, col_off, out_act)       # (K = the row pitch, as in the hidden layers)
     return acts if keep else None
 
 
@@ -773,12 +770,17 @@ def reset_rows_limit(dev=None):
             t[0:1].fill_(INT_MAX)
 
 
-def _density_march(model, renderer, rays, jitter, cap=None):
+def _density_march(model, renderer, rays, jitter, cap=None, density_fwd=None, weight_thres=None):
+    """The march prologue of every pass: densities, weights, the list of the active samples (w > threshold) and the context that holds them.
+    ``density_fwd``: called as density_fwd(ms, vd, sigma) to launch what fills sigma, in place of clift_density_fwd (the edit renders);
+    ``weight_thres``: in place of renderer.raymarch_weight_thres."""
     views = model.named_views()
     N = rays.shape[0]
     S = int(renderer.n_samples)
     dev = rays.device
     ms = march_struct(renderer, model)
+    thres = float(renderer.raymarch_weight_thres if weight_thres is None else weight_thres)
+    ms.weight_thres = thres                 # the march counts, clift_compact_fill lists: the same threshold
     res = grid_res(views)
     vd = vm_struct(views, "density", res)
     sigma = torch.empty((N, S), dtype=torch.float32, device=dev)
@@ -786,7 +788,10 @@ def _density_march(model, renderer, rays, jitter, cap=None):
     ray_out = torch.empty((N, 8), dtype=torch.float32, device=dev)
     n_active = torch.empty((N,), dtype=torch.int32, device=dev)
     st = stream()
-    call("clift_density_fwd", C.byref(ms), C.byref(vd), ptr(rays), ptr(jitter), N, ptr(sigma), st)
+    if density_fwd is None:
+        call("clift_density_fwd", C.byref(ms), C.byref(vd), ptr(rays), ptr(jitter), N, ptr(sigma), st)
+    else:
+        density_fwd(ms, vd, sigma)
     call("clift_march_fwd", C.byref(ms), ptr(rays), ptr(jitter), N, ptr(sigma), ptr(alpha), ptr(T), ptr(w), ptr(ray_out),
          ptr(n_active), st)
     ray_start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
@@ -802,7 +807,7 @@ def _density_march(model, renderer, rays, jitter, cap=None):
         call("clift_scan_counts", ptr(n_active), N, ptr(ray_start), st)
         M = int(ray_start[N].item())        # the one host sync of the chunk: sizes the active-sample buffers
         act_idx = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
-        call("clift_compact_fill", ptr(w), ptr(ray_start), N, S, float(renderer.raymarch_weight_thres), ptr(act_idx), st)
+        call("clift_compact_fill", ptr(w), ptr(ray_start), N, S, thres, ptr(act_idx), st)
     else:
         # sync-free: buffers and grids are sized by the capacity, the true count stays on the device (rows_limit()[0]) where every
         # per-sample kernel clamps to it; an overflow (count > cap: samples dropped) is recorded in rows_limit()[1] for the caller
@@ -812,7 +817,7 @@ def _density_march(model, renderer, rays, jitter, cap=None):
         M = max(int(cap), 1)
         call("clift_scan_counts_capped", ptr(n_active), N, ptr(ray_start), M, ptr(lim), C.c_void_p(lim.data_ptr() + 4), st)
         act_idx = torch.empty((M,), dtype=torch.int32, device=dev)
-        call("clift_compact_fill_capped", ptr(w), ptr(ray_start), N, S, float(renderer.raymarch_weight_thres), ptr(act_idx), M, st)
+        call("clift_compact_fill_capped", ptr(w), ptr(ray_start), N, S, thres, ptr(act_idx), M, st)
     ctx = RenderCtx()
     ctx.ms, ctx.res, ctx.N, ctx.S, ctx.M = ms, res, N, S, M
     ctx.capped = cap is not None
@@ -900,6 +905,73 @@ def _composite_fwd(ctx, w, out, colour=True, feats=True):
          softmax_mode, white_bg, c(rgb_raw), c(rgb_map), f(sem_raw), f(sem_map), f(inst_map), stream())
 
 
+def _composite_outputs(ctx, argmax, want_rgb=True, want_sem=True):
+    """The per-ray outputs of a pass -- colours (``want_rgb``), semantics (``want_sem``), instance features (ctx.D > 0) -- and the compositing
+    launch(es) that fill them (``argmax``: semantic_weight_mode "argmax").  Leaves the raw sums in the context; returns (rgb, sem, inst) maps."""
+    N, M, Ccls, D, dev = ctx.N, ctx.M, ctx.C, ctx.D, ctx.rays.device
+    # (the sum kernel writes every (ray, channel) when there are heads to sum; only a chunk without active samples needs the zeros)
+    fresh = torch.empty if M > 0 else torch.zeros
+    rgb_raw = fresh((N, 3), dtype=torch.float32, device=dev) if want_rgb else None
+    rgb_map = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_rgb else None
+    sem_raw = fresh((N, Ccls), dtype=torch.float32, device=dev) if want_sem else None
+    sem_map = torch.empty((N, Ccls), dtype=torch.float32, device=dev) if want_sem else None
+    inst_map = fresh((N, D), dtype=torch.float32, device=dev) if D > 0 else None
+    out = (rgb_raw, rgb_map, sem_raw, sem_map, inst_map)
+    if M > 0 and argmax and (want_sem or D > 0):
+        # renderer.py:142-143: the semantic / instance sums take the one-hot of each ray's heaviest sample (of ALL its samples: a heaviest
+        # sample below the threshold is not in the list and the ray's sums stay 0, as in the reference, whose heads are 0 there); the colours
+        # keep the weights -- two passes of the compositing kernels, one per weight array
+        ctx.w_feat = torch.zeros_like(ctx.w).scatter_(1, ctx.w.argmax(dim=1, keepdim=True), 1.0)
+        if want_rgb:
+            _composite_fwd(ctx, ctx.w, out, feats=False)
+        _composite_fwd(ctx, ctx.w_feat, out, colour=False)
+    else:   # (no active sample in the chunk -- reference: the `if appearance_mask.any()` branch is skipped -- no weights and no head outputs)
+        _composite_fwd(ctx, ctx.w if M > 0 else None, out)
+    ctx.rgb_raw, ctx.sem_raw = rgb_raw, sem_raw
+    return rgb_map, sem_map, inst_map
+
+
+def _app_tail(M, H1, W2, b2, W3, b3, hdt, rgb_s):
+    """The last two appearance layers as their own launches: H2 = relu(H1 W2^T + b2) stored as ``hdt``, pre = H2 W3^T + b3,
+    rgb_s = sigmoid(pre).  Returns (H2, pre)."""
+    H2 = torch.empty((M, W2.shape[0]), dtype=hdt, device=H1.device)
+    gemm(M, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
+    pre = torch.empty((M, 3), dtype=torch.float32, device=H1.device)
+    gemm(M, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
+    call("clift_rows_act_fwd", ptr(pre), 3, M, 3, 1, ptr(rgb_s), 3, stream())
+    return H2, pre
+
+
+def _app_layers(M, X, layers, hdt, keep_h2, keep):
+    """The appearance MLP over its encoded input rows X (M, the first layer's row pitch), inside _app_precision(): H1 = relu(X W1^T + b1) stored as ``hdt``, then the
+    last two layers fused where a kernel exists -- H2 is written only for a backward (``keep_h2``) -- else _app_tail (H2 written, ``keep``
+    receives the pre-activation colours).  Returns (H1, H2, rgb_s)."""
+    (W1, b1), (W2, b2), (W3, b3) = layers
+    dev, ldx = X.device, _pitch(W1)
+    H1 = torch.empty((M, W1.shape[0]), dtype=hdt, device=dev)
+    gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
+    rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    if (MLP_PRECISION in (0, 2) and hdt == torch.float32 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128
+            and persistent_ok()):
+        # second hidden layer + output layer + sigmoid in one launch; H2 is written only for a backward
+        H2 = torch.empty((M, 128), dtype=torch.float32, device=dev) if keep_h2 else None
+        if MLP_PRECISION == 2 and persistent_x6_ok():        # (only inside _app_precision() with APP_X6)
+            call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
+                 ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
+        else:
+            app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
+    elif (MLP_PRECISION == 1 and hdt == torch.bfloat16 and H1.dtype == torch.bfloat16 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4
+            and W3.shape[1] == 128 and M >= 64 and persistent_ok()):
+        # bf16 mode: the same pair of layers over the bf16-stored activation (csrc/layer_nb16.hip)
+        H2 = torch.empty((M, 128), dtype=torch.bfloat16, device=dev) if keep_h2 else None
+        call("clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
+             ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
+    else:
+        H2, pre = _app_tail(M, H1, W2, b2, W3, b3, hdt, rgb_s)
+        keep.append(pre)
+    return H1, H2, rgb_s
+
+
 def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_sem=True, want_inst=True, grad_heads=("app", "sem", "fast", "slow"),
                    cap=None, want_dist=True):
     """Full renderer.forward (reference renderer.py:80-176).  Returns dict of outputs and the backward context.
@@ -908,9 +980,7 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
     rays, jitter = _check_rays(rays, jitter)
     views = model.named_views()
     ctx = _density_march(model, renderer, rays, jitter, cap)
-    N, S, M = ctx.N, ctx.S, ctx.M
-    dev = rays.device
-    st = stream()
+    S, M, dev, st = ctx.S, ctx.M, rays.device, stream()
     Ccls = model.num_semantic_classes
     D = model.dim_feature_instance if (want_inst and model.render_instance_mlp is not None) else 0
     ctx.softmax_mode = 1 if renderer.semantic_weight_mode == "softmax" else 0
@@ -951,8 +1021,7 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
             with _app_precision():
                 Wb = views["appearance_basis_mat.weight"]
                 nf, nc = Wb.shape
-                (W1, b1), (W2, b2), (W3, b3) = params["app"]
-                ldx = _pitch(W1)
+                ldx = _pitch(params["app"][0][0])
                 hdt = act_dtype() if ldx % 8 == 0 else torch.float32      # bf16 mode: encoded input and hidden activations bf16-stored
                 if front is not None:
                     feat, ldf, X = front
@@ -964,32 +1033,7 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
                     X = torch.empty((M, ldx), dtype=hdt, device=dev)
                     call("clift_app_encode_fwd", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(rays), ptr(ctx.act_idx), S, M,
                          ptr(X), ldx, int(hdt == torch.bfloat16), stream())
-                H1 = torch.empty((M, W1.shape[0]), dtype=hdt, device=dev)
-                gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
-                rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
-                if (MLP_PRECISION in (0, 2) and hdt == torch.float32 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128
-                        and persistent_ok()):
-                    # second hidden layer + output layer + sigmoid in one launch; H2 is written only for a backward
-                    H2 = torch.empty((M, 128), dtype=torch.float32, device=dev) if "app" in grad_heads else None
-                    if MLP_PRECISION == 2 and persistent_x6_ok():        # (only inside _app_precision() with APP_X6)
-                        call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
-                             ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
-                    else:
-                        app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
-                elif (MLP_PRECISION == 1 and hdt == torch.bfloat16 and H1.dtype == torch.bfloat16 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4
-                        and W3.shape[1] == 128 and M >= 64 and persistent_ok()):
-                    # bf16 mode: the same pair of layers over the bf16-stored activation (csrc/layer_nb16.hip)
-                    H2 = torch.empty((M, 128), dtype=torch.bfloat16, device=dev) if "app" in grad_heads else None
-                    call("clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
-                         ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
-                else:
-                    H2 = torch.empty((M, W2.shape[0]), dtype=hdt, device=dev)
-                    gemm(M, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
-                    pre = torch.empty((M, 3), dtype=torch.float32, device=dev)
-                    gemm(M, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
-                    call("clift_rows_act_fwd", ptr(pre), 3, M, 3, 1, ptr(rgb_s), 3, stream())
-                    keep.append(pre)
-                ctx.rgb_s = rgb_s
+                H1, H2, ctx.rgb_s = _app_layers(M, X, params["app"], hdt, "app" in grad_heads, keep)
                 if SOAK_KEEP:
                     ctx.soak = dict(feat=feat, X=X, H1=H1)
                 if "app" in grad_heads:
@@ -1003,25 +1047,7 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
         for slot, chain in _head_chains(model, views, ctx, params, grad_heads, want_sem):
             br.run(slot, chain)
         br.join()
-    # (the sum kernel writes every (ray, channel) when there are heads to sum; only a chunk without active samples needs the zeros)
-    fresh = torch.empty if M > 0 else torch.zeros
-    rgb_raw = fresh((N, 3), dtype=torch.float32, device=dev) if want_rgb else None
-    rgb_map = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_rgb else None
-    sem_raw = fresh((N, Ccls), dtype=torch.float32, device=dev) if want_sem else None
-    sem_map = torch.empty((N, Ccls), dtype=torch.float32, device=dev) if want_sem else None
-    inst_map = fresh((N, D), dtype=torch.float32, device=dev) if D > 0 else None
-    out = (rgb_raw, rgb_map, sem_raw, sem_map, inst_map)
-    if M > 0 and renderer.semantic_weight_mode == "argmax" and (want_sem or D > 0):
-        # renderer.py:142-143: the semantic / instance sums take the one-hot of each ray's heaviest sample (of ALL its samples: a heaviest
-        # sample below the threshold is not in the list and the ray's sums stay 0, as in the reference, whose heads are 0 there); the colours
-        # keep the weights -- two passes of the compositing kernels, one per weight array
-        ctx.w_feat = torch.zeros_like(ctx.w).scatter_(1, ctx.w.argmax(dim=1, keepdim=True), 1.0)
-        if want_rgb:
-            _composite_fwd(ctx, ctx.w, out, feats=False)
-        _composite_fwd(ctx, ctx.w_feat, out, colour=False)
-    else:   # (no active sample in the chunk -- reference: the `if appearance_mask.any()` branch is skipped -- no weights and no head outputs)
-        _composite_fwd(ctx, ctx.w if M > 0 else None, out)
-    ctx.rgb_raw, ctx.sem_raw = rgb_raw, sem_raw
+    rgb_map, sem_map, inst_map = _composite_outputs(ctx, renderer.semantic_weight_mode == "argmax", want_rgb, want_sem)
     out = dict(rgb=rgb_map, semantics=sem_map, instances=inst_map, depth=ctx.ray_out[:, 1],
                dist_reg=ctx.ray_out[:, 5].mean() if want_dist else None, opacity=ctx.ray_out[:, 0])     # (the trainer never reads the VALUE of the regulariser)
     return out, ctx
@@ -1047,12 +1073,7 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     if model.semantic_plane is not None or model.instance_plane is not None:
         raise NotImplementedError("edit_forward: a semantic / instance head on its own VM grid is not supported (xyz MLP heads only)")
     views = model.named_views()
-    N, S, dev, st = rays.shape[0], int(renderer.n_samples), rays.device, stream()
-    global _limit_owner
-    lim_t = _rows_limit.get((dev.type, dev.index))
-    if lim_t is not None and _limit_owner is not None:      # (as in _density_march: a synchronising pass after a sync-free one)
-        lim_t[0:1].fill_(INT_MAX)
-        _limit_owner = None
+    N, dev, st = rays.shape[0], rays.device, stream()
     if isinstance(edit, _edit.Edit):
         rec = edit.record()
         edit_kernel, edit_args = "clift_edit_%s", (C.byref(rec),)
@@ -1060,22 +1081,12 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
         prog = _edit.as_program(edit)
         rec = prog.records()
         edit_kernel, edit_args = "clift_edit_list_%s", (rec, len(prog))
-    ms = march_struct(renderer, model)
-    ms.weight_thres = float(weight_thres)                   # clift_march_fwd counts, clift_compact_fill lists: the same threshold
-    ctx = RenderCtx()
-    ctx.ms, ctx.res, ctx.N, ctx.S, ctx.rays = ms, grid_res(views), N, S, rays
-    vd = vm_struct(views, "density", ctx.res)
-    ctx.sigma = torch.empty((N, S), dtype=torch.float32, device=dev)
-    ctx.alpha, ctx.T, ctx.w = torch.empty_like(ctx.sigma), torch.empty_like(ctx.sigma), torch.empty_like(ctx.sigma)
-    ctx.ray_out = torch.empty((N, 8), dtype=torch.float32, device=dev)
-    n_active = torch.empty((N,), dtype=torch.int32, device=dev)
-    ctx.ray_start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
-    call(edit_kernel % "density_fwd", C.byref(ms), *edit_args, C.byref(vd), ptr(rays), N, ptr(ctx.sigma), st)
-    call("clift_march_fwd", C.byref(ms), ptr(rays), None, N, ptr(ctx.sigma), ptr(ctx.alpha), ptr(ctx.T), ptr(ctx.w), ptr(ctx.ray_out), ptr(n_active), st)
-    call("clift_scan_counts", ptr(n_active), N, ptr(ctx.ray_start), st)
-    M = ctx.M = int(ctx.ray_start[N].item())
-    ctx.act_idx = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
-    call("clift_compact_fill", ptr(ctx.w), ptr(ctx.ray_start), N, S, float(weight_thres), ptr(ctx.act_idx), st)
+
+    def density_fwd(ms, vd, sigma):
+        call(edit_kernel % "density_fwd", C.byref(ms), *edit_args, C.byref(vd), ptr(rays), N, ptr(sigma), st)
+
+    ctx = _density_march(model, renderer, rays, None, density_fwd=density_fwd, weight_thres=weight_thres)
+    ms, M = ctx.ms, ctx.M
     Ccls = model.num_semantic_classes
     D = model.dim_feature_instance if model.render_instance_mlp is not None else 0
     ctx.softmax_mode = 1 if renderer.semantic_weight_mode == "softmax" else 0
@@ -1097,51 +1108,21 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
             with _app_precision():
                 Wb = views["appearance_basis_mat.weight"]
                 nf = Wb.shape[0]
-                (W1, b1), (W2, b2), (W3, b3) = params["app"]
-                ldx, ldf = _pitch(W1), (nf + 3) // 4 * 4
+                ldx, ldf = _pitch(params["app"][0][0]), (nf + 3) // 4 * 4
                 feat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
                 with exact_fp32():
                     gemm(M, nf, nc, F, nc, Wb, _pitch(Wb), feat, ldf)
                 X = torch.empty((M, ldx), dtype=torch.float32, device=dev)
                 call("clift_app_encode_points", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(dirs), 4, M, ptr(X), ldx, stream())
-                H1 = torch.empty((M, W1.shape[0]), dtype=torch.float32, device=dev)
-                gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
-                rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
-                if MLP_PRECISION in (0, 2) and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128 and persistent_ok():
-                    if MLP_PRECISION == 2 and persistent_x6_ok():
-                        call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
-                             None, 128, ptr(rgb_s), 3, 1, stream())
-                    else:
-                        app_last2(M, H1, W2, b2, W3, b3, None, rgb_s)
-                else:
-                    H2 = torch.empty((M, W2.shape[0]), dtype=torch.float32, device=dev)
-                    gemm(M, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
-                    pre = torch.empty((M, 3), dtype=torch.float32, device=dev)
-                    gemm(M, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
-                    call("clift_rows_act_fwd", ptr(pre), 3, M, 3, 1, ptr(rgb_s), 3, stream())
-                    keep.extend([H2, pre])
-                keep.extend([feat, X, H1, F, dirs])
-                ctx.rgb_s = rgb_s
+                H1, H2, ctx.rgb_s = _app_layers(M, X, params["app"], torch.float32, False, keep)
+                keep.extend([feat, X, H1, H2, F, dirs])
 
         br = Branches(model=model)
         br.run(0, app_chain)
         for slot, chain in _head_chains(model, views, ctx, params, (), True):
             br.run(slot, chain)
         br.join()
-    fresh = torch.empty if M > 0 else torch.zeros
-    rgb_raw = fresh((N, 3), dtype=torch.float32, device=dev)
-    rgb_map = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    sem_raw = fresh((N, Ccls), dtype=torch.float32, device=dev)
-    sem_map = torch.empty((N, Ccls), dtype=torch.float32, device=dev)
-    inst_map = fresh((N, D), dtype=torch.float32, device=dev) if D > 0 else None
-    out = (rgb_raw, rgb_map, sem_raw, sem_map, inst_map)
-    if M > 0 and renderer.semantic_weight_mode == "argmax":         # exactly as render_forward: one-hot of each ray's heaviest sample
-        ctx.w_feat = torch.zeros_like(ctx.w).scatter_(1, ctx.w.argmax(dim=1, keepdim=True), 1.0)
-        _composite_fwd(ctx, ctx.w, out, feats=False)
-        _composite_fwd(ctx, ctx.w_feat, out, colour=False)
-    else:
-        _composite_fwd(ctx, ctx.w if M > 0 else None, out)
-    ctx.rgb_raw, ctx.sem_raw = rgb_raw, sem_raw
+    rgb_map, sem_map, inst_map = _composite_outputs(ctx, renderer.semantic_weight_mode == "argmax")
     return dict(rgb=rgb_map, semantics=sem_map, instances=inst_map, depth=ctx.ray_out[:, 1], opacity=ctx.ray_out[:, 0]), ctx
 
 
@@ -1501,10 +1482,6 @@ def appearance_mlp_points(module, viewdirs, features):
     call("clift_app_encode_points", ptr(f), nf, nf, module.pe_feat, module.pe_view, ptr(d), 3, n, ptr(X), ldx, stream())
     H1 = torch.empty((n, W1.shape[0]), dtype=torch.float32, device=f.device)
     gemm(n, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
-    H2 = torch.empty((n, W2.shape[0]), dtype=torch.float32, device=f.device)
-    gemm(n, W2.shape[0], W2.shape[1], H1, H1.shape[1], W2, _pitch(W2), H2, H2.shape[1], bias=b2, act=1)
-    pre = torch.empty((n, 3), dtype=torch.float32, device=f.device)
-    gemm(n, 3, W3.shape[1], H2, H2.shape[1], W3, _pitch(W3), pre, 3, bias=b3)
-    out = torch.empty_like(pre)
-    call("clift_rows_act_fwd", ptr(pre), 3, n, 3, 1, ptr(out), 3, stream())
+    out = torch.empty((n, 3), dtype=torch.float32, device=f.device)
+    _app_tail(n, H1, W2, b2, W3, b3, torch.float32, out)
     return out

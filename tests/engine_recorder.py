@@ -2,7 +2,8 @@
 
 ``Recorder`` replaces ``engine.call`` for the duration of a ``with`` block: nothing is launched; every call is stored as
 [entry point, arguments] with integers and floats as they are, pointers as None (NULL) or [buffer number, byte offset] -- buffers numbered by
-first appearance in the record -- and structs (Gemm, VM, VMGrad, March) as {field: value} in the same form.  A clift_gemm launch also carries
+first appearance in the record -- and structs (Gemm, VM, VMGrad, March, EditRec) as {field: value} in the same form, a struct inside a struct
+likewise; a host array of structs (the ``edits`` of the clift_edit_list_* entry points) as the list of them.  A clift_gemm launch also carries
 the name of the route clift_gemm_route gives its descriptor (the real library: it loads without a GPU).
 
 A pointer is resolved against the storages the recorder knows and keeps alive until it is dropped, so that no address is used twice within a
@@ -109,6 +110,8 @@ class Recorder:
             if ctype is C.c_void_p:
                 if self.pointers:
                     out[name] = self._pointer(v)
+            elif issubclass(ctype, C.Structure):
+                out[name] = self._struct(v)
             elif issubclass(ctype, C.Array):
                 if ctype._type_ is not C.c_void_p:
                     out[name] = list(v)
@@ -127,6 +130,8 @@ class Recorder:
                 rec.append(float(a) if kind in (C.c_float, C.c_double) else int(a))
             elif hasattr(a, "_obj"):                     # byref(struct)
                 rec.append(self._struct(a._obj))
+            elif isinstance(a, C.Array) and issubclass(a._type_, C.Structure):        # host array of structs: by content, no device pointer
+                rec.append([self._struct(x) for x in a])
             elif self.pointers:
                 rec.append(self._pointer(a.value if isinstance(a, C.c_void_p) else a))
         entry = [name, rec]

@@ -16,8 +16,19 @@ before its head / compositing sequences were gathered into shared helpers.
   * COMPOSITE_ACT_FUSED cleared on the grid fields and together with argmax weights (the remaining compositing call sites)          (63)
   * the point-wise utilities, once per mode                                                                                         (3)
 The golden file holds, per case, the sequence of entry points (indices into ``names``) and the sha256 of the full record, plus the sha256 of
-the enumeration.  ``python tests/test_engine_launches.py --dump DIR`` writes the full records, one JSON file per case, for diffing two trees;
-``--golden`` rewrites the golden file from the tree it runs in."""
+the enumeration.
+
+``edit_cases()`` enumerates 108 scene-edit renders (``engine.edit_forward``) the same way, against tests/golden/engine_edit_launches.json,
+recorded from the engine as it stood while ``edit_forward`` still carried its own copies of the march prologue, the appearance layers and the
+compositing tail (recorder and test extended, engine.py untouched).  Slow-fast xyz field (heads on grids are refused), 64 rays:
+  * per mode: M in {0, 300, 4096} x (softmax weights, softmax on white, argmax) x (one delete, one move with a rotation, a list of a copy
+    and a delete), ``weight_thres`` 0                                                                                              (81)
+  * per mode: one delete at weight_thres 1e-4                                                                                       (3)
+  * per mode, M = 4096, the move and the list: kernel_switches(tiled_only=True), kernel_switches(x6_tiled=True), APP_X6 cleared,
+    APP_BF16 cleared                                                                                                               (24)
+
+``python tests/test_engine_launches.py --dump DIR`` writes the full records of both enumerations, one JSON file per case, for diffing two
+trees; ``--golden`` / ``--golden-edit`` rewrites the one / the other golden file from the tree it runs in."""
 import contextlib
 import hashlib
 import json
@@ -31,6 +42,7 @@ from conftest import REPO
 from engine_recorder import Recorder
 
 GOLDEN = os.path.join(REPO, "tests", "golden", "engine_launches.json")
+GOLDEN_EDIT = os.path.join(REPO, "tests", "golden", "engine_edit_launches.json")
 GRID, RAYS, CLASSES, DIM_INST = 16, 64, 22, 6
 MODES = ("fp32", "bf16", "fp32x6")
 ROWS = (0, 63, 300, 4096)
@@ -47,6 +59,8 @@ CLEARED = ("APP_FRONT_FUSED", "COMPOSITE_ACT_FUSED", "APP_OUT_BWD_FUSED", "FUSE_
            "APP_SCATTER_XA", "DENS_BWD_SIGMA", "APP_BF16", "APP_X6")
 VARIATIONS = tuple("-" + f for f in CLEARED) + ("+KEEP_FIRST_ACT", "tiled_only", "x6_tiled")
 KEYS = ("mode", "field", "M", "pass", "weights", "white", "cap", "vary")
+EDIT_KEYS = ("mode", "edit", "M", "weights", "white", "thres", "vary")
+EDITS = ("delete", "move", "copy+delete")
 
 
 def cases():
@@ -89,12 +103,30 @@ def cases():
     return out
 
 
-def case_name(c):
-    return "/".join(str(c[k]) for k in KEYS)
+def edit_cases():
+    out = []
+
+    def add(mode, edit, M, weights="softmax", white=0, thres=0.0, vary=""):
+        out.append(dict(zip(EDIT_KEYS, (mode, edit, M, weights, white, thres, vary))))
+
+    for mode in MODES:
+        for M in (0, 300, 4096):
+            for weights, white in (("softmax", 0), ("softmax", 1), ("argmax", 0)):
+                for edit in EDITS:
+                    add(mode, edit, M, weights, white)
+        add(mode, "delete", 300, thres=1e-4)
+        for vary in ("tiled_only", "x6_tiled", "-APP_X6", "-APP_BF16"):     # (the appearance tail and the xyz heads branch on them)
+            for edit in ("move", "copy+delete"):
+                add(mode, edit, 4096, vary=vary)
+    return out
+
+
+def case_name(c):       # (the keys of a case are in KEYS / EDIT_KEYS order)
+    return "/".join(str(v) for v in c.values())
 
 
 def cases_sha256(cs):
-    return hashlib.sha256(json.dumps([[c[k] for k in KEYS] for c in cs]).encode()).hexdigest()
+    return hashlib.sha256(json.dumps([list(c.values()) for c in cs]).encode()).hexdigest()
 
 
 # ----------------------------------------------------------------------------- running one case
@@ -168,12 +200,27 @@ def run_points(engine, n):
     engine.feat_mlp_points(m.render_instance_mlp.mlp, engine.grid_feature_points(m, "instance", xyz))
 
 
+def edit_program(kind):
+    """The edits of an edit case (an ``Edit`` or a list of them) on one fixed box; every number is a binary fraction and the rotation a
+    quarter turn about z, so that the records hold the same bits wherever they are resolved."""
+    from contrastive_lift_amd import edit
+    box = edit.EditBox([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]], [0.125, -0.25, 0.0625], [-0.375, -0.25, -0.1875], [0.375, 0.25, 0.1875])
+    t, R = [0.25, 0.0, -0.125], [[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]]
+    return {"delete": lambda: edit.delete(box), "move": lambda: edit.move(box, t, R), "copy+delete": lambda: [edit.copy(box, t), edit.delete(box)],
+            "copy+copy": lambda: [edit.copy(box, t), edit.copy(box, [-0.25, 0.0, 0.125], R)]}[kind]()
+
+
 def record(c, pointers=True):
     """The launches of one case: [[entry point, arguments(, route)], ...]."""
     from contrastive_lift_amd import engine
     prev = engine.set_mlp_precision(c["mode"])
     try:
         with variation(c["vary"]):
+            if "edit" in c:
+                model, renderer, rays = field_on_cpu("xyz_sf"), renderer_on_cpu(c["weights"]), torch.zeros((RAYS, 8), dtype=torch.float32)
+                with Recorder(active=c["M"], roots=lambda: [model.param_flat, rays], pointers=pointers) as rec:
+                    engine.edit_forward(model, renderer, rays, edit_program(c["edit"]), bool(c["white"]), weight_thres=c["thres"])
+                return rec.launches
             if c["pass"] == "points":
                 models = [field_on_cpu("xyz_sf"), field_on_cpu("both_grid")]
                 with Recorder(roots=lambda: [m.param_flat for m in models], pointers=pointers) as rec:
@@ -205,8 +252,8 @@ def golden_document(cs):
 
 
 # ----------------------------------------------------------------------------- tests
-def test_engine_launches_match_the_recorded_ones():
-    doc, cs = json.load(open(GOLDEN)), cases()
+def compare_with_golden(golden, cs):
+    doc = json.load(open(golden))
     assert len(cs) == len(doc["cases"]) and cases_sha256(cs) == doc["cases_sha256"], "cases() no longer enumerates what the golden file was recorded for"
     bad = []
     for c in cs:
@@ -223,11 +270,26 @@ def test_engine_launches_match_the_recorded_ones():
     assert not bad, f"{len(bad)} of {len(cs)} cases differ:\n" + "\n".join(bad[:20])
 
 
+def test_engine_launches_match_the_recorded_ones():
+    compare_with_golden(GOLDEN, cases())
+
+
+def test_edit_launches_match_the_recorded_ones():
+    compare_with_golden(GOLDEN_EDIT, edit_cases())
+
+
+def run_edit(engine, model, renderer, pas, rays, jitter, white, cap, n_classes, dim_inst):
+    """run_pass for the scene-edit render ``pas`` = "edit:<kind of edit_program>" (no jitter, no backward)."""
+    return engine.edit_forward(model, renderer, rays, edit_program(pas[5:]), white)[1]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["fp32x6", "bf16"])
-def test_stand_in_launches_what_the_gpu_run_launches(mode):
+@pytest.mark.parametrize("mode, pas", [("fp32x6", "render_all"), ("bf16", "render_all"), ("fp32x6", "edit:copy+copy")], ids=["fp32x6", "bf16", "fp32x6-edit"])
+def test_stand_in_launches_what_the_gpu_run_launches(mode, pas):
     """The recorder's stand-in cannot drift from reality: a render forward + backward of 512 rays on the 32^3 synthetic scene, really launched,
-    and the same pass on the CPU stand-in with the row count the device found, give the same entry points with the same scalars."""
+    and the same pass on the CPU stand-in with the row count the device found, give the same entry points with the same scalars.  Likewise an
+    edit render of the same rays under a program of two copies (which kill nothing: M > 0)."""
+    run = run_edit if pas.startswith("edit:") else run_pass
     from contrastive_lift_amd import engine
     from contrastive_lift_amd.synthetic import make_scene
     n, grid = 512, 32
@@ -237,12 +299,12 @@ def test_stand_in_launches_what_the_gpu_run_launches(mode):
     prev = engine.set_mlp_precision(mode)
     try:
         with Recorder(launch=engine.call, pointers=False) as real:
-            ctx = run_pass(engine, model, renderer, "render_all", rays, jitter, False, None, CLASSES, DIM_INST)
+            ctx = run(engine, model, renderer, pas, rays, jitter, False, None, CLASSES, DIM_INST)
         torch.cuda.synchronize()
         assert ctx.M > 0
         cpu_model = field_on_cpu("xyz_sf", grid=grid)
         with Recorder(active=ctx.M, pointers=False) as stand_in:
-            run_pass(engine, cpu_model, renderer_on_cpu("softmax", grid), "render_all", torch.zeros((n, 8)), torch.zeros((n,)), False, None, CLASSES, DIM_INST)
+            run(engine, cpu_model, renderer_on_cpu("softmax", grid), pas, torch.zeros((n, 8)), torch.zeros((n,)), False, None, CLASSES, DIM_INST)
     finally:
         engine.set_mlp_precision(prev)
     assert [l[0] for l in stand_in.launches] == [l[0] for l in real.launches]
@@ -252,12 +314,16 @@ def test_stand_in_launches_what_the_gpu_run_launches(mode):
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--dump"]:
         os.makedirs(sys.argv[2], exist_ok=True)
-        for c in cases():
+        for c in cases() + edit_cases():
             with open(os.path.join(sys.argv[2], case_name(c).replace("/", "__") + ".json"), "w") as f:
                 f.write("\n".join(json.dumps(l) for l in record(c)) + "\n")
     elif sys.argv[1:2] == ["--golden"]:
         with open(GOLDEN, "w") as f:
             json.dump(golden_document(cases()), f, separators=(",", ":"))
             f.write("\n")
+    elif sys.argv[1:2] == ["--golden-edit"]:
+        with open(GOLDEN_EDIT, "w") as f:
+            json.dump(golden_document(edit_cases()), f, separators=(",", ":"))
+            f.write("\n")
     else:
-        sys.exit("usage: test_engine_launches.py --dump DIR | --golden")
+        sys.exit("usage: test_engine_launches.py --dump DIR | --golden | --golden-edit")
