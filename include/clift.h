@@ -734,6 +734,21 @@ int clift_iso_vertices(const float* vol, int n0, int n1, int n2, float level, co
 int clift_iso_faces(const float* vol, int n0, int n1, int n2, float level, const unsigned char* edge_mask, const long* vert_off,
                     const long* tri_off, long V, long F, int* faces, clift_stream_t s);
 
+/* ---- connected components of a keyed lattice (a further ABI 27 addition; csrc/components.hip).
+ *
+ * key (n0, n1, n2) int32, x-major like vol: lin(i, j, k) = (i n1 + j) n2 + k; 0 is background.  Two lattice points belong together iff they are
+ * neighbours under `connectivity` and carry the same non-zero key; a component is a class of the transitive closure.  connectivity: 6 = faces,
+ * 26 = full, 14 = the KUHN neighbourhood +-d for the seven non-zero d in {0,1}^3 -- exactly the seven edge classes of the iso-surface entries
+ * above, so that with key = (vol >= level) every face of that mesh belongs to one component of the inside set and to no second one (all vertex
+ * pairs of a Kuhn tetrahedron are Kuhn edges).
+ * root (N) int32, N = n0 n1 n2: root[p] = the smallest linear index of any point of p's component, -1 where key[p] == 0.  The result is defined
+ * without reference to execution order: two runs give the same bits.  Union-find with link-to-smaller-root in three launches (a 4 x 8 x 16 tile
+ * in LDS; the pairs across tile borders by device-scope atomic-min on the root words; a flattening pass).  No workgroup waits for another, and
+ * every loop is a root chase or a union retry whose index strictly descends.  Memory: nothing beside key and root.
+ * Errors, all checked before the device is touched: a dimension < 1, N >= CLIFT_ISO_LIMIT = 2^31 (the message names the limit), a connectivity
+ * other than 6 / 14 / 26, a NULL buffer. */
+int clift_cc_label(const int* key, int n0, int n1, int n2, int connectivity, int* root, clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,

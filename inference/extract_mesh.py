@@ -3,6 +3,7 @@
 
     python inference/extract_mesh.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt [--upsample 2] [--alpha_level 0.5 | --level SIGMA]
                                      [--cached_centroids_path all_centroids.pkl] [--split_instances] [--save_voxel_cloud]
+                                     [--min_component VOXELS] [--keep_largest K] [--connectivity {6,kuhn,26}] [--split_disconnected [MIN_VOXELS]]
 
 The checkpoint is loaded exactly as by ``inference/render_panopli.py`` (its ``load_for_inference``).  sigma is evaluated on the
 ``upsample``-times refined lattice of the scene box (``TensoRFRenderer.get_dense_sigma``, the reference's renderer.py:731-748, one launch),
@@ -19,6 +20,16 @@ carry that id); ``--save_voxel_cloud`` adds ``voxelcloud.pkl``: the voxels of ``
 with class and instance id by the same rule as the vertices and a colour from the appearance head at a ZERO view direction (a voxel
 has no normal), in the layout of ``pointcloud.pkl``, so ``inference/fit_bboxes.py --pointcloud`` reads it unchanged -- unlike ``pointcloud.pkl`` it
 holds the whole occupied volume, not only what some test camera saw.  Prints the time of every stage (device events).
+
+The raw iso-surface of a learnt density is full of floaters.  ``--min_component VOXELS`` / ``--keep_largest K`` label the connected components
+of the inside lattice points on the device (``components.filter_components``, clift_cc_label) and push the small ones below the level before
+the surface is extracted: with the default ``--connectivity kuhn`` (the mesher's own seven edge classes) a mesh face belongs to exactly one
+component, so what is left is the unfiltered mesh minus whole closed pieces.  ``--split_disconnected [MIN_VOXELS]`` cures ids that two
+objects share across the room (the nearest centroid knows nothing of space): every inside lattice point gets its id by the vertices' rule
+(zero normals, as for the voxel cloud), the lattice of thing ids is split into components (``components.split_disconnected``: the largest
+piece of an id keeps it, every other piece of at least MIN_VOXELS points gets a fresh id), and a vertex takes the new id of the inside
+endpoint of its edge wherever its own id is that point's original id.  Without these flags the files are byte-identical to what the tool
+wrote before it had them.  (The voxel cloud lives on another lattice, the model grid: it is neither filtered nor split.)
 """
 import argparse
 import math
@@ -36,6 +47,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 import render_panopli as rp                                           # noqa: E402
+from contrastive_lift_amd import components as cc                     # noqa: E402
 from contrastive_lift_amd import mesh as cm                           # noqa: E402
 from contrastive_lift_amd.config import load_run_config               # noqa: E402
 
@@ -71,18 +83,63 @@ class StageTimer:
         return times
 
 
-def surrogate_ids(model, renderer, points, normals, thing_classes, centroids, use_delta):
+def surrogate_ids(model, renderer, points, normals, thing_classes, centroids, use_delta, chunk=2 ** 20):
     """(semantics, instances, rgb) of world points: ``mesh.label_vertices``; without centroids its 0-based head argmax becomes 1 + argmax
     on thing classes and 0 on stuff, so that 0 means stuff in every file this tool writes."""
-    sem, inst, rgb = cm.label_vertices(model, renderer, points, normals, thing_classes, centroids=centroids, use_delta=use_delta)
+    sem, inst, rgb = cm.label_vertices(model, renderer, points, normals, thing_classes, centroids=centroids, chunk=chunk, use_delta=use_delta)
     if centroids is None:
         thing = torch.isin(sem, torch.tensor(sorted(int(c) for c in thing_classes), dtype=torch.int64, device=sem.device))
         inst = torch.where(thing, inst + 1, torch.zeros_like(inst))
     return sem, inst, rgb
 
 
+def lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, chunk=2 ** 20):
+    """The id lattice ``--split_disconnected`` works on: (n0, n1, n2) int32, the instance id (``surrogate_ids`` with zero normals) of every
+    inside lattice point of a thing class, 0 elsewhere.  ONE call for all inside points: with centroids the numbering offsets every class
+    by the labels seen before it in that call, so ids of separate calls do not compare; ``chunk`` only bounds the field evaluation inside
+    ``mesh.label_vertices``."""
+    inside = (sigma >= torch.tensor(float(level), dtype=torch.float32, device=sigma.device)).reshape(-1).nonzero().reshape(-1)
+    ids = torch.zeros(sigma.numel(), dtype=torch.int32, device=sigma.device)
+    ticks = renderer.lattice_ticks(sigma.shape)
+    n1, n2 = int(sigma.shape[1]), int(sigma.shape[2])
+    xyz = torch.stack([ticks[0][inside // (n1 * n2)], ticks[1][(inside // n2) % n1], ticks[2][inside % n2]], 1).contiguous()
+    ids[inside] = surrogate_ids(model, renderer, xyz, torch.zeros_like(xyz), things, centroids, use_delta, chunk=chunk)[1].int()
+    return ids.view(sigma.shape)
+
+
+def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity):
+    """-> (vertex ids after the split, table {fresh id: parent}).  A vertex takes the new id of the inside endpoint of its edge when its own
+    id equals that point's original id; otherwise it keeps its id.  Fresh ids start above every id in use, the vertices' included (a vertex
+    on a class boundary can carry an id that no lattice point has)."""
+    above = int(inst.max()) + 1 if inst.numel() else 1
+    new_ids, table = cc.split_disconnected(ids, connectivity=connectivity, min_voxels=min_voxels, first_fresh=above)
+    at = cc.vertex_owner_inside(keys, sigma, level)
+    old, new = ids.reshape(-1)[at].long(), new_ids.reshape(-1)[at].long()
+    return torch.where(inst == old, new, inst), table
+
+
+def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=0, keep_largest=None, connectivity="kuhn",
+                   split_disconnected=None):
+    """Everything between the density lattice and the files: (components) - isosurface - label_vertices - (split), each closed by a mark
+    of ``timer``.  -> dict(verts, faces, normals, sem, inst, rgb, sigma (as meshed), info (of filter_components, or None), table (of
+    split_disconnected, or None))."""
+    info = table = None
+    if int(min_component or 0) > 0 or keep_largest is not None:
+        sigma, info = cc.filter_components(sigma, level, min_voxels=min_component, keep_largest=keep_largest, connectivity=connectivity)
+        timer.done("components")
+    verts, faces, normals, *keys = cm.extract_isosurface(sigma, level, renderer.lattice_ticks(sigma.shape), return_keys=split_disconnected is not None)
+    timer.done("isosurface")
+    sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta)
+    timer.done("label_vertices")
+    if split_disconnected is not None:
+        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta)
+        inst, table = split_vertex_ids(inst, keys[0], sigma, level, ids, int(split_disconnected), connectivity)
+        timer.done("split")
+    return dict(verts=verts, faces=faces, normals=normals, sem=sem, inst=inst, rgb=rgb, sigma=sigma, info=info, table=table)
+
+
 def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
-                 device="cuda:0"):
+                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None):
     out = rp.output_dirname(config, "trajectory_blender", True, False, False)
     out.mkdir(exist_ok=True, parents=True)
     device = torch.device(device)
@@ -97,13 +154,17 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     timer = StageTimer()
     sigma = renderer.get_dense_sigma(model, upsample)
     timer.done("dense_sigma")
-    verts, faces, normals = cm.extract_isosurface(sigma, level, renderer.lattice_ticks(sigma.shape))
-    timer.done("isosurface")
-    sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta)
-    timer.done("label_vertices")
+    m = surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=min_component, keep_largest=keep_largest,
+                       connectivity=connectivity, split_disconnected=split_disconnected)
+    verts, faces, normals, sem, inst, rgb = (m[k] for k in ("verts", "faces", "normals", "sem", "inst", "rgb"))
     times = timer.report()
     print(f"sigma lattice {tuple(sigma.shape)}, level {level:.6g}: {verts.shape[0]} vertices, {faces.shape[0]} faces, "
           f"instance ids {sorted(torch.unique(inst).tolist())}")
+    if m["info"] is not None:
+        print(f"components ({connectivity}): {m['info']['K']} of the inside set, {len(m['info']['kept'])} kept, "
+              f"{m['info']['dropped']} lattice points dropped")
+    if m["table"] is not None:
+        print(f"split_disconnected ({connectivity}, pieces of at least {int(split_disconnected)} points): {len(m['table'])} fresh ids")
     cm.write_ply(out / "mesh.ply", verts, faces, normals, rgb, sem, inst)
     if split_instances:
         f_inst = inst[faces.long()]                                   # (F, 3)
@@ -145,6 +206,16 @@ def build_parser():
     ap.add_argument("--save_voxel_cloud", action="store_true",
                     help="also write voxelcloud.pkl (the occupied voxels, class and id as for the vertices, rgb at a zero view direction, in "
                          "pointcloud.pkl's layout) for inference/fit_bboxes.py")
+    ap.add_argument("--min_component", type=int, default=0, metavar="VOXELS",
+                    help="drop every connected component of the inside lattice points with fewer than this many points before meshing (0 = off)")
+    ap.add_argument("--keep_largest", type=int, default=None, metavar="K", help="keep only the K largest components (ties: the smaller first point)")
+    ap.add_argument("--connectivity", type=str, default="kuhn", choices=["6", "kuhn", "26"],
+                    help="what makes two lattice points neighbours: kuhn = the mesher's seven edge classes (14 neighbours), under which every mesh "
+                         "face belongs to exactly one component")
+    ap.add_argument("--split_disconnected", type=int, nargs="?", const=1, default=None, metavar="MIN_VOXELS",
+                    help="give the separated pieces of one instance id ids of their own: the largest keeps the id, every other piece of at least "
+                         "MIN_VOXELS lattice points (default 1) gets a fresh one; mesh_instance_<id>.ply follows the new ids (the PLY holds ids up "
+                         "to 65535: raise MIN_VOXELS or --min_component on a frothy scene)")
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="as render_panopli.py (the scene loader wants it)")
     return ap
 
@@ -156,4 +227,5 @@ if __name__ == "__main__":
     cfg.image_dim = list(args.image_dim)
     print(extract_mesh(cfg, upsample=args.upsample, alpha_level=args.alpha_level, level=args.level,
                        cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
-                       save_voxel_cloud=args.save_voxel_cloud)[0])
+                       save_voxel_cloud=args.save_voxel_cloud, min_component=args.min_component, keep_largest=args.keep_largest,
+                       connectivity=args.connectivity, split_disconnected=args.split_disconnected)[0])
