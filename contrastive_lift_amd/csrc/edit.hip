@@ -8,6 +8,7 @@
 // to scene_{i-1}, and a sample is evaluated in scene_n by walking the list backwards (edit_walk).  The program is a by-value kernel
 // argument: the records are the same for every lane, the trip count is wave-uniform and the records arrive through scalar loads.
 #include "clift_dev.h"
+#include "lattice_dev.h"
 #include <math.h>
 #include <stddef.h>
 CLIFT_ROWS_LIMIT_BINDER(edit)
@@ -117,6 +118,37 @@ __device__ __forceinline__ EditS edit_sample(const RayG& g, const MarchP& m, con
 // edit_sample; a killed sample stops (sigma = 0, nothing is looked up); a sample inside edit i's destination box continues at M_i p + t_i with
 // the view direction Dinv_i d.  The in-aabb flag is taken once, from the unedited point.  For n = 1 this is edit_sample, op for op; a sample
 // no edit remaps keeps the bits of sample_xn.  L lives in the kernel-argument segment and i is wave-uniform: scalar loads, no scratch copy.
+// The POINT form of the walk, shared by the ray kernels (edit_walk) and the point / lattice kernels below: p and d are walked in place.
+struct EditH {
+    bool kill;    // sigma = 0: some edit's kill rule named the point (p, d: where the walk stopped)
+    int hops;     // how many edits remapped it (0 .. CLIFT_EDIT_MAX)
+};
+__device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], float d[3]) {
+    EditH h;
+    h.kill = false;
+    h.hops = 0;
+    for (int i = L.n - 1; i >= 0; --i) {
+        const EditP& e = L.e[i];
+        const bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
+        const bool mov = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
+        const bool kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !mov) : false;
+        if (!h.kill && mov) {                               // (a killed sample has stopped: later tests see its last point, and change nothing)
+            const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
+            const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { p[j] = q[j]; d[j] = v[j]; }
+            ++h.hops;
+        }
+        h.kill = h.kill || kill;
+    }
+    return h;
+}
+// normalised coordinates of a walked point, every op rounded separately (sample_xn's ops)
+__device__ __forceinline__ void edit_normalise(const float p[3], const float lo[3], const float inv2[3], float xn[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xn[i] = __fsub_rn(__fmul_rn(__fsub_rn(p[i], lo[i]), inv2[i]), 1.0f);
+}
+
 struct EditW {
     bool in;      // inside the aabb (before any remap)
     bool kill;    // sigma = 0: some edit's kill rule named the sample
@@ -125,28 +157,14 @@ __device__ __forceinline__ EditW edit_walk(const RayG& g, const MarchP& m, const
     EditW s;
     float p[3];
     s.in = true;
-    s.kill = false;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
         s.in = s.in && !(m.lo[i] > p[i]) && !(p[i] > m.hi[i]);
         d[i] = g.d[i];
     }
-    for (int i = L.n - 1; i >= 0; --i) {
-        const EditP& e = L.e[i];
-        const bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
-        const bool mov = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
-        const bool kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !mov) : false;
-        if (!s.kill && mov) {                               // (a killed sample has stopped: later tests see its last point, and change nothing)
-            const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
-            const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { p[j] = q[j]; d[j] = v[j]; }
-        }
-        s.kill = s.kill || kill;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) xn[i] = __fsub_rn(__fmul_rn(__fsub_rn(p[i], m.lo[i]), m.inv2[i]), 1.0f);
+    s.kill = edit_walk_point(L, p, d).kill;
+    edit_normalise(p, m.lo, m.inv2, xn);
     return s;
 }
 
@@ -342,4 +360,112 @@ extern "C" int clift_edit_list_active(const clift_march_t* h_m, const clift_edit
     if (M <= 0) return 0;
     k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
     return clift_check_launch("clift_edit_list_active");
+}
+
+// ============================================================================ the walk over arbitrary points
+// One thread per row: world point (and view direction) in, the point (and direction) at which the field is to be looked up out, plus the
+// state byte.  No aabb test and no table: what "inside the scene" means is the caller's business (mesh.label_vertices, the lattice below).
+// A row no edit remaps is copied through untouched, so it keeps its input bits.  in == out is allowed (a thread reads its row, then writes it).
+__device__ __forceinline__ unsigned char edit_state(const EditH& h) { return (unsigned char)(h.hops | (h.kill ? CLIFT_EDIT_STATE_KILLED : 0)); }
+
+__global__ __launch_bounds__(256) void k_edit_list_points(EditL L, const float* pts, int ldp, const float* dirs, int ldd, long n, float* out_pts,
+                                                           float* out_dirs, unsigned char* state) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const float* pi = pts + (size_t)r * ldp;
+    float p[3] = {pi[0], pi[1], pi[2]}, d[3] = {0.f, 0.f, 0.f};
+    if (dirs != nullptr) {
+        const float* di = dirs + (size_t)r * ldd;
+        d[0] = di[0]; d[1] = di[1]; d[2] = di[2];
+    }
+    const EditH h = edit_walk_point(L, p, d);
+    float* po = out_pts + (size_t)r * ldp;
+    po[0] = p[0]; po[1] = p[1]; po[2] = p[2];
+    if (dirs != nullptr) {
+        float* dout = out_dirs + (size_t)r * ldd;
+        dout[0] = d[0]; dout[1] = d[1]; dout[2] = d[2];
+    }
+    if (state != nullptr) state[r] = edit_state(h);
+}
+
+extern "C" int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, const float* pts, int ldp, const float* dirs, int ldd, long n,
+                                      float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_points", &L)) return 1;
+    CLIFT_REQUIRE(ldp >= 3 && (dirs == nullptr || ldd >= 3), "clift_edit_list_points: ldp and ldd must be >= 3 (got %d, %d)", ldp, ldd);
+    CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "clift_edit_list_points: %ld rows, must be in [0, 2^36)", n);
+    if (n == 0) return 0;
+    CLIFT_REQUIRE(pts != nullptr && out_pts != nullptr, "clift_edit_list_points: NULL pts or out_pts");
+    CLIFT_REQUIRE((dirs == nullptr) == (out_dirs == nullptr), "clift_edit_list_points: dirs and out_dirs come together (both or neither NULL)");
+    k_edit_list_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
+    return clift_check_launch("clift_edit_list_points");
+}
+
+// ============================================================================ sigma on the lattice of the edited scene
+// clift_dense_sigma (isosurface.hip) with the program in it, one launch.  k_dense_sigma gives 4 lanes to a lattice point for the 18 table
+// reads; the walk is a few hundred VALU ops per point at 8 edits and would be done four times over if every lane of the quad walked.  So
+// the two phases use two mappings of one wave's 64 points: for the walk lane = point (lattice_point, then edit_walk_point, each done ONCE
+// per point), and for the taps four passes of 16 points x 4 lanes, as in edit_density_fwd, the quad fetching its point's normalised
+// position from the lane that walked it by __shfl -- registers only, no LDS.  The records arrive by scalar loads (L is a kernel
+// argument, the trip count is wave-uniform).  A killed point reads no table and gets exactly 0; a pass none of whose 16 points is alive
+// is skipped, and a wave all of whose points are killed leaves after the walk.  A point no edit remaps keeps the xn of lattice_point
+// and goes through vm_density_lane / vm_sigma in k_dense_sigma's lane roles: the bits of clift_dense_sigma.  A remapped point is
+// normalised with edit_walk's separately rounded ops; outside the box it reads zero padding (make_tap).  No atomics.
+__global__ __launch_bounds__(256) void k_edit_list_dense_sigma(VmP t, EditL L, float3 lo, float3 hi, float3 inv_ext2, const float* __restrict__ s0,
+                                                                const float* __restrict__ s1, const float* __restrict__ s2, int n0, int n1, int n2,
+                                                                float shift, float* __restrict__ out, unsigned char* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    const long total = (long)n0 * n1 * n2;
+    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long base = v - lane;                                      // the wave's first point (< total: the grid is cdiv(total, 256) and 256 = 4 waves)
+    if (base >= total) return;                                       // wave-uniform
+    const bool valid = v < total;
+    const long vc = valid ? v : total - 1;                           // (the tail lanes walk the last point again: no divergence around the loop)
+    const int i2 = (int)(vc % n2), i1 = (int)((vc / n2) % n1), i0 = (int)(vc / ((long)n1 * n2));
+    float p[3], xn[3], d[3] = {0.f, 0.f, 0.f};
+    lattice_point(lo, hi, inv_ext2, s0[i0], s1[i1], s2[i2], p, xn);
+    const EditH h = edit_walk_point(L, p, d);
+    if (h.hops > 0) {
+        const float l3[3] = {lo.x, lo.y, lo.z}, inv3[3] = {inv_ext2.x, inv_ext2.y, inv_ext2.z};
+        edit_normalise(p, l3, inv3, xn);
+    }
+    if (valid && state != nullptr) state[v] = edit_state(h);
+    const unsigned long long on = __ballot(valid && !h.kill);
+    if (on == 0) {                                                   // wave-uniform: nothing of this wave is looked up
+        if (valid) out[v] = 0.f;
+        return;
+    }
+    const int q = lane & 3;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int sl = pass * 16 + (lane >> 2);
+        float sig = 0.f;
+        if ((on >> (pass * 16)) & 0xffffull) {                       // wave-uniform: some point of this pass is looked up
+            const float xq[3] = {__shfl(xn[0], sl), __shfl(xn[1], sl), __shfl(xn[2], sl)};
+            const bool mine = (on >> sl) & 1ull;
+            float acc = mine ? vm_density_lane(t, xq, q) : 0.f;
+            acc += __shfl_xor(acc, 1);
+            acc += __shfl_xor(acc, 2);
+            if (mine) sig = vm_sigma(acc, shift);
+        }
+        if (q == 0 && base + sl < total) out[base + sl] = sig;
+    }
+}
+
+extern "C" int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, int n_edits, const float* h_lo3, const float* h_hi3,
+                                           const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2,
+                                           float shift, float* out, unsigned char* state, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_dense_sigma", &L)) return 1;
+    CLIFT_REQUIRE(h_dens && h_lo3 && h_hi3 && h_inv_ext2, "clift_edit_list_dense_sigma: NULL host record");
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_list_dense_sigma: comps must be a multiple of 4 (got %d)", h_dens->comps);
+    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_edit_list_dense_sigma: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
+    const long total = (long)n0 * n1 * n2;
+    CLIFT_REQUIRE(total < (1L << 36), "clift_edit_list_dense_sigma: %ld lattice points, must be < 2^36", total);
+    CLIFT_REQUIRE(s0 && s1 && s2 && out, "clift_edit_list_dense_sigma: NULL device buffer");
+    k_edit_list_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, make_float3(h_lo3[0], h_lo3[1], h_lo3[2]),
+                                                                        make_float3(h_hi3[0], h_hi3[1], h_hi3[2]),
+                                                                        make_float3(h_inv_ext2[0], h_inv_ext2[1], h_inv_ext2[2]), s0, s1, s2, n0, n1,
+                                                                        n2, shift, out, state);
+    return clift_check_launch("clift_edit_list_dense_sigma");
 }

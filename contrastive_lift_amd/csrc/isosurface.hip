@@ -2,11 +2,13 @@
 // iso-surface of a scalar lattice by marching tetrahedra on the Kuhn split.
 // Reference rows: model/renderer/panopli_tensoRF_renderer.py:731-748 (get_dense_sigma; the reference keeps no extractor of its own).
 #include "clift_dev.h"
+#include "lattice_dev.h"
 
 // ============================================================================ sigma on the lattice
 // k_alpha_lattice (march.hip) without the alpha step: lattice point p_a = lo_a (1 - s) + hi_a s with s = the caller's linspace value of
 // that axis, normalised like renderer.py:633, density + softplus like tensoRF.py:114-125.  4 lanes per lattice point (lane q owns channels
-// [4q, 4q + 4) + 16 per pass), long indices, fully coalesced store.
+// [4q, 4q + 4) + 16 per pass), long indices, fully coalesced store.  The point and the per-lane sum live in lattice_dev.h: the edited lattice
+// (k_edit_list_dense_sigma, edit.hip) shares them.
 __global__ __launch_bounds__(256) void k_dense_sigma(VmP t, float3 lo, float3 hi, float3 inv_ext2, const float* __restrict__ s0,
                                                       const float* __restrict__ s1, const float* __restrict__ s2, int n0, int n1, int n2,
                                                       float shift, float* __restrict__ out) {
@@ -15,21 +17,12 @@ __global__ __launch_bounds__(256) void k_dense_sigma(VmP t, float3 lo, float3 hi
     const int q = (int)(gid & 3);
     if (v >= total) return;
     const int i2 = (int)(v % n2), i1 = (int)((v / n2) % n1), i0 = (int)(v / ((long)n1 * n2));
-    const float a = s0[i0], b = s1[i1], c = s2[i2];
-    const float p[3] = {lo.x * (1.f - a) + hi.x * a, lo.y * (1.f - b) + hi.y * b, lo.z * (1.f - c) + hi.z * c};
-    const float xn[3] = {(p[0] - lo.x) * inv_ext2.x - 1.f, (p[1] - lo.y) * inv_ext2.y - 1.f, (p[2] - lo.z) * inv_ext2.z - 1.f};
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const VmTaps tp = vm_taps(t, i, xn);
-        for (int c4 = q * 4; c4 < t.comps; c4 += 16) acc += f4_hsum(f4_mul(vm_plane4(t, i, tp, c4), vm_line4(t, i, tp, c4)));
-    }
+    float p[3], xn[3];
+    lattice_point(lo, hi, inv_ext2, s0[i0], s1[i1], s2[i2], p, xn);
+    float acc = vm_density_lane(t, xn, q);
     acc += __shfl_xor(acc, 1);
     acc += __shfl_xor(acc, 2);
-    if (q == 0) {
-        const float x = acc + shift;
-        out[v] = (x > 20.f) ? x : log1pf(expf(x));
-    }
+    if (q == 0) out[v] = vm_sigma(acc, shift);
 }
 
 extern "C" int clift_dense_sigma(const clift_vm_t* h_dens, const float* h_lo3, const float* h_hi3, const float* h_inv_ext2, const float* s0,

@@ -26,6 +26,12 @@ from . import _lib
 DELETE, EXTRACT, DUPLICATE, MANIPULATE = 0, 1, 2, 3          # CLIFT_EDIT_* of include/clift.h
 _MODE_NAMES = {DELETE: "delete", EXTRACT: "extract", DUPLICATE: "duplicate", MANIPULATE: "manipulate"}
 MAX_EDITS = 8                                                # CLIFT_EDIT_MAX: edits in one program (EditProgram)
+STATE_KILLED = 0x80                                          # CLIFT_EDIT_STATE_KILLED: the kill bit of a walk's state byte (apply_to_points)
+STATE_REMAPS = 0x0f                                          # CLIFT_EDIT_STATE_REMAPS: its remap count
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else x
 
 
 def _np(x, shape):
@@ -166,6 +172,7 @@ class EditProgram:
         p = np.array(points, dtype=np.float64)
         d = None if dirs is None else np.array(dirs, dtype=np.float64)
         dead = np.zeros(p.shape[0], dtype=bool)
+        hops = np.zeros(p.shape[0], dtype=np.uint8)
         for e in reversed(self.edits):
             dead |= e.killed(p)                           # (a killed point is not walked further: its p stays where the walk stopped)
             if e.mode >= DUPLICATE:
@@ -173,16 +180,45 @@ class EditProgram:
                 p[mov] = p[mov] @ e.M.T + e.t
                 if d is not None:
                     d[mov] = d[mov] @ e.dir_inv.T
-        return p, d, dead
+                hops[mov] += 1
+        return p, d, dead, hops
 
     def source_points(self, points, dirs=None):
         """Where (n, 3) fp64 world points are finally looked up -- and, with ``dirs``, (points, view directions).  Rows of killed points
         (``killed``) hold the position at which the walk stopped."""
-        p, d, _ = self._walk(points, dirs)
+        p, d = self._walk(points, dirs)[:2]
         return p if dirs is None else (p, d)
 
     def killed(self, points):
         return self._walk(points, None)[2]
+
+    def apply_to_points(self, points, dirs=None, backend="device"):
+        """The walk over arbitrary world points (n, 3), with view directions (n, 3) or without: -> (source points, source directions or
+        None, state).  state (n) uint8 = the number of remaps (0 .. ``MAX_EDITS``) in the low bits, ``STATE_KILLED`` set where some edit's
+        kill rule named the point; a killed row holds the position at which its walk stopped, a row no edit remaps holds its input.  No
+        aabb test: the caller decides what is inside the scene.  ``backend="device"``: device fp32 tensors through
+        clift_edit_list_points (one launch; tensors in, tensors out; an untouched row gets its input bits back).  ``backend="host"``:
+        the fp64 walk of ``source_points`` / ``killed``, numpy arrays out."""
+        if backend == "host":
+            p, d, dead, hops = self._walk(np.asarray(_host(points), dtype=np.float64).reshape(-1, 3),
+                                          None if dirs is None else np.asarray(_host(dirs), dtype=np.float64).reshape(-1, 3))
+            return p, d, hops | np.where(dead, np.uint8(STATE_KILLED), np.uint8(0))
+        if backend != "device":
+            raise ValueError(f"backend is 'device' or 'host' (got {backend!r})")
+        import torch
+        pts = _lib.f32(points, "points").reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        dr = None
+        if dirs is not None:
+            dr = _lib.f32(dirs, "dirs").reshape(-1, 3).contiguous()
+            if dr.shape[0] != n or dr.device != pts.device:
+                raise ValueError(f"apply_to_points: {dr.shape[0]} directions on {dr.device} for {n} points on {pts.device}")
+        out_p = torch.empty_like(pts)
+        out_d = None if dr is None else torch.empty_like(dr)
+        state = torch.empty(n, dtype=torch.uint8, device=pts.device)
+        _lib.call("clift_edit_list_points", self.records(), len(self.edits), _lib.ptr(pts), 3, _lib.ptr(dr), 3, n, _lib.ptr(out_p),
+                  _lib.ptr(out_d), _lib.ptr(state), _lib.stream())
+        return out_p, out_d, state
 
 
 def as_program(x):

@@ -77,7 +77,7 @@ def extract_isosurface(vol, level, ticks, want_normals=True, return_keys=False):
 
 
 @torch.no_grad()
-def label_vertices(model, renderer, verts, normals, thing_classes, centroids=None, chunk=2 ** 20, use_delta=False):
+def label_vertices(model, renderer, verts, normals, thing_classes, centroids=None, chunk=2 ** 20, use_delta=False, edit=None):
     """Per vertex (world positions ``verts`` (V, 3) on the device): semantic class (V) int64 = argmax of the semantic head; instance id (V)
     int64; rgb (V, 3) fp32 in [0, 1] from the appearance head seen along ``-normal``.  All through the field's own point-wise methods
     (xyz-MLP and VM-grid heads alike), ``chunk`` vertices at a time.
@@ -87,8 +87,16 @@ def label_vertices(model, renderer, verts, normals, thing_classes, centroids=Non
     an ``all_centroids.pkl``: class -> (K, E)): vertices of stuff classes get 0, a vertex of thing class c gets the nearest centroid of c,
     numbered as ``inference.assign_clusters`` numbers ``pred_surrogateid`` -- over ALL vertices at once, since that numbering offsets
     every class by the labels seen before it.  ``use_delta``: the field predicts an offset, the feature is output + position
-    (render_panopli.py, config.use_delta)."""
+    (render_panopli.py, config.use_delta).
+
+    ``edit`` (an ``edit.Edit``, an ``edit.EditProgram`` or a sequence of edits): the vertices are those of the EDITED scene.  Every chunk
+    first goes through ``EditProgram.apply_to_points(verts, -normals)`` (clift_edit_list_points): the three heads are evaluated where the
+    vertex's content came from, the appearance head along the turned view direction, and with ``use_delta`` the feature is
+    fast(source) + source -- a moved object keeps its class, id and colour, a copy carries the original's id.  A killed vertex (the cap
+    of a cut) is labelled at the position where its walk stopped.  Rows the program does not touch get the bits they get without it."""
+    from . import edit as ed
     from . import inference as inf
+    prog = None if edit is None else ed.as_program(edit)
     verts = _lib.f32(verts, "verts").reshape(-1, 3).contiguous()
     dev = verts.device
     V = verts.shape[0]
@@ -104,11 +112,13 @@ def label_vertices(model, renderer, verts, normals, thing_classes, centroids=Non
     for a in range(0, V, int(chunk)):
         b = min(V, a + int(chunk))
         xyz = verts[a:b]
+        view = (-normals[a:b]).contiguous()
+        if prog is not None:
+            xyz, view, _ = prog.apply_to_points(xyz, view)
         xn = renderer.normalize_coordinates(xyz).contiguous()
         sem[a:b] = model.render_semantic_mlp(None, model.compute_semantic_feature(xn)).argmax(-1)
         fast = model.render_instance_mlp(None, model.compute_instance_feature(xn))[:, :E]
         feats[a:b] = fast + xyz if use_delta else fast
-        view = (-normals[a:b]).contiguous()
         rgb[a:b] = model.render_appearance_mlp(view, model.compute_appearance_feature(xn))
     if centroids is None:
         inst = feats.argmax(-1) if V else torch.zeros(0, dtype=torch.int64, device=dev)

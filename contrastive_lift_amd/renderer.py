@@ -230,11 +230,18 @@ class TensoRFRenderer(nn.Module):
         return [self.bbox_aabb[0][a] * (1 - s[a]) + self.bbox_aabb[1][a] * s[a] for a in range(3)]
 
     @torch.no_grad()
-    def get_dense_sigma(self, tensorf, upsample=1):
+    def get_dense_sigma(self, tensorf, upsample=1, edit=None, return_state=False):
         """sigma = softplus(density + shift) on the (g0 u, g1 u, g2 u) lattice of the current box (renderer.py:731-748), on the device:
-        one clift_dense_sigma launch, no materialised meshgrid and no loop over x-slabs."""
+        one clift_dense_sigma launch, no materialised meshgrid and no loop over x-slabs.
+
+        ``edit`` (an ``edit.Edit``, an ``edit.EditProgram`` or a sequence of edits, as in ``engine.edit_forward``): the lattice of the
+        EDITED scene, still one launch (clift_edit_list_dense_sigma) -- every lattice point is walked backwards through the program; a
+        killed point is exactly 0, a remapped point is looked up where its content came from, a point no edit touches has the bits it has
+        without ``edit``.  ``return_state=True`` -> (sigma, state): state (n0, n1, n2) uint8 = the number of remaps, ``edit.STATE_KILLED``
+        set where killed (all zero without ``edit``)."""
         import ctypes as C
         from . import _lib
+        from . import edit as ed
         upsample = int(upsample)
         if upsample < 1:
             raise ValueError(f"upsample must be >= 1 (got {upsample})")
@@ -246,9 +253,16 @@ class TensoRFRenderer(nn.Module):
         lo, hi = self.bbox_aabb_host
         f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
         sigma = torch.empty((n[0], n[1], n[2]), dtype=torch.float32, device=dev)
-        _lib.call("clift_dense_sigma", C.byref(vd), f3(lo), f3(hi), f3(self.inv_box_extent_host), _lib.ptr(ticks[0]), _lib.ptr(ticks[1]),
-                  _lib.ptr(ticks[2]), n[0], n[1], n[2], float(tensorf.splus_density_shift), _lib.ptr(sigma), _lib.stream())
-        return sigma
+        if edit is None:
+            _lib.call("clift_dense_sigma", C.byref(vd), f3(lo), f3(hi), f3(self.inv_box_extent_host), _lib.ptr(ticks[0]), _lib.ptr(ticks[1]),
+                      _lib.ptr(ticks[2]), n[0], n[1], n[2], float(tensorf.splus_density_shift), _lib.ptr(sigma), _lib.stream())
+            return (sigma, torch.zeros(sigma.shape, dtype=torch.uint8, device=dev)) if return_state else sigma
+        prog = ed.as_program(edit)
+        state = torch.empty(sigma.shape, dtype=torch.uint8, device=dev) if return_state else None
+        _lib.call("clift_edit_list_dense_sigma", C.byref(vd), prog.records(), len(prog), f3(lo), f3(hi), f3(self.inv_box_extent_host),
+                  _lib.ptr(ticks[0]), _lib.ptr(ticks[1]), _lib.ptr(ticks[2]), n[0], n[1], n[2], float(tensorf.splus_density_shift),
+                  _lib.ptr(sigma), _lib.ptr(state), _lib.stream())
+        return (sigma, state) if return_state else sigma
 
     @torch.no_grad()
     def get_instance_clusters(self, tensorf, mode):

@@ -170,6 +170,30 @@ int clift_edit_list_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_
                                 const float* rays, int N, float* sigma, clift_stream_t s);
 int clift_edit_list_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
                            float* xa, float* dirs, clift_stream_t s);
+/* The same walk off the rays (an ABI 27 addition): over arbitrary points, and over the lattice of clift_dense_sigma.  Both take the program as
+ * clift_edit_list_density_fwd does (a HOST array copied into the launch; the same errors, raised before anything is launched) and walk it with the
+ * very operations above.  The STATE byte of a point: the number of edits that remapped it (0 .. CLIFT_EDIT_MAX) in CLIFT_EDIT_STATE_REMAPS,
+ * CLIFT_EDIT_STATE_KILLED set if some kill rule named it.
+ *
+ * clift_edit_list_points: pts (n, ldp >= 3) world points, dirs (n, ldd >= 3) view directions or NULL.  out_pts / out_dirs (the same pitches; only
+ * the first three columns of a row are written; out_dirs is NULL exactly when dirs is) = the world point and the direction at which the field is
+ * to be looked up -- for a killed row the position at which its walk stopped.  state (n) uint8 or NULL.  There is NO aabb test: what "inside the
+ * scene" means is the caller's decision.  A row that no edit remaps gets its input bits back, point and direction.  out_pts may be pts and
+ * out_dirs may be dirs.  n == 0 returns 0 without a launch.  Errors: the program's, a pitch < 3, n < 0 or >= 2^36, a NULL pts or out_pts, dirs
+ * without out_dirs or the reverse.
+ *
+ * clift_edit_list_dense_sigma: clift_dense_sigma (below; the same arguments with the same meaning) on the EDITED scene, one launch.  The lattice
+ * point is formed as there, then walked.  A killed point gets exactly 0.0f and reads no table.  A remapped point is normalised with separately
+ * rounded ops, (p - lo) * inv_ext2 - 1, and looked up; a source point outside the box reads zero padding, as in clift_edit_list_density_fwd and
+ * clift_density_points.  A point that no edit remaps or kills gets the bits of clift_dense_sigma.  state (n0 n1 n2) uint8 or NULL.  No atomics:
+ * two runs give the same bits.  Errors: clift_dense_sigma's and the program's, all raised before the device is touched. */
+#define CLIFT_EDIT_STATE_KILLED 0x80
+#define CLIFT_EDIT_STATE_REMAPS 0x0f
+int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, const float* pts, int ldp, const float* dirs, int ldd, long n, float* out_pts,
+                           float* out_dirs, unsigned char* state, clift_stream_t s);
+int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, int n_edits, const float* h_lo3, const float* h_hi3,
+                                const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2, float shift,
+                                float* out, unsigned char* state, clift_stream_t s);
 
 /* ---- a7-a8: renderer.py:83-84,100-103,137,173-174,626-631 + eff_distloss (renderer.py:101).
  * Per sample alpha, T (transmittance before the sample), w = alpha*T, all (N, S).

@@ -4,6 +4,8 @@
     python inference/extract_mesh.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt [--upsample 2] [--alpha_level 0.5 | --level SIGMA]
                                      [--cached_centroids_path all_centroids.pkl] [--split_instances] [--save_voxel_cloud]
                                      [--min_component VOXELS] [--keep_largest K] [--connectivity {6,kuhn,26}] [--split_disconnected [MIN_VOXELS]]
+                                     [--bboxes bboxes.pkl (--instance ID --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz]
+                                                           [--pad 0.0] | --script edits.json)]
 
 The checkpoint is loaded exactly as by ``inference/render_panopli.py`` (its ``load_for_inference``).  sigma is evaluated on the
 ``upsample``-times refined lattice of the scene box (``TensoRFRenderer.get_dense_sigma``, the reference's renderer.py:731-748, one launch),
@@ -30,6 +32,16 @@ objects share across the room (the nearest centroid knows nothing of space): eve
 piece of an id keeps it, every other piece of at least MIN_VOXELS points gets a fresh id), and a vertex takes the new id of the inside
 endpoint of its edge wherever its own id is that point's original id.  Without these flags the files are byte-identical to what the tool
 wrote before it had them.  (The voxel cloud lives on another lattice, the model grid: it is neither filtered nor split.)
+
+``--bboxes`` with ``--instance`` / ``--op`` or with ``--script`` meshes the EDITED scene: the edit (``inference/edit_scene.py``'s
+``resolve_edit`` / ``resolve_program``: the same boxes, the same rigid copy / move, the same script format) is walked at every lattice point
+inside the density launch (``get_dense_sigma(edit=)``, clift_edit_list_dense_sigma) and at every vertex before it is labelled
+(``label_vertices(edit=)``), so a moved object keeps its class, id and colour and a copy carries the original's id (``--split_disconnected``
+gives the copy a fresh one).  The file is ``mesh_edit_<op>_<id>.ply`` or ``mesh_edit_script_<stem>.ply`` beside ``mesh.ply``, the
+``--split_instances`` files are ``mesh_edit_..._instance_<id>.ply``; the component flags act on the edited lattice.  At a cut face -- where
+a box face passes through matter: an extracted or moved object's sides, the hole a delete leaves -- the mesh is closed by a cap whose colour
+and labels are the field's values just inside the object.  ``--save_voxel_cloud`` is refused together with an edit: that cloud lives on the
+model grid through ``get_instance_clusters``, which knows nothing of edits.
 """
 import argparse
 import math
@@ -83,27 +95,29 @@ class StageTimer:
         return times
 
 
-def surrogate_ids(model, renderer, points, normals, thing_classes, centroids, use_delta, chunk=2 ** 20):
+def surrogate_ids(model, renderer, points, normals, thing_classes, centroids, use_delta, chunk=2 ** 20, edit=None):
     """(semantics, instances, rgb) of world points: ``mesh.label_vertices``; without centroids its 0-based head argmax becomes 1 + argmax
-    on thing classes and 0 on stuff, so that 0 means stuff in every file this tool writes."""
-    sem, inst, rgb = cm.label_vertices(model, renderer, points, normals, thing_classes, centroids=centroids, chunk=chunk, use_delta=use_delta)
+    on thing classes and 0 on stuff, so that 0 means stuff in every file this tool writes.  ``edit``: the points are points of the edited
+    scene (``label_vertices(edit=)``)."""
+    kw = {} if edit is None else {"edit": edit}
+    sem, inst, rgb = cm.label_vertices(model, renderer, points, normals, thing_classes, centroids=centroids, chunk=chunk, use_delta=use_delta, **kw)
     if centroids is None:
         thing = torch.isin(sem, torch.tensor(sorted(int(c) for c in thing_classes), dtype=torch.int64, device=sem.device))
         inst = torch.where(thing, inst + 1, torch.zeros_like(inst))
     return sem, inst, rgb
 
 
-def lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, chunk=2 ** 20):
+def lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, chunk=2 ** 20, edit=None):
     """The id lattice ``--split_disconnected`` works on: (n0, n1, n2) int32, the instance id (``surrogate_ids`` with zero normals) of every
     inside lattice point of a thing class, 0 elsewhere.  ONE call for all inside points: with centroids the numbering offsets every class
     by the labels seen before it in that call, so ids of separate calls do not compare; ``chunk`` only bounds the field evaluation inside
-    ``mesh.label_vertices``."""
+    ``mesh.label_vertices``.  ``edit``: sigma is the edited lattice, and every point is labelled where its content came from."""
     inside = (sigma >= torch.tensor(float(level), dtype=torch.float32, device=sigma.device)).reshape(-1).nonzero().reshape(-1)
     ids = torch.zeros(sigma.numel(), dtype=torch.int32, device=sigma.device)
     ticks = renderer.lattice_ticks(sigma.shape)
     n1, n2 = int(sigma.shape[1]), int(sigma.shape[2])
     xyz = torch.stack([ticks[0][inside // (n1 * n2)], ticks[1][(inside // n2) % n1], ticks[2][inside % n2]], 1).contiguous()
-    ids[inside] = surrogate_ids(model, renderer, xyz, torch.zeros_like(xyz), things, centroids, use_delta, chunk=chunk)[1].int()
+    ids[inside] = surrogate_ids(model, renderer, xyz, torch.zeros_like(xyz), things, centroids, use_delta, chunk=chunk, edit=edit)[1].int()
     return ids.view(sigma.shape)
 
 
@@ -119,9 +133,10 @@ def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity):
 
 
 def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=0, keep_largest=None, connectivity="kuhn",
-                   split_disconnected=None):
+                   split_disconnected=None, edit=None):
     """Everything between the density lattice and the files: (components) - isosurface - label_vertices - (split), each closed by a mark
-    of ``timer``.  -> dict(verts, faces, normals, sem, inst, rgb, sigma (as meshed), info (of filter_components, or None), table (of
+    of ``timer``.  ``edit``: sigma is the lattice of the edited scene (``get_dense_sigma(edit=)``); vertices and lattice points are then
+    labelled where their content came from.  -> dict(verts, faces, normals, sem, inst, rgb, sigma (as meshed), info (of filter_components, or None), table (of
     split_disconnected, or None))."""
     info = table = None
     if int(min_component or 0) > 0 or keep_largest is not None:
@@ -129,17 +144,23 @@ def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, 
         timer.done("components")
     verts, faces, normals, *keys = cm.extract_isosurface(sigma, level, renderer.lattice_ticks(sigma.shape), return_keys=split_disconnected is not None)
     timer.done("isosurface")
-    sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta)
+    sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta, edit=edit)
     timer.done("label_vertices")
     if split_disconnected is not None:
-        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta)
+        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, edit=edit)
         inst, table = split_vertex_ids(inst, keys[0], sigma, level, ids, int(split_disconnected), connectivity)
         timer.done("split")
     return dict(verts=verts, faces=faces, normals=normals, sem=sem, inst=inst, rgb=rgb, sigma=sigma, info=info, table=table)
 
 
 def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
-                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None):
+                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None):
+    """``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``."""
+    if edit is not None and save_voxel_cloud:
+        raise SystemExit(VOXEL_CLOUD_WITH_EDIT)
+    if edit is not None and not edit_tag:
+        raise ValueError("extract_mesh: an edit needs its edit_tag (the file is mesh_edit_<tag>.ply)")
+    stem = mesh_stem(edit_tag if edit is not None else None)
     out = rp.output_dirname(config, "trajectory_blender", True, False, False)
     out.mkdir(exist_ok=True, parents=True)
     device = torch.device(device)
@@ -152,10 +173,10 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     level = default_level(renderer, alpha_level) if level is None else float(level)
     use_delta = bool(getattr(config, "use_delta", False))
     timer = StageTimer()
-    sigma = renderer.get_dense_sigma(model, upsample)
+    sigma = renderer.get_dense_sigma(model, upsample) if edit is None else renderer.get_dense_sigma(model, upsample, edit=edit)
     timer.done("dense_sigma")
     m = surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=min_component, keep_largest=keep_largest,
-                       connectivity=connectivity, split_disconnected=split_disconnected)
+                       connectivity=connectivity, split_disconnected=split_disconnected, edit=edit)
     verts, faces, normals, sem, inst, rgb = (m[k] for k in ("verts", "faces", "normals", "sem", "inst", "rgb"))
     times = timer.report()
     print(f"sigma lattice {tuple(sigma.shape)}, level {level:.6g}: {verts.shape[0]} vertices, {faces.shape[0]} faces, "
@@ -165,7 +186,7 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
               f"{m['info']['dropped']} lattice points dropped")
     if m["table"] is not None:
         print(f"split_disconnected ({connectivity}, pieces of at least {int(split_disconnected)} points): {len(m['table'])} fresh ids")
-    cm.write_ply(out / "mesh.ply", verts, faces, normals, rgb, sem, inst)
+    cm.write_ply(out / f"{stem}.ply", verts, faces, normals, rgb, sem, inst)
     if split_instances:
         f_inst = inst[faces.long()]                                   # (F, 3)
         for i in torch.unique(inst).tolist():
@@ -173,7 +194,7 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
             if sel.shape[0] == 0:
                 continue
             used, renum = torch.unique(sel, return_inverse=True)
-            cm.write_ply(out / f"mesh_instance_{int(i)}.ply", verts[used], renum.int(), normals[used], rgb[used], sem[used], inst[used])
+            cm.write_ply(out / f"{stem}_instance_{int(i)}.ply", verts[used], renum.int(), normals[used], rgb[used], sem[used], inst[used])
     if save_voxel_cloud:
         state = random.getstate()                                     # the draw is seeded for a reproducible file; the caller's generator is put back
         random.seed(0)
@@ -189,8 +210,62 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     return out, times
 
 
+VOXEL_CLOUD_WITH_EDIT = ("--save_voxel_cloud cannot be combined with an edit: the voxel cloud lives on the model grid through "
+                         "get_instance_clusters, which knows nothing of edits -- export it without --bboxes")
+EDIT_OPS = ("delete", "extract", "copy", "move")                      # edit_scene.OPS (checked in resolve_cli_edit)
+
+
+def mesh_stem(edit_tag=None):
+    """File stem of the mesh: ``mesh``, or ``mesh_edit_<tag>`` for an edited scene; ``<stem>.ply`` and ``<stem>_instance_<id>.ply``."""
+    return "mesh" if edit_tag is None else f"mesh_edit_{edit_tag}"
+
+
+def edit_tag_of(args):
+    """``<op>_<id>`` or ``script_<file stem>`` (the tags of inference/edit_scene.py's output folders); None without an edit."""
+    if args.script is not None:
+        return f"script_{Path(args.script).stem}"
+    return None if args.op is None else f"{args.op}_{args.instance}"
+
+
+def resolve_cli_edit(args):
+    """(edit, tag) of the parsed command line, (None, None) without an edit: the boxes of ``--bboxes`` through inference/edit_scene.py's
+    ``resolve_edit`` / ``resolve_program``."""
+    tag = edit_tag_of(args)
+    if tag is None:
+        return None, None
+    import json
+    import edit_scene as es
+    assert tuple(es.OPS) == EDIT_OPS
+    with open(args.bboxes, "rb") as f:
+        boxes = pickle.load(f)
+    if args.script is not None:
+        with open(args.script) as f:
+            return es.resolve_program(boxes, json.load(f)), tag
+    return es.resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad), tag
+
+
+class _Parser(argparse.ArgumentParser):
+    """The cross-argument rules of the edit flags, checked where the arguments are parsed."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.script is None and (a.instance is None) != (a.op is None):
+            self.error("--instance and --op come together")
+        if edit_tag_of(a) is None:
+            if a.bboxes is not None:
+                self.error("--bboxes needs an edit: --instance ID --op OP, or --script FILE.json")
+            return a
+        if a.script is not None and a.instance is not None:
+            self.error("--script holds the edits: give it without --instance / --op")
+        if a.bboxes is None:
+            self.error("an edit needs --bboxes (bboxes.pkl of inference/fit_bboxes.py)")
+        if a.save_voxel_cloud:
+            raise SystemExit(VOXEL_CLOUD_WITH_EDIT)
+        return a
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="Extract a labelled surface mesh (mesh.ply) from a trained checkpoint.")
+    ap = _Parser(description="Extract a labelled surface mesh (mesh.ply) from a trained checkpoint.")
     ap.add_argument("--ckpt_path", type=str, required=True)
     ap.add_argument("--upsample", type=int, default=2, help="sigma lattice = grid x this factor per axis")
     lv = ap.add_mutually_exclusive_group()
@@ -217,6 +292,16 @@ def build_parser():
                          "MIN_VOXELS lattice points (default 1) gets a fresh one; mesh_instance_<id>.ply follows the new ids (the PLY holds ids up "
                          "to 65535: raise MIN_VOXELS or --min_component on a frothy scene)")
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="as render_panopli.py (the scene loader wants it)")
+    ap.add_argument("--bboxes", type=str, default=None, help="bboxes.pkl of inference/fit_bboxes.py: mesh the scene under an edit (with --instance / --op or --script)")
+    ap.add_argument("--instance", type=int, default=None, help="instance id (a key of bboxes.pkl) the edit acts on")
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument("--op", choices=EDIT_OPS, default=None, help="the edit; the file is mesh_edit_<op>_<id>.ply")
+    which.add_argument("--script", type=str, default=None, metavar="FILE.json",
+                       help="an ordered list of up to 8 edits (the format of inference/edit_scene.py --script); the file is mesh_edit_script_<stem>.ply")
+    ap.add_argument("--translate", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="copy / move: translation t")
+    ap.add_argument("--rotate_deg", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("RX", "RY", "RZ"),
+                    help="copy / move: rotation about the box centre, R = Rz Ry Rx (degrees)")
+    ap.add_argument("--pad", type=float, default=0.0, help="grow the fitted box by this much on every side")
     return ap
 
 
@@ -225,7 +310,8 @@ if __name__ == "__main__":
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
     cfg.image_dim = list(args.image_dim)
+    the_edit, the_tag = resolve_cli_edit(args)
     print(extract_mesh(cfg, upsample=args.upsample, alpha_level=args.alpha_level, level=args.level,
                        cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
                        save_voxel_cloud=args.save_voxel_cloud, min_component=args.min_component, keep_largest=args.keep_largest,
-                       connectivity=args.connectivity, split_disconnected=args.split_disconnected)[0])
+                       connectivity=args.connectivity, split_disconnected=args.split_disconnected, edit=the_edit, edit_tag=the_tag)[0])
