@@ -109,8 +109,10 @@ extern "C" int clift_tv_fwd_bwd_multi(const clift_tv_set_t* set, float* loss_acc
         most = t > most ? t : most;
     }
     // few, long-running blocks: every block ends in ONE atomic on the same loss word, and same-address atomics serialise (~5 ns each:
-    // 12 k blocks spent 60 us there)
-    const int bx = (int)((most + 255) / 256 < 128 ? (most + 255) / 256 : 128);
+    // 12 k blocks spent 60 us there).  At least one block: a set whose planes all have fewer than four elements has most == 0, and its
+    // value (zero or not: a (1, 2, 1) plane has one difference) still has to be added
+    const long want = (most + 255) / 256;
+    const int bx = (int)(want < 1 ? 1 : want < 128 ? want : 128);
     k_tv_multi<<<dim3(bx, set->n), 256, 0, as_stream(s)>>>(*set, loss_accum);
     return clift_check_launch("clift_tv_fwd_bwd_multi");
 }
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256) void k_contrastive_rows(const float* __restric
 }
 
 __global__ __launch_bounds__(256) void k_contrastive_grad(const float* __restrict__ f, const int* __restrict__ y, int B, int E, float temp,
-                                                           const float* __restrict__ pz, float* __restrict__ loss, float* __restrict__ gf) {
+                                                           const float* __restrict__ pz, float* __restrict__ terms, float* __restrict__ gf) {
     __shared__ float sh[4];
     const int a = blockIdx.x;
     float fa[CL_MAXE], ga[CL_MAXE];
@@ -349,7 +351,18 @@ __global__ __launch_bounds__(256) void k_contrastive_grad(const float* __restric
         const float t = block_sum_256(ga[e], sh);
         if (threadIdx.x == 0 && gf) gf[(size_t)a * E + e] = t;
     }
-    if (threadIdx.x == 0 && pa != 0.f) unsafeAtomicAdd(loss, -logf(pa / Za) * invB);
+    if (threadIdx.x == 0) terms[a] = pa != 0.f ? -logf(pa / Za) * invB : 0.f;
+}
+
+// loss = sum of the per-row terms, in a fixed order: one block, strided partial sums, then the block tree.  (B atomics on the loss word
+// instead made the value depend on their order, and at B = 513 left it up to 1.2e-6 relative from the fp64 sum -- a chain of B roundings of
+// the running total.)
+__global__ __launch_bounds__(256) void k_contrastive_loss(const float* __restrict__ terms, int B, float* __restrict__ loss) {
+    __shared__ float sh[4];
+    float part = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) part += terms[i];
+    const float t = block_sum_256(part, sh);
+    if (threadIdx.x == 0) loss[0] = t;
 }
 
 __global__ void k_zero1(float* p) { p[0] = 0.f; }
@@ -357,10 +370,14 @@ __global__ void k_zero1(float* p) { p[0] = 0.f; }
 extern "C" int clift_contrastive(const float* feat, const int* labels, int B, int E, float temperature, float* loss, float* g_feat,
                                  float* work, clift_stream_t s) {
     CLIFT_REQUIRE(E >= 1 && E <= CL_MAXE, "clift_contrastive: E must be in [1,%d]", CL_MAXE);
-    k_zero1<<<1, 1, 0, as_stream(s)>>>(loss);
-    if (B <= 0) return clift_check_launch("clift_contrastive");
+    if (B <= 0) {
+        k_zero1<<<1, 1, 0, as_stream(s)>>>(loss);
+        return clift_check_launch("clift_contrastive");
+    }
+    // work: [p(B) | Z(B) | per-row loss terms(B)]
     k_contrastive_rows<<<B, 256, 0, as_stream(s)>>>(feat, labels, B, E, temperature, work);
-    k_contrastive_grad<<<B, 256, 0, as_stream(s)>>>(feat, labels, B, E, temperature, work, loss, g_feat);
+    k_contrastive_grad<<<B, 256, 0, as_stream(s)>>>(feat, labels, B, E, temperature, work, work + 2 * (size_t)B, g_feat);
+    k_contrastive_loss<<<1, 256, 0, as_stream(s)>>>(work + 2 * (size_t)B, B, loss);
     return clift_check_launch("clift_contrastive");
 }
 

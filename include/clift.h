@@ -569,7 +569,8 @@ int clift_semantic_loss_rows(const float* pred, const float* probs, const float*
 int clift_segment_loss(const float* feats, int ld, const int* group, const float* conf, const float* class_w, int B,
                        int C, int G, float scale, float* work, float* loss, float* grad, int ldg, clift_stream_t s);
 
-/* ---- a16: model/loss/loss.py:62-82.  loss[0] = value; g_feat (B,E) = d loss / d features (nullable). */
+/* ---- a16: model/loss/loss.py:62-82.  loss[0] = value; g_feat (B,E) = d loss / d features (nullable).  1 <= E <= 32.  The value is the
+ * sum of the per-row terms in a fixed order (kept in work): the same inputs give the same bits. */
 int clift_contrastive(const float* feat, const int* labels, int B, int E, float temperature, float* loss,
                       float* g_feat, float* work /* >= 4*B floats */, clift_stream_t s);
 
@@ -580,7 +581,9 @@ int clift_slow_fast(const float* inst, const int* labels, const float* conf, int
                     float* g_inst, float* work, clift_stream_t s);
 
 /* ---- inference post-processing: inference/render_panopli.py:371-419 (assign_clusters: per-class cdist + argmin against
- * cached centroids).  labels[i] = argmin_c |feat_i - centroid_c| where valid[i] != 0 (NULL = all), else -1. */
+ * cached centroids).  labels[i] = argmin_c |feat_i - centroid_c| where valid[i] != 0 (NULL = all), else -1.  feat (n, ldf), ldf >= E;
+ * the lowest index wins a tie.  A row whose squared distance to every centroid is NaN (a NaN feature, or NaN centroids) or
+ * overflows to +inf gets -1, like an invalid row: no distance compares below the running minimum, which starts at +inf. */
 int clift_nearest_centroid(const float* feat, int ldf, int E, const float* centroids, int K, const unsigned char* valid,
                            long n, int* labels, clift_stream_t s);
 
