@@ -155,6 +155,8 @@ _SIGNATURES = {
     "clift_iso_vertices": ([_P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _L, _P, _P, _P], C.c_int),
     "clift_iso_faces": ([_P, _I, _I, _I, _F, _P, _P, _P, _L, _L, _P, _P], C.c_int),
     "clift_cc_label": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
+    "clift_density_grad_points": ([_P, _P, _I, _L, _F, _P, _P, _P], C.c_int),
+    "clift_ray_surface": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P, _P], C.c_int),
     "clift_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P], C.c_int),
     "clift_ema": ([_P, _P, _L, _F, _P], C.c_int),
 }

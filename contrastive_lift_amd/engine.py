@@ -714,6 +714,7 @@ class RenderCtx:
         self.sigma = self.alpha = self.T = self.w = self.ray_out = self.ray_start = self.act_idx = None
         self.N = self.S = self.M = 0
         self.capped = False                  # a sync-free chunk: M is the capacity, the row count stays on the device (ray_start[N])
+        self.edited = False                  # sigma came from a caller's launch (the edit renders): xa may hold remapped positions
         self.white_bg = self.softmax_mode = self.stop_grad = self.C = self.D = 0
         self.want = (False, False, False)    # (colour, semantic, instance) outputs composited
         self.xa = None                       # (M, 4) positions of the active samples
@@ -821,6 +822,7 @@ def _density_march(model, renderer, rays, jitter, cap=None, density_fwd=None, we
     ctx = RenderCtx()
     ctx.ms, ctx.res, ctx.N, ctx.S, ctx.M = ms, res, N, S, M
     ctx.capped = cap is not None
+    ctx.edited = density_fwd is not None
     if ctx.capped:
         _limit_owner = ctx
     ctx.rays, ctx.jitter = rays, jitter
@@ -1407,6 +1409,82 @@ def density_points(model, xyz, activation=True):
     call("clift_density_points", C.byref(vd), ptr(x), x.shape[1], x.shape[0], float(model.splus_density_shift), int(bool(activation)),
          ptr(out), stream())
     return out
+
+
+@torch.no_grad()
+def density_grad_points(model, xyz, world=True, renderer=None):
+    """(n, 4) rows [gx, gy, gz, sigma_raw] at normalised points: the analytic gradient of the density before its softplus (DESIGN.md 6g;
+    right-sided on a texel line, the zero padding seen as a step at the table's edge) and that density itself, with the bits of
+    ``density_points(activation=False)``.  ``world``: the gradient in world units, g_a * 2 / extent_a of ``renderer``'s box (a renderer, or the
+    three factors themselves, is then required: the field does not know its box); False: with respect to the normalised coordinates."""
+    x = _points(xyz)
+    reset_rows_limit(x.device)
+    inv2 = None
+    if world:
+        if renderer is None:
+            raise _lib.CliftError("density_grad_points(world=True) needs the renderer whose box scales the gradient (or world=False)")
+        inv2 = (C.c_float * 3)(*[float(v) for v in getattr(renderer, "inv_box_extent_host", renderer)])
+    views = model.named_views()
+    vd = vm_struct(views, "density", grid_res(views))
+    out = torch.empty((x.shape[0], 4), dtype=torch.float32, device=x.device)
+    call("clift_density_grad_points", C.byref(vd), ptr(x), x.shape[1], x.shape[0], float(model.splus_density_shift), inv2, ptr(out), stream())
+    return out
+
+
+def _surface_launches(model, ctx, q):
+    """The two launches of the surface pass over a march context whose xa is filled: the world gradient at the active samples, then the
+    per-ray median hit and normal sums."""
+    N, M, dev = ctx.N, ctx.M, ctx.rays.device
+    q = float(q)
+    if not 0.0 < q < 1.0:
+        raise _lib.CliftError(f"surface outputs: q must lie in (0, 1), got {q}")
+    G = None
+    if M > 0:
+        views = model.named_views()
+        vd = vm_struct(views, "density", ctx.res)
+        G = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        call("clift_density_grad_points", C.byref(vd), ptr(ctx.xa), 4, M, float(ctx.ms.density_shift), ctx.ms.inv_ext2, ptr(G), stream())
+    depth = torch.empty((N,), dtype=torch.float32, device=dev)
+    k_med = torch.empty((N,), dtype=torch.int32, device=dev)
+    nrm = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    call("clift_ray_surface", C.byref(ctx.ms), ptr(ctx.rays), ptr(ctx.jitter), N, ptr(ctx.T), ptr(ctx.w), ptr(ctx.ray_start),
+         ptr(ctx.act_idx) if M > 0 else None, M, ptr(G), q, ptr(depth), ptr(k_med), ptr(nrm), stream())
+    rays = ctx.rays
+    return dict(depth_median=depth, hit=k_med >= 0, k_median=k_med, normals=nrm[:, :3],
+                points=rays[:, 0:3] + depth[:, None] * rays[:, 3:6])
+
+
+@torch.no_grad()
+def surface_from_ctx(model, renderer, ctx, q=0.5):
+    """Surface outputs of the rays of a context that ``render_forward`` or ``feature_forward`` returned, from what its march
+    stored: dict(depth_median (N,), hit (N,) bool, k_median (N,) int32, normals (N, 3) = sum_k w_k n_k, un-normalised, points (N, 3) =
+    o + depth_median d; depth_median and k_median are 0 and -1 where hit is False).  Two launches; the context is only read.
+    Refused: a sync-free (capped) context, whose row count never reached the host, and a context of ``edit_forward``, where the gradient at a
+    remapped sample would have to be turned back through the edit."""
+    if not isinstance(ctx, RenderCtx) or ctx.ms is None:
+        raise _lib.CliftError("surface_from_ctx: not a context of render_forward / feature_forward")
+    if ctx.capped:
+        raise _lib.CliftError("surface_from_ctx: a sync-free (capped) context is not supported: its active-sample count stays on the device")
+    if ctx.edited:
+        raise _lib.CliftError("surface_from_ctx: a context of edit_forward is not supported: normals and median depth under a scene edit "
+                              "are out of scope (the gradient at a remapped sample would have to be turned back through the edit)")
+    if ctx.M > 0 and ctx.xa is None:
+        raise _lib.CliftError("surface_from_ctx: the context holds no positions of its active samples (xa)")
+    return _surface_launches(model, ctx, q)
+
+
+@torch.no_grad()
+def surface_forward(model, renderer, rays, jitter=None, q=0.5):
+    """Geometry only: the march, the positions of the active samples and the two surface launches -- no head runs.  Returns (the dict of
+    ``surface_from_ctx`` plus depth = the expected distance and opacity, context)."""
+    rays, jitter = _check_rays(rays, jitter)
+    ctx = _density_march(model, renderer, rays, jitter)
+    if ctx.M > 0:
+        ctx.xa = torch.empty((ctx.M, 4), dtype=torch.float32, device=rays.device)
+        call("clift_active_xyz", C.byref(ctx.ms), ptr(rays), ptr(jitter), ptr(ctx.act_idx), ctx.M, ptr(ctx.xa), stream())
+    out = _surface_launches(model, ctx, q)
+    out["depth"], out["opacity"] = ctx.ray_out[:, 1], ctx.ray_out[:, 0]
+    return out, ctx
 
 
 def _basis_feature_points(model, prefix, xyz, precision):

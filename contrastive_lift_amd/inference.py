@@ -40,6 +40,24 @@ def render_rays_edit(model, renderer, rays, chunk, white_bg=False, edit=None, we
     return tuple(torch.cat(x, 0) for x in outs)
 
 
+@torch.no_grad()
+def render_rays_surface(model, renderer, rays, chunk, white_bg=False, q=0.5):
+    """``render_rays`` plus the surface outputs of every chunk's march (engine.surface_from_ctx, two more launches per chunk): returns
+    rgb (P,3), semantics (P,C), instances (P,D), distance (P,), distance_median (P,), hit (P,) as float 0 / 1, normals (P,3) --
+    the un-normalised sums of w n.  The first four are ``render_rays``' own.  It has the ``render_fn`` signature of ``render_rays_sharded``
+    (bind ``q`` with functools.partial), which carries all seven over the ranks."""
+    outs = [[] for _ in range(7)]
+    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
+    for i in range(0, rays.shape[0], chunk):
+        o, ctx = engine.render_forward(model, renderer, rays[i:i + chunk], None, bool(white_bg), grad_heads=())
+        s = engine.surface_from_ctx(model, renderer, ctx, q)
+        for dst, x in zip(outs, (o["rgb"], o["semantics"], o["instances"], o["depth"].clone(), s["depth_median"], s["hit"].to(torch.float32),
+                                 s["normals"].contiguous())):
+            dst.append(x)
+        del ctx
+    return tuple(torch.cat(x, 0) for x in outs)
+
+
 def tile_bounds(n, world):
     """Contiguous row-tile boundaries of n rays over `world` ranks (sizes differ by at most one)."""
     return [(n * r) // world for r in range(world + 1)]

@@ -174,6 +174,14 @@ class TensoRFRenderer(nn.Module):
         params = [tensorf.get_parameter(n) for n in names]
         return _FeatureFn.apply(tensorf, self, rays, jitter, "semantic", names, *params)
 
+    # ------------------------------------------------------------------ surface outputs of the ray route
+    @torch.no_grad()
+    def forward_surface(self, tensorf, rays, q=0.5):
+        """Geometry of the rays without any head: dict(depth_median (N,), hit (N,) bool, k_median (N,) int32, normals (N,3) = sum_k w_k n_k
+        with n = -grad sigma_raw / |grad sigma_raw|, points (N,3) = o + depth_median d, depth (N,) = the expected distance, opacity (N,)).
+        No jitter (is_train False), no gradient."""
+        return engine.surface_forward(tensorf, self, rays, None, q)[0]
+
     # ------------------------------------------------------------------ scene edits (renderer.py:303-623)
     def _forward_edit(self, tensorf, rays, white_bg, resolved):
         out, _ = engine.edit_forward(tensorf, self, rays, resolved, white_bg)

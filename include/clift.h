@@ -776,6 +776,32 @@ int clift_iso_faces(const float* vol, int n0, int n1, int n2, float level, const
  * other than 6 / 14 / 26, a NULL buffer. */
 int clift_cc_label(const int* key, int n0, int n1, int n2, int connectivity, int* root, clift_stream_t s);
 
+/* ---- surface outputs of the ray route (a further ABI 27 addition; csrc/surface.hip).
+ *
+ * clift_density_grad_points: out (n, 4) fp32, row = [gx, gy, gz, sigma_raw] at the normalised points xn (n, ldx >= 3), where
+ *   sigma_raw(xn) = sum_i sum_c P_ic(xn[a_i], xn[b_i]) L_ic(xn[v_i]) + shift  is what clift_density_points(activation = 0) evaluates (column 3
+ *   carries its bits) and g = d sigma_raw / d xn is its analytic derivative inside the cell the lookup selects by floor: on a texel line the
+ *   right-sided derivative.  A tap outside the table counts as the value 0, so at the table's edge the derivative sees the step to the padding;
+ *   farther than one texel outside everything is 0.  h_inv2 (host, 3 floats; the inv_ext2 of clift_march_t) scales the gradient to world units,
+ *   g_a * inv2_a; NULL leaves it with respect to xn.
+ *   Errors: comps not a positive multiple of 4, a table size < 1, ldx < 3, n >= 2^36, a NULL buffer.  n <= 0 returns 0 without a launch.
+ *
+ * clift_ray_surface: per ray of a march (the record, rays and jitter of clift_march_fwd; T, w (N, S) as it wrote them; ray_start (N + 1) and
+ *   act_idx (M) of clift_scan_counts / clift_compact_fill; G (M, 4) = clift_density_grad_points at the active samples, world units), with
+ *   rem_k = T[k] - w[k] and thr = 1 - q, each one fp32 subtraction, q in (0, 1):
+ *     k_med[r] = min{k : rem_k <= thr}, or -1 (then depth_med[r] = 0);
+ *     depth_med[r] = z_k + f delta_k,  f = den > 0 ? clamp((prev - thr) / den, 0, 1) : 0,  den = prev - rem_k,  prev = rem_{k-1} (1 for k = 0),
+ *       z_k and delta_k = z_{k+1} - z_k (0 at k = S - 1) the march's own fp32 expressions;
+ *     normal[r] = [sum over the ray's active samples, in list order, of w_k n_k, 0],  n = -g / |g| where |g|^2 >= 1e-30, else 0: un-normalised,
+ *       its length is at most the opacity.
+ *   One wave per ray, no atomics: two runs give the same bits.  M = 0 (G and act_idx may be NULL) and rays without active samples are fine.
+ *   Errors: q outside (0, 1), S < 1, M < 0, N S >= 2^31 - 1, a NULL buffer.  N <= 0 returns 0 without a launch. */
+int clift_density_grad_points(const clift_vm_t* h_dens, const float* xn, int ldx, long n, float shift, const float* h_inv2, float* out,
+                              clift_stream_t s);
+int clift_ray_surface(const clift_march_t* h_m, const float* rays, const float* jitter, int N, const float* T, const float* w,
+                      const int* ray_start, const int* act_idx, int M, const float* G, float q, float* depth_med, int* k_med, float* normal,
+                      clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,

@@ -11,6 +11,11 @@ halves the step ratio (RP:104) and renders every test frame in chunks on the GPU
 ``vis_semantics_and_surrogate/*.png`` under ``runs/<scene>_<test|trajectory>_<experiment>/`` (RP:142-193).  With ``--save_pointcloud``
 also ``pointcloud.pkl``: every rendered pixel back-projected along its ray (RP:124) with its surrogate id, the input of
 ``inference/fit_bboxes.py`` and of the reference's ``inference/visualize_bboxes.py``.
+
+Surface outputs of the ray route (two more launches per chunk, only when asked for): ``--save_surface`` writes per frame
+``surface/<frame>.npz`` (depth_median, hit, normals) and ``vis_normals/<frame>.png``; ``--pointcloud_depth median`` back-projects to the
+median-depth hit point instead of the expected distance, drops the pixels whose ray never loses half its transmittance and adds their
+normals to ``pointcloud.pkl``.
 """
 import argparse
 import os
@@ -113,7 +118,11 @@ def scene_frames(scene, trajectory_name, test_only):
 
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
                               cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
-                              meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn"):
+                              meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn", save_surface=False, pointcloud_depth="expected"):
+    if pointcloud_depth not in ("expected", "median"):
+        raise ValueError(f"pointcloud_depth must be 'expected' or 'median', got {pointcloud_depth!r}")
+    median_cloud = bool(save_pointcloud) and pointcloud_depth == "median"
+    surface = bool(save_surface) or median_cloud
     out = output_dirname(config, trajectory_name, test_only, use_dbscan, segmentwise)
     out.mkdir(exist_ok=True, parents=True)
     device, rank = distributed_device(device)
@@ -122,13 +131,22 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
     fg = scene.segmentation_data.fg_classes
     rgbs, sems, depths, inst_feats, thing_feats, slow_feats, points = [], [], [], [], [], [], []
     names = []
+    hits, normals, depths_med = [], [], []
     with torch.no_grad():
         for name, rays, K_frame in scene_frames(scene, trajectory_name, test_only):
             names.append(name)
-            p_rgb, p_sem, p_inst, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg)
+            if surface:
+                p_rgb, p_sem, p_inst, p_dist, p_dmed, p_hit, p_nrm = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg,
+                                                                                            render_fn=inf.render_rays_surface)
+                hits.append(p_hit > 0.5)
+                normals.append(p_nrm.cpu())
+                depths_med.append(inf.distance_to_depth(K_frame, p_dmed.view(H, W)).cpu())
+            else:
+                p_rgb, p_sem, p_inst, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg)
             depths.append(inf.distance_to_depth(K_frame, p_dist.view(H, W)))
             if save_pointcloud:
-                points.append(points3d.backproject(rays, p_dist).float().cpu())
+                # (use_delta below keeps the expected distance for the instance features: only the saved points change)
+                points.append(points3d.backproject(rays, p_dmed if median_cloud else p_dist).float().cpu())
             if config.use_delta:
                 p_inst = p_inst + (rays[:, 0:3] + p_dist[:, None] * rays[:, 3:6])
             if model.slow_fast_mode:
@@ -169,12 +187,26 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
         d = (d - d.min()) / max(float(np.ptp(d)), 1e-8)
         vis = np.concatenate([rgbs[j].reshape(H, W, 3).cpu().numpy(), pal[sem_id], pal[sur_id], np.repeat(d[..., None], 3, -1)], 1)
         Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_semantics_and_surrogate" / name)
+    if save_surface:
+        for d in ("surface", "vis_normals"):
+            (out / d).mkdir(exist_ok=True)
+        for j, frame_name in enumerate(names):
+            hit = hits[j].reshape(H, W).cpu().numpy()
+            nrm = normals[j].reshape(H, W, 3).numpy().astype(np.float32)
+            np.savez(out / "surface" / f"{frame_name}.npz", depth_median=depths_med[j].reshape(H, W).numpy().astype(np.float32), hit=hit, normals=nrm)
+            unit = nrm / np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-20)
+            vis = np.where(hit[..., None], (unit + 1.0) * 0.5, 0.0)
+            Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_normals" / f"{frame_name}.png")
     if save_pointcloud:
         # the layout visualize_bboxes.py:269-275 loads: points (P, 3), instances (P,) = the ids written to pred_surrogateid (0 = stuff)
         cloud = {"points": torch.cat(points, 0).numpy().astype(np.float32),
                  "instances": torch.cat([i.argmax(dim=1) for i in insts], 0).cpu().numpy().astype(np.uint16),
                  "semantics": torch.cat([s.argmax(dim=1) for s in sems], 0).cpu().numpy().astype(np.uint8),
                  "rgb": (torch.cat(rgbs, 0).cpu().numpy().clip(0, 1) * 255).astype(np.uint8)}
+        if median_cloud:        # the hit points: rows whose ray has no hit leave every array alike, the normals come along
+            keep = torch.cat(hits, 0).cpu().numpy()
+            cloud = {k: v[keep] for k, v in cloud.items()}
+            cloud["normals"] = torch.cat(normals, 0).numpy().astype(np.float32)[keep]
         with open(out / "pointcloud.pkl", "wb") as f:
             pickle.dump(cloud, f)
     return out
@@ -201,6 +233,12 @@ if __name__ == "__main__":
                          "(DeviceHDBSCAN: clift_emst + the host tree pass, pinned to sklearn's estimator)")
     ap.add_argument("--save_pointcloud", action="store_true",
                     help="also write pointcloud.pkl (points, instances, semantics, rgb of every rendered pixel) for inference/fit_bboxes.py")
+    ap.add_argument("--save_surface", action="store_true",
+                    help="also write surface/<frame>.npz (depth_median, hit, normals) and vis_normals/<frame>.png: the median-depth hit and the "
+                         "composited field normal of every pixel's ray")
+    ap.add_argument("--pointcloud_depth", choices=("expected", "median"), default="expected",
+                    help="where --save_pointcloud puts a pixel's point: at the expected distance (the reference), or at the median-depth hit "
+                         "(pixels without a hit are dropped, a normals key is added)")
     args = ap.parse_args()
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
@@ -210,4 +248,5 @@ if __name__ == "__main__":
                                     use_dbscan=args.use_dbscan, segmentwise=args.segmentwise,
                                     cached_centroids_path=args.cached_centroids_path, use_silverman=args.use_silverman,
                                     cluster_size=args.cluster_size, meanshift=args.meanshift, hdbscan=args.hdbscan,
-                                    save_pointcloud=args.save_pointcloud))
+                                    save_pointcloud=args.save_pointcloud, save_surface=args.save_surface,
+                                    pointcloud_depth=args.pointcloud_depth))
