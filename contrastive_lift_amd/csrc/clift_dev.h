@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/clift.h"
+#include "row_ranges.h"
 
 #define CLIFT_WAVE 64
 
@@ -25,6 +26,8 @@ static inline bool clift_switch_off(unsigned bits) { return (clift_switches() & 
 
 static inline hipStream_t as_stream(clift_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// row ranges of a persistent launch over the CUs such launches may use (per_cu blocks on each)
+static inline RowRanges persistent_ranges(long rows, int ROWS, int per_cu = 1) { return row_ranges(rows, ROWS, clift_persistent_cus(), per_cu); }
 
 // ----------------------------------------------------------------------------- kernel-argument mirrors
 struct MarchP {

@@ -14,19 +14,10 @@
 //   trans operand (memory [k][row]): a thread takes the float4s of rows 4 m4 .. +3 at k = 2 kp and 2 kp + 1 and writes four
 //     packed k-pairs (4-byte stores); the lane -> (m4, kp) mapping puts the 32 lanes of a store group on 4 rows-of-four x 8
 //     k-pairs = 32 distinct banks, at the price of 64-byte (not 128-byte) global segments per k row.
-#include "gemm_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 constexpr int BKH = 32;     // k depth of one staged tile
 constexpr int LPD = 18;     // LDS row pitch in dwords (36 bf16)
-
-static __device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    bf16x2 p;
-    p[0] = (__bf16)lo; p[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, p);
-}
 
 template <int ROWS, int NT, bool TR>
 struct StagerH {
@@ -159,12 +150,12 @@ struct StagerH {
                 int a, b;
                 coords(e, a, b);
                 if (!TR) {
-                    *reinterpret_cast<uint2*>(L + a * LPD + (b >> 1)) = make_uint2(pack2(v[p].x, v[p].y), pack2(v[p].z, v[p].w));
+                    *reinterpret_cast<uint2*>(L + a * LPD + (b >> 1)) = make_uint2(pack_bf16_cast(v[p].x, v[p].y), pack_bf16_cast(v[p].z, v[p].w));
                 } else {
                     const float4 lo = v[2 * p], hi = v[2 * p + 1];
                     unsigned* q = L + a * LPD + (b >> 1);
-                    q[0] = pack2(lo.x, hi.x); q[LPD] = pack2(lo.y, hi.y);
-                    q[2 * LPD] = pack2(lo.z, hi.z); q[3 * LPD] = pack2(lo.w, hi.w);
+                    q[0] = pack_bf16_cast(lo.x, hi.x); q[LPD] = pack_bf16_cast(lo.y, hi.y);
+                    q[2 * LPD] = pack_bf16_cast(lo.z, hi.z); q[3 * LPD] = pack_bf16_cast(lo.w, hi.w);
                 }
             }
         }

@@ -16,19 +16,10 @@
 // fragment time: 4x redundant VALU work across the waves of a block row plus 32 spilled VGPRs made it slower than the exact
 // fp32 kernel.)  The wgrad form (both operands streamed, k-major) stays on the exact-fp32 kernel.
 // LDS per block (BK = 16): 3 x (128 + 256) x 40 B = 45 KB.
-#include "gemm_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 constexpr int BKS = 16;       // k depth of one staged tile = one bf16 MFMA k-step
 constexpr int PBD = 10;       // dword row pitch of a plane image (16 bf16 + 4 pad = 40 B: conflict-free ds_read_b64)
-
-static __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    bf16x2 p;
-    p[0] = (__bf16)lo; p[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, p);
-}
 
 // ---------------------------------------------------------------------------------------------- weight split (once per launch)
 // planes[p][n][k], p = 0 (leading) .. 2, n < Np, k < Kp; B(n,k) = b_trans ? B[k*ldb+n] : B[n*ldb+k]; zero outside N x K.
@@ -127,16 +118,16 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN >= 8 ? 4 : 1)) void k_gemm_s
             if (NEA % NT == 0 || e < NEA) {
                 // exact three-way split of 4 consecutive k, 8 bytes into each plane
                 const float a0 = va[p].x, a1 = va[p].y, a2 = va[p].z, a3 = va[p].w;
-                const unsigned h0 = pack_bf16(a0, a1), h1 = pack_bf16(a2, a3);
+                const unsigned h0 = pack_bf16_cast(a0, a1), h1 = pack_bf16_cast(a2, a3);
                 const float r0 = a0 - __uint_as_float(h0 << 16), r1 = a1 - __uint_as_float(h0 & 0xffff0000u);
                 const float r2 = a2 - __uint_as_float(h1 << 16), r3 = a3 - __uint_as_float(h1 & 0xffff0000u);
-                const unsigned m0_ = pack_bf16(r0, r1), m1_ = pack_bf16(r2, r3);
+                const unsigned m0_ = pack_bf16_cast(r0, r1), m1_ = pack_bf16_cast(r2, r3);
                 const float s0 = r0 - __uint_as_float(m0_ << 16), s1 = r1 - __uint_as_float(m0_ & 0xffff0000u);
                 const float s2 = r2 - __uint_as_float(m1_ << 16), s3 = r3 - __uint_as_float(m1_ & 0xffff0000u);
                 unsigned* q = lds_a + (e >> 2) * PBD + (e & 3) * 2;
                 *reinterpret_cast<uint2*>(q) = make_uint2(h0, h1);
                 *reinterpret_cast<uint2*>(q + LAP) = make_uint2(m0_, m1_);
-                *reinterpret_cast<uint2*>(q + 2 * LAP) = make_uint2(pack_bf16(s0, s1), pack_bf16(s2, s3));
+                *reinterpret_cast<uint2*>(q + 2 * LAP) = make_uint2(pack_bf16_cast(s0, s1), pack_bf16_cast(s2, s3));
             }
         }
 #pragma unroll

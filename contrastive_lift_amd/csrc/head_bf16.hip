@@ -13,12 +13,7 @@
 // Arithmetic is that of the per-layer path (fp32 K = 3 layer rounded to bf16, weights rounded to bf16 RNE on load, fp32 accumulate in
 // the same k order, bias + ReLU in fp32, activations rounded to bf16 between layers; the output layer multiplies the bf16-rounded h3
 // with bf16-rounded weights in fp32): results agree with it up to the summation order of the E-wide output layer.
-#include "gemm_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
+#include "mfma_dev.h"
 
 struct HeadP {
     const float* x4;                  // (M, 4) normalised positions
@@ -35,15 +30,6 @@ constexpr int HB_ROWS = 64;                  // rows per tile
 constexpr int HB_TILE = HB_ROWS * 32;        // uint4 per activation tile (64 rows x 512 B)
 constexpr int HB_XROWS = 2048;               // positions staged per refill
 
-static __device__ __forceinline__ bf16x8 hb_cvt8(const float4 a, const float4 b) {
-    bf16x8 r;
-    r[0] = (__bf16)a.x; r[1] = (__bf16)a.y; r[2] = (__bf16)a.z; r[3] = (__bf16)a.w;
-    r[4] = (__bf16)b.x; r[5] = (__bf16)b.y; r[6] = (__bf16)b.z; r[7] = (__bf16)b.w;
-    return r;
-}
-static __device__ __forceinline__ unsigned hb_pack(float lo, float hi) {
-    return (unsigned)float_to_bf16_bits(lo) | ((unsigned)float_to_bf16_bits(hi) << 16);
-}
 static __device__ __forceinline__ float hb_round(float v) { return bf16_bits_to_float(float_to_bf16_bits(v)); }
 
 __global__ __launch_bounds__(512, 2) void k_head_bf16_fwd(HeadP p, int rows_per_block) {
@@ -70,8 +56,8 @@ __global__ __launch_bounds__(512, 2) void k_head_bf16_fwd(HeadP p, int rows_per_
             const int k = 16 * s + 8 * lh;
             const float4* q1 = reinterpret_cast<const float4*>(p.W1 + (size_t)n * p.ldw1 + k);
             const float4* q2 = reinterpret_cast<const float4*>(p.W2 + (size_t)n * p.ldw2 + k);
-            w1[s] = hb_cvt8(q1[0], q1[1]);
-            w2[s] = hb_cvt8(q2[0], q2[1]);
+            w1[s] = cvt8(q1[0], q1[1]);
+            w2[s] = cvt8(q2[0], q2[1]);
         }
     }
     // ---- small operands in LDS (registers are taken by the weights): hidden-layer biases, first-layer coefficients
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(512, 2) void k_head_bf16_fwd(HeadP p, int rows_per_
             o[1] = fmaxf(fmaf(g1.z, x.z, fmaf(g1.y, x.y, fmaf(g1.x, x.x, g1.w))), 0.f);
             o[2] = fmaxf(fmaf(g2.z, x.z, fmaf(g2.y, x.y, fmaf(g2.x, x.x, g2.w))), 0.f);
             o[3] = fmaxf(fmaf(g3.z, x.z, fmaf(g3.y, x.y, fmaf(g3.x, x.x, g3.w))), 0.f);
-            const uint2 v = make_uint2(hb_pack(o[0], o[1]), hb_pack(o[2], o[3]));
+            const uint2 v = make_uint2(pack_bf16_bits(o[0], o[1]), pack_bf16_bits(o[2], o[3]));
             reinterpret_cast<uint2*>(buf0 + row * 32 + ((lane >> 1) ^ (row & 15)))[lane & 1] = v;
             if (p.h1 && r0 + row < rend) *reinterpret_cast<uint2*>(p.h1 + (size_t)gr * 256 + 4 * lane) = v;
         }
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void k_head_bf16_fwd(HeadP p, int rows_per_
                     float v[4];
                     v[0] = fmaxf(acc[x][4 * q + 0] + bq.x, 0.f); v[1] = fmaxf(acc[x][4 * q + 1] + bq.y, 0.f);
                     v[2] = fmaxf(acc[x][4 * q + 2] + bq.z, 0.f); v[3] = fmaxf(acc[x][4 * q + 3] + bq.w, 0.f);
-                    const uint2 pk = make_uint2(hb_pack(v[0], v[1]), hb_pack(v[2], v[3]));
+                    const uint2 pk = make_uint2(pack_bf16_bits(v[0], v[1]), pack_bf16_bits(v[2], v[3]));
                     if (layer == 0) reinterpret_cast<uint2*>(D + row * 32 + ((4 * wave + q) ^ (row & 15)))[lh] = pk;      // next layer's operand tile
                     if (hs && m < rend) *reinterpret_cast<uint2*>(hs + (size_t)m * 256 + 32 * wave + 8 * q + 4 * lh) = pk;
                     if (layer == 1 && p.E > 0) {          // output layer on the bf16-rounded activation: this lane's share of the E sums of row `row`
@@ -206,9 +192,7 @@ extern "C" int clift_xyz_head_bf16_fwd(const float* x4, const float* W0, int ldw
     CLIFT_REQUIRE(((((uintptr_t)h1) | ((uintptr_t)h2) | ((uintptr_t)h3)) & 7) == 0, "clift_xyz_head_bf16_fwd: activation destinations must be 8-byte aligned");
     HeadP p = {x4, W0, ldw0, b0, W1, ldw1, b1, W2, ldw2, b2, Wout, ldwo, bout, E, out, ldo,
                reinterpret_cast<unsigned short*>(h1), reinterpret_cast<unsigned short*>(h2), reinterpret_cast<unsigned short*>(h3), M};
-    const int tiles = cdiv(M, HB_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), HB_ROWS) * HB_ROWS;
-    k_head_bf16_fwd<<<cdiv(M, rpb), 512, 0, as_stream(s)>>>(p, rpb);
+    const RowRanges r = persistent_ranges(M, HB_ROWS);
+    k_head_bf16_fwd<<<r.grid, 512, 0, as_stream(s)>>>(p, r.rpb);
     return clift_check_launch("clift_xyz_head_bf16_fwd");
 }

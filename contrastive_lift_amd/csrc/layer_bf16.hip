@@ -14,33 +14,12 @@
 //     lands in slot c ^ (r & 15), which makes the ds_read_b128 fragment reads (16 consecutive rows, same k) conflict-free;
 //   * operands swapped in the MFMA (weights first): a lane owns one output row; v_permlane32_swap pairs the two half-waves'
 //     4-column groups into 8 consecutive bf16 so that every store / mask read is 16 bytes per lane.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_bf16)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4k __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int LY_ROWS = 64;                 // rows per streamed tile (two 32-row MFMA tiles per wave)
 constexpr int LY_TILE = LY_ROWS * 32;       // uint4 per tile: 64 rows x 512 B
 
-static __device__ __forceinline__ bf16x8 cvt8(const float4 a, const float4 b) {
-    bf16x8 r;
-    r[0] = (__bf16)a.x; r[1] = (__bf16)a.y; r[2] = (__bf16)a.z; r[3] = (__bf16)a.w;
-    r[4] = (__bf16)b.x; r[5] = (__bf16)b.y; r[6] = (__bf16)b.z; r[7] = (__bf16)b.w;
-    return r;
-}
-static __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    return (unsigned)float_to_bf16_bits(lo) | ((unsigned)float_to_bf16_bits(hi) << 16);
-}
-static __device__ __forceinline__ unsigned keep_positive(unsigned v, unsigned mk) {      // per 16-bit half: v where the mask half is > 0
-    const unsigned lo = bf16_bits_positive((unsigned short)(mk & 0xffffu)) ? 0x0000ffffu : 0u;
-    const unsigned hi = bf16_bits_positive((unsigned short)(mk >> 16)) ? 0xffff0000u : 0u;
-    return v & (lo | hi);
-}
-template <int N>
-static __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 static __device__ __forceinline__ void wait_vm_upto(int n) {       // wave-uniform n, a multiple of 4 (everything here issues in fours)
     if (n >= 36) wait_vm<36>();
     else if (n >= 32) wait_vm<32>();
@@ -171,7 +150,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_bf16(GemmP g, int rows_per_blo
                          : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3])
                          : "memory");
         }
-        f32x4k px0, px1;
+        f32x4 px0, px1;
         if (K3W) {                           // this lane's two rows' positions, from the tile's position slot (inline asm for the reason given at the mask reads)
             const unsigned pa = (unsigned)(uintptr_t)(lds_ptr_t)(lds + NST * STAGE + (t % NST) * LY_ROWS + li);
             asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:512\n\ts_waitcnt lgkmcnt(0)" : "=&v"(px0), "=&v"(px1) : "v"(pa) : "memory");
@@ -191,8 +170,8 @@ __global__ __launch_bounds__(512, 2) void k_layer_bf16(GemmP g, int rows_per_blo
                         v[e] = acc[x][4 * q + e] + bias[4 * q + e];
                         if (!DGRAD && g.act == 1) v[e] = fmaxf(v[e], 0.f);
                     }
-                    (h ? P1 : P0)[0] = pack_bf16(v[0], v[1]);
-                    (h ? P1 : P0)[1] = pack_bf16(v[2], v[3]);
+                    (h ? P1 : P0)[0] = pack_bf16_bits(v[0], v[1]);
+                    (h ? P1 : P0)[1] = pack_bf16_bits(v[2], v[3]);
                 }
                 const u32x2 s0 = __builtin_amdgcn_permlane32_swap(P0[0], P1[0], false, false);
                 const u32x2 s1 = __builtin_amdgcn_permlane32_swap(P0[1], P1[1], false, false);
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_bf16(GemmP g, int rows_per_blo
                 }
                 if (K3W) {
                     if (m < rend) {              // rows past the range are copies of its last row: they count for nothing
-                        const f32x4k p = x ? px1 : px0;
+                        const f32x4 p = x ? px1 : px0;
                         const unsigned ow[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
                         for (int c = 0; c < 8; ++c) {
@@ -282,13 +261,6 @@ int clift_layer_bf16_launch(const GemmP& p, int b_trans, hipStream_t st) {
 // Swizzle (at the DMA source, the image being lane-linear): 16-byte chunk c of row r sits in slot c ^ ((r & 3) << 2), so the four
 // rows of a transposed read land in four different 64-byte bank spans.  All LDS reads are inline asm (see the mask reads above).
 // The partial products are added to gW with fp32 atomics at the end (the same count as the split-K launch this replaces).
-static __device__ __forceinline__ uint2 tr_read(unsigned addr) {
-    uint2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-static __device__ __forceinline__ float bf16_pair_sum(unsigned u) { return __uint_as_float(u << 16) + __uint_as_float(u & 0xffff0000u); }
-
 __global__ __launch_bounds__(512, 2) void k_wgrad_bf16_stream(GemmP g, int rows_per_block) {
     asm volatile("v_mov_b32 v255, 0" ::: "v255");       // register ballast (csrc/layer_x6w.hip): nothing else is scheduled onto this SIMD beside the bf16 MFMA stream
     constexpr int STAGE = 2 * LY_TILE;                                        // uint4 per stage: dY tile then X tile
@@ -402,10 +374,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_bf16_stream(GemmP g, int rows_
 int clift_wgrad_bf16_stream2d_launch(const GemmP& p, hipStream_t st);
 int clift_wgrad_bf16_stream_launch(const GemmP& p, hipStream_t st) {
     if (p.K >= 4096) return clift_wgrad_bf16_stream2d_launch(p, st);      // 64 row ranges x 4 column slices
-    const int tiles = cdiv(p.K, LY_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(p.K, blocks), LY_ROWS) * LY_ROWS;
-    k_wgrad_bf16_stream<<<cdiv(p.K, rpb), 512, 0, st>>>(p, rpb);
+    const RowRanges r = persistent_ranges(p.K, LY_ROWS);
+    k_wgrad_bf16_stream<<<r.grid, 512, 0, st>>>(p, r.rpb);
     return clift_check_launch("clift_gemm(bf16 wgrad stream)");
 }
 

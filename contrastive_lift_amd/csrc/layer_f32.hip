@@ -23,17 +23,11 @@
 // All LDS reads and the mask loads are inline asm: beside an in-flight LDS-DMA the compiler guards ordinary reads of the array /
 // ordinary global loads with s_waitcnt vmcnt(0), which would drain the prefetched tile and the output stores; each asm wait is
 // tied to the registers it guards as a data dependency, and sched_barriers pin the read-ahead order.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_f32)
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LF_ROWS = 32;                  // rows per streamed tile
 constexpr int LF_TILE = LF_ROWS * 64;        // float4 per tile: 32 rows x 1 KB
-
-template <int N>
-static __device__ __forceinline__ void wait_vmf() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // GEN (forward only): the layer's input is not read from memory but GENERATED -- it is the first layer of an xyz head,
 // A[m][c] = relu(W0[c] . x_m + b0[c]) with K = 3 (tensoRF.py:475,576), i.e. 13 VALU instructions per 16 bytes where the streamed
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_f32(GemmP g, int rows_per_bloc
             w[j] = make_float4(q[0], q[ld], q[2 * ld], q[3 * ld]);
         }
     }
-    wait_vmf<0>();
+    wait_vm<0>();
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)lds;
     // GEN: this lane's first-layer coefficients (columns 4 lane .. +3)
     float gw0[4], gw1[4], gw2[4], gbb[4];
@@ -178,7 +172,6 @@ __global__ __launch_bounds__(512, 2) void k_layer_f32(GemmP g, int rows_per_bloc
         __syncthreads();
     }
     auto outv_tile = [&](int tile) {
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         float po[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -250,7 +243,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_f32(GemmP g, int rows_per_bloc
             // end of tile t-1 for its mask)
             // (K3W: no stores, no mask loads -- the tile's DMAs are all there is; OUTV without a hidden store: the only younger instructions are the owner
             // threads' output stores, which most waves never issue)
-            if (t >= 2 && !K3W && (!OUTV || op.store_hidden)) wait_vmf<4>(); else wait_vmf<0>();
+            if (t >= 2 && !K3W && (!OUTV || op.store_hidden)) wait_vm<4>(); else wait_vm<0>();
             __builtin_amdgcn_s_barrier();                                    // everyone's rows have landed; everyone is done with the other stage
             asm volatile("" ::: "memory");
         } else {
@@ -366,13 +359,11 @@ __global__ __launch_bounds__(512, 2) void k_layer_f32(GemmP g, int rows_per_bloc
 // Eligibility is decided by the caller (gemm.hip): N = K = 256, plain row-major A, 16-byte-aligned rows; forward: [n][k] weights,
 // no mask; dgrad (b_trans): [k][n] weights, fp32 mask, no bias / activation.
 int clift_layer_f32_launch(const GemmP& p, int b_trans, hipStream_t st) {
-    const int tiles = cdiv(p.M, LF_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();                    // one persistent block per CU
-    const int rpb = cdiv(cdiv(p.M, blocks), LF_ROWS) * LF_ROWS;
+    const RowRanges r = persistent_ranges(p.M, LF_ROWS);
     const GenP none = {nullptr, nullptr, 0, nullptr, nullptr, 0};
     const OutP no_out = {nullptr, 0, nullptr, 0, nullptr, 0, 1};
-    if (b_trans) k_layer_f32<true, false, false><<<cdiv(p.M, rpb), 512, 0, st>>>(p, rpb, none, no_out, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
-    else k_layer_f32<false, false, false><<<cdiv(p.M, rpb), 512, 0, st>>>(p, rpb, none, no_out, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
+    if (b_trans) k_layer_f32<true, false, false><<<r.grid, 512, 0, st>>>(p, r.rpb, none, no_out, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
+    else k_layer_f32<false, false, false><<<r.grid, 512, 0, st>>>(p, r.rpb, none, no_out, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
     return clift_check_launch("clift_gemm(fp32 layer)");
 }
 
@@ -387,12 +378,10 @@ extern "C" int clift_xyz_head_last2_fwd(const float* A, int lda, const float* W,
     CLIFT_REQUIRE(hidden == nullptr || ((((uintptr_t)hidden) & 15) == 0 && ldh % 4 == 0 && ldh >= 256), "clift_xyz_head_last2_fwd: hidden must be 16-byte aligned, pitch >= 256");
     GemmP p = {};
     p.M = M; p.N = 256; p.K = 256; p.A = A; p.lda = lda; p.B = W; p.ldb = ldw; p.C = hidden; p.ldc = ldh; p.bias = b; p.act = 1;
-    const int tiles = cdiv(M, LF_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), LF_ROWS) * LF_ROWS;
+    const RowRanges r = persistent_ranges(M, LF_ROWS);
     const GenP none = {nullptr, nullptr, 0, nullptr, nullptr, 0};
     const OutP op = {Wout, ldwo, bout, E, out, ldo, hidden != nullptr ? 1 : 0};
-    k_layer_f32<false, false, true><<<cdiv(M, rpb), 512, 0, as_stream(s)>>>(p, rpb, none, op, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
+    k_layer_f32<false, false, true><<<r.grid, 512, 0, as_stream(s)>>>(p, r.rpb, none, op, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
     return clift_check_launch("clift_xyz_head_last2_fwd");
 }
 
@@ -407,12 +396,10 @@ extern "C" int clift_xyz_head_first2_fwd(const float* x4, const float* W0, int l
     CLIFT_REQUIRE(h1 == nullptr || ((((uintptr_t)h1) & 15) == 0 && ldh1 % 4 == 0 && ldh1 >= 256), "clift_xyz_head_first2_fwd: h1 must be 16-byte aligned, pitch >= 256");
     GemmP p = {};
     p.M = M; p.N = 256; p.K = 256; p.A = nullptr; p.lda = 256; p.B = W1; p.ldb = ldw1; p.C = h2; p.ldc = ldh2; p.bias = b1; p.act = 1;
-    const int tiles = cdiv(M, LF_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), LF_ROWS) * LF_ROWS;
+    const RowRanges r = persistent_ranges(M, LF_ROWS);
     const GenP gp = {x4, W0, ldw0, b0, h1, ldh1};
     const OutP no_out = {nullptr, 0, nullptr, 0, nullptr, 0, 1};
-    k_layer_f32<false, true, false><<<cdiv(M, rpb), 512, 0, as_stream(s)>>>(p, rpb, gp, no_out, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
+    k_layer_f32<false, true, false><<<r.grid, 512, 0, as_stream(s)>>>(p, r.rpb, gp, no_out, K3P{nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr});
     return clift_check_launch("clift_xyz_head_first2_fwd");
 }
 
@@ -430,11 +417,9 @@ extern "C" int clift_xyz_head_first2_bwd(const float* dH2, int ldd, const float*
                   "clift_xyz_head_first2_bwd: W0 / gW0 (256 x 3, pitch >= 3) and b0 / gb0 (256) are required");
     GemmP p = {};
     p.M = M; p.N = 256; p.K = 256; p.A = dH2; p.lda = ldd; p.B = W1; p.ldb = ldw1; p.C = nullptr; p.ldc = 256;
-    const int tiles = cdiv(M, LF_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), LF_ROWS) * LF_ROWS;
+    const RowRanges r = persistent_ranges(M, LF_ROWS);
     const GenP none = {nullptr, nullptr, 0, nullptr, nullptr, 0};
     const OutP no_out = {nullptr, 0, nullptr, 0, nullptr, 0, 1};
-    k_layer_f32<true, false, false, true><<<cdiv(M, rpb), 512, 0, as_stream(s)>>>(p, rpb, none, no_out, K3P{x4, W0, ldw0, b0, gW0, ldgw0, gb0});
+    k_layer_f32<true, false, false, true><<<r.grid, 512, 0, as_stream(s)>>>(p, r.rpb, none, no_out, K3P{x4, W0, ldw0, b0, gW0, ldgw0, gb0});
     return clift_check_launch("clift_xyz_head_first2_bwd");
 }

@@ -12,16 +12,10 @@
 // LDS image: lane-linear (DMA); 16-byte chunk c of row r sits in slot c ^ (r & 7) of its row (low three bits only, so that a
 // 40-chunk row keeps the permutation inside its 8-chunk groups); a ds_read_b128 pass of 16 lanes (rows r .. r+15, one chunk index)
 // then touches every bank exactly twice -- the minimum for 256 bytes.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_n128)
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int LN_ROWS = 64;                  // rows per streamed tile (two 32-row halves)
-
-template <int N>
-static __device__ __forceinline__ void wait_vmn() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // OUTV (forward, KC = 32): the layer is the last hidden layer of the appearance MLP and the 3-wide output layer + sigmoid
 // (tensoRF.py:395-397,410) is applied to the tile while it is in registers: every lane holds 16 values of its row, 4 x 16 FMAs give its
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_n128(GemmP g, int rows_per_blo
             w[j] = make_float4(q[0], q[ld], q[2 * ld], q[3 * ld]);
         }
     }
-    wait_vmn<0>();
+    wait_vm<0>();
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)lds;
     const int rt = 32 * wr + li;                                             // this lane's row inside a tile
     unsigned off4[4];         // slot of chunk 2 jj + lh of this lane's row inside its 8-chunk group
@@ -110,7 +104,6 @@ __global__ __launch_bounds__(512, 2) void k_layer_n128(GemmP g, int rows_per_blo
         __syncthreads();
     }
     auto outv_tile = [&](int tile) {
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         float po[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_n128(GemmP g, int rows_per_blo
     for (int t = 0; t < ntiles; ++t) {
         // DMA of tile t was issued during tile t-1; younger than it: the 4 stores of tile t-2 (the dgrad drained everything for its mask)
         // (OUTV without a hidden store: the only younger instructions are the owner threads' output stores, which half of the waves never issue)
-        if (t >= 2 && (!OUTV || op.store_hidden)) wait_vmn<4>(); else wait_vmn<0>();
+        if (t >= 2 && (!OUTV || op.store_hidden)) wait_vm<4>(); else wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const int m = rbeg + t * LN_ROWS + rt;
@@ -217,10 +210,9 @@ __global__ __launch_bounds__(512, 2) void k_layer_n128(GemmP g, int rows_per_blo
 // Eligibility is decided by the caller (gemm.hip): N = 128, K in {128, 160} with lda >= K (pad columns of A and of the weight rows
 // are zero), plain row-major A, 16-byte-aligned rows; forward: [n][k] weights; dgrad (b_trans): [k][n] weights, fp32 mask (required).
 int clift_layer_n128_launch(const GemmP& p, int b_trans, hipStream_t st) {
-    const int tiles = cdiv(p.M, LN_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(p.M, blocks), LN_ROWS) * LN_ROWS;
-    const dim3 grid(cdiv(p.M, rpb));
+    const RowRanges r = persistent_ranges(p.M, LN_ROWS);
+    const int rpb = r.rpb;
+    const dim3 grid(r.grid);
     const OutN no_out = {nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, 1};
     if (p.K == 160 && !b_trans) k_layer_n128<40, false, false><<<grid, 512, 0, st>>>(p, rpb, no_out);
     else if (p.K == 128 && !b_trans) k_layer_n128<32, false, false><<<grid, 512, 0, st>>>(p, rpb, no_out);
@@ -241,11 +233,9 @@ extern "C" int clift_app_head_last2_fwd(const float* A, int lda, const float* W,
     CLIFT_REQUIRE(hidden == nullptr || ((((uintptr_t)hidden) & 15) == 0 && ldh % 4 == 0 && ldh >= 128), "clift_app_head_last2_fwd: hidden must be 16-byte aligned, pitch >= 128");
     GemmP p = {};
     p.M = M; p.N = 128; p.K = 128; p.A = A; p.lda = lda; p.B = W; p.ldb = ldw; p.C = hidden; p.ldc = ldh; p.bias = b; p.act = 1;
-    const int tiles = cdiv(M, LN_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), LN_ROWS) * LN_ROWS;
+    const RowRanges r = persistent_ranges(M, LN_ROWS);
     const OutN op = {Wout, ldwo, bout, E, pre, ldp, out, ldo, sigmoid, hidden != nullptr ? 1 : 0};
-    k_layer_n128<32, false, true><<<cdiv(M, rpb), 512, 0, as_stream(s)>>>(p, rpb, op);
+    k_layer_n128<32, false, true><<<r.grid, 512, 0, as_stream(s)>>>(p, r.rpb, op);
     return clift_check_launch("clift_app_head_last2_fwd");
 }
 
@@ -317,7 +307,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_n128_stream(GemmP g, int rows_
         for (int i = 0; i < (GENX ? 4 : 4 + NDX); ++i) dma_piece(t, i);
     };
     // ---- GENX: this lane's first-layer coefficients (columns 128 (quad & 1) + 4 (lane & 31) .. +3) and the position ring
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     float gw0[4] = {0.f, 0.f, 0.f, 0.f}, gw1[4] = {0.f, 0.f, 0.f, 0.f}, gw2[4] = {0.f, 0.f, 0.f, 0.f}, gbb[4] = {0.f, 0.f, 0.f, 0.f};
     if (GENX) {
 #pragma unroll
@@ -355,7 +344,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_n128_stream(GemmP g, int rows_
     for (int x = 0; x < NT; ++x)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x2 bsum2 = {0.f, 0.f};
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)lds;
     const unsigned yoff = (unsigned)(lh * 512 + (32 * wn + li) * 4);                           // dY element (row lh, column 32 wn + li)
@@ -448,7 +436,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_n128_stream(GemmP g, int rows_
         }
     }
     if (g.colsum && wk == 0 && (quad & 1) == 0) {      // (one of the two quadrants that saw these dY columns adds the bias gradient)
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         const unsigned u = __float_as_uint(bsum2[0] + bsum2[1]);
         const u32x2 sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
         const float tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);

@@ -12,41 +12,16 @@
 //   k_wgrad_n6<KT>                           gW (128, 32 KT) += dY^T X, gb += column sums of dY
 // Forward / dgrad: wave = one 32-column group of the output, 32-row tiles.  The rows of a tile are loaded as 16-byte pieces into registers one
 // tile ahead (coalesced: lane = piece), split by whoever loaded them (cooperative: each value is split ONCE per workgroup, 22 VALU per piece)
-// and written as three bf16 plane images into LDS (two stages; the image and its bank swizzle are layer_nb16.hip's: 16-byte chunk c of row r in
+// and written as three bf16 plane images into LDS (two stages; the image is layer_nb16.hip's, its bank swizzle bank_sw<KCH> of mfma_dev.h: 16-byte chunk c of row r in
 // slot c ^ (r & 15) for 256-byte rows, c ^ ((r >> 2) & 3) for 320-byte rows); every wave then reads whole-K fragments of the tile against its
 // register-resident weight planes (reading them a whole k-step ahead of their MFMAs instead of where the compiler puts them measured the same or
 // slower: profiles/r05_n6_prefetch_variant.txt).  One barrier per tile.  Two workgroups per CU (60 / 48 KB of LDS each) overlap one's split with the other's MFMAs.
 // A row's bits depend on nothing but the row: fixed k order, fixed column partition -- a frame rendered in row tiles is bit-identical to the
 // unsharded render.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_n6)
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int N6_ROWS = 32;
-
-static __device__ __forceinline__ unsigned n6_pk(float lo, float hi) {         // two fp32 -> packed bf16 (RNE), `lo` in the low half
-    bf16x2 p;
-    p[0] = (__bf16)lo; p[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, p);
-}
-static __device__ __forceinline__ float n6_lo(unsigned p) { return __uint_as_float(p << 16); }
-static __device__ __forceinline__ float n6_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-// exact three-way split of a pair (x = h + m + l, each term a bf16): the arithmetic of layer_x6.hip's x6_split_pair
-static __device__ __forceinline__ void n6_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = n6_pk(a, b);
-    const float ra = a - n6_lo(h), rb = b - n6_hi(h);
-    m = n6_pk(ra, rb);
-    l = n6_pk(ra - n6_lo(m), rb - n6_hi(m));
-}
-static __device__ __forceinline__ f32x16 n6_mfma(const u32x4& w, const u32x4& a, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
-}
-template <int KCH>
-static __device__ __forceinline__ int n6_sw(int r) { return KCH == 16 ? (r & 15) : ((r >> 2) & 3); }
 
 // The fused output layer of the forward form (OUTV): the layer is the LAST hidden layer (128 -> 128) and the E <= 4 wide output layer +
 // sigmoid (tensoRF.py:397,410) is applied to the finished tile in exact fp32 FMAs: a lane holds 16 columns of its row, 16 x E FMAs give its
@@ -108,7 +83,7 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_n6(GemmP g, int rows_per_
 #pragma unroll
             for (int pr = 0; pr < 4; ++pr) {
                 unsigned h, m, l;
-                n6_split_pair(v[2 * pr], v[2 * pr + 1], h, m, l);
+                split3_pair(v[2 * pr], v[2 * pr + 1], h, m, l);
                 wh[s][pr] = h; wm[s][pr] = m; wl[s][pr] = l;
             }
         }
@@ -136,7 +111,7 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_n6(GemmP g, int rows_per_
     for (int i = 0; i < PER; ++i) {
         const int p = tid + NT * i, row = p / C4, c4 = p - row * C4;
         prow[i] = row;
-        pofs[i] = row * (KCH * 16) + ((((c4 >> 1) ^ n6_sw<KCH>(row)) << 4) | ((c4 & 1) << 3));
+        pofs[i] = row * (KCH * 16) + ((((c4 >> 1) ^ bank_sw<KCH>(row)) << 4) | ((c4 & 1) << 3));
     }
     float4 P[PER];
     // (addresses = a wave-uniform base of the block's row range + a 32-bit byte offset: two VALU per piece instead of the 64-bit multiply-add chain;
@@ -156,8 +131,8 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_n6(GemmP g, int rows_per_
     auto split_store = [&](int stage, int i) {
         if (NPIECE % NT != 0 && tid + NT * i >= NPIECE) return;
         unsigned h0, m0, l0, h1, m1, l1;
-        n6_split_pair(P[i].x, P[i].y, h0, m0, l0);
-        n6_split_pair(P[i].z, P[i].w, h1, m1, l1);
+        split3_pair(P[i].x, P[i].y, h0, m0, l0);
+        split3_pair(P[i].z, P[i].w, h1, m1, l1);
         unsigned char* d = lb + stage * (STAGE * 16) + pofs[i];
         *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
         *reinterpret_cast<u32x2*>(d + PLANE * 16) = u32x2{m0, m1};
@@ -188,7 +163,7 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_n6(GemmP g, int rows_per_
         for (int r = 0; r < 16; ++r) { acc0[r] = bias[r]; acc1[r] = 0.f; }     // (the bias rides in the first chain's start: sixteen adds fewer per tile)
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            const int ci = li * KCH + ((2 * s + lh) ^ n6_sw<KCH>(li));
+            const int ci = li * KCH + ((2 * s + lh) ^ bank_sw<KCH>(li));
             const u32x4 fh = __builtin_bit_cast(u32x4, T[ci]);
             const u32x4 fm = __builtin_bit_cast(u32x4, T[PLANE + ci]);
             const u32x4 fl = __builtin_bit_cast(u32x4, T[2 * PLANE + ci]);
@@ -198,12 +173,12 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_n6(GemmP g, int rows_per_
                 split_store(nxt, s / 2);
                 fetch(t + 2, s / 2);
             }
-            acc0 = n6_mfma(wh[s], fh, acc0);
-            acc1 = n6_mfma(wh[s], fm, acc1);
-            acc0 = n6_mfma(wm[s], fm, acc0);
-            acc1 = n6_mfma(wm[s], fh, acc1);
-            acc0 = n6_mfma(wh[s], fl, acc0);
-            acc1 = n6_mfma(wl[s], fh, acc1);
+            acc0 = mfma_bf16(wh[s], fh, acc0);
+            acc1 = mfma_bf16(wh[s], fm, acc1);
+            acc0 = mfma_bf16(wm[s], fm, acc0);
+            acc1 = mfma_bf16(wm[s], fh, acc1);
+            acc0 = mfma_bf16(wh[s], fl, acc0);
+            acc1 = mfma_bf16(wl[s], fh, acc1);
         }
         // epilogue: lane (li, lh) holds row li of the tile, columns 32 wave + 8 q + 4 lh + (0..3) for q = 0..3
         float v[16];
@@ -252,23 +227,15 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_n6(GemmP g, int rows_per_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the fetches past the last tile were issued unconditionally: a wave does not end with loads in flight
 }
 
-static int n6_grid(int M, int per_cu, int& rpb) {
-    const int tiles = cdiv(M, N6_ROWS);
-    const int want = per_cu * clift_persistent_cus();
-    const int blocks = tiles < want ? tiles : want;
-    rpb = cdiv(cdiv(M, blocks), N6_ROWS) * N6_ROWS;
-    return cdiv(M, rpb);
-}
-
 // Eligibility is decided by the caller (gemm.hip): fp32 row-major A with 16-byte-aligned rows; forward: [n][k] weights, bias, ReLU, no mask;
 // dgrad (b_trans): [k][n] weights, fp32 mask (N = 128) or none (N = 160), no bias / activation.
 int clift_layer_n6_launch(const GemmP& p, int b_trans, hipStream_t st) {
-    int rpb;
     const N6Out none = {nullptr, 0, nullptr, 0, nullptr, 0, 0, 1};
-    if (!b_trans && p.K == 160) { const int grid = n6_grid(p.M, 2, rpb); k_layer_n6<10, 4, false, false, false><<<grid, 256, 0, st>>>(p, rpb, none); }
-    else if (!b_trans && p.K == 128) { const int grid = n6_grid(p.M, 2, rpb); k_layer_n6<8, 4, false, false, false><<<grid, 256, 0, st>>>(p, rpb, none); }
-    else if (b_trans && p.N == 128 && p.mask) { const int grid = n6_grid(p.M, 2, rpb); k_layer_n6<8, 4, true, true, false><<<grid, 256, 0, st>>>(p, rpb, none); }
-    else if (b_trans && p.N == 160 && !p.mask) { const int grid = n6_grid(p.M, 1, rpb); k_layer_n6<8, 5, true, false, false><<<grid, 320, 0, st>>>(p, rpb, none); }
+    const RowRanges r2 = persistent_ranges(p.M, N6_ROWS, 2), r1 = persistent_ranges(p.M, N6_ROWS, 1);      // the four-wave forms run two blocks per CU
+    if (!b_trans && p.K == 160) k_layer_n6<10, 4, false, false, false><<<r2.grid, 256, 0, st>>>(p, r2.rpb, none);
+    else if (!b_trans && p.K == 128) k_layer_n6<8, 4, false, false, false><<<r2.grid, 256, 0, st>>>(p, r2.rpb, none);
+    else if (b_trans && p.N == 128 && p.mask) k_layer_n6<8, 4, true, true, false><<<r2.grid, 256, 0, st>>>(p, r2.rpb, none);
+    else if (b_trans && p.N == 160 && !p.mask) k_layer_n6<8, 5, true, false, false><<<r1.grid, 320, 0, st>>>(p, r1.rpb, none);
     else { clift_set_error("clift_gemm(fp32x6 128-wide layer): no such form"); return 1; }
     return clift_check_launch("clift_gemm(fp32x6 128-wide layer)");
 }
@@ -286,9 +253,8 @@ extern "C" int clift_app_head_last2_x6_fwd(const float* A, int lda, const float*
     GemmP p = {};
     p.M = M; p.N = 128; p.K = 128; p.A = A; p.lda = lda; p.B = W; p.ldb = ldw; p.C = hidden; p.ldc = ldh; p.bias = b; p.act = 1;
     const N6Out op = {Wout, ldwo, bout, E, out, ldo, sigmoid, hidden ? 1 : 0};
-    int rpb;
-    const int grid = n6_grid(M, 2, rpb);
-    k_layer_n6<8, 4, false, false, true><<<grid, 256, 0, as_stream(s)>>>(p, rpb, op);
+    const RowRanges r = persistent_ranges(M, N6_ROWS, 2);
+    k_layer_n6<8, 4, false, false, true><<<r.grid, 256, 0, as_stream(s)>>>(p, r.rpb, op);
     return clift_check_launch("clift_app_head_last2_x6_fwd");
 }
 
@@ -299,15 +265,6 @@ extern "C" int clift_app_head_last2_x6_fwd(const float* A, int lda, const float*
 // (ds_read_b64_tr_b16: both MFMA operands are COLUMNS of the row-major tiles) are used here once per bf16 plane.  32-row tiles, two stages; the
 // rows arrive through registers one tile ahead and are split by whoever loaded them, as in k_layer_n6; rows past the end of the range are
 // zeroed in the split (a clamped copy would be counted twice).
-template <int OFF>
-static __device__ __forceinline__ uint2 n6_tr_read(unsigned addr) {          // (the constant part of the address rides in the instruction's offset field)
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-    uint2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-    return r;
-}
-typedef __attribute__((address_space(3))) void* n6_lds_ptr_t;
-
 template <int KT>
 __global__ __launch_bounds__(512, 1) void k_wgrad_n6(GemmP g, int rows_per_block) {
     constexpr int XCH = 4 * KT;                          // 16-byte chunks per row of an X plane image
@@ -367,8 +324,8 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_n6(GemmP g, int rows_per_block
     auto put = [&](int stage, int ofs, int pl_bytes, float4 v, bool live) {
         if (!live) v = make_float4(0.f, 0.f, 0.f, 0.f);
         unsigned h0, m0, l0, h1, m1, l1;
-        n6_split_pair(v.x, v.y, h0, m0, l0);
-        n6_split_pair(v.z, v.w, h1, m1, l1);
+        split3_pair(v.x, v.y, h0, m0, l0);
+        split3_pair(v.z, v.w, h1, m1, l1);
         unsigned char* d = lds + stage * STAGE + ofs;
         *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
         *reinterpret_cast<u32x2*>(d + pl_bytes) = u32x2{m0, m1};
@@ -391,7 +348,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_n6(GemmP g, int rows_per_block
         for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
     // lane-constant fragment addresses (bytes), as in k_wgrad_nb16: row 8 lh + ((lane & 15) >> 2) of a 16-row step, 4-chunk group by column tile
     const int s4 = (lane >> 2) & 3;                      // row & 3
-    const unsigned lds0 = (unsigned)(uintptr_t)(n6_lds_ptr_t)lds;
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)lds;
     const int frow = 8 * lh + ((lane & 15) >> 2);
     const int cin = 2 * ((lane >> 4) & 1) + ((lane & 3) >> 1);
     const unsigned ya = lds0 + (unsigned)(frow * 256 + (((4 * wn) ^ (4 * s4)) + cin) * 16 + (lane & 1) * 8);
@@ -415,14 +372,14 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_n6(GemmP g, int rows_per_block
         const int nxt = (t + 1) & 1;
         const unsigned yb = ya + so, xb0 = xa[0] + so, xb1 = xa[1] + so, xb2 = xa[2] + so;
         auto tr_y = [&](int pl, int ms, int p) -> uint2 {
-#define N6_Y(PL, MS, PP) if (pl == PL && ms == MS && p == PP) return n6_tr_read<PL * YPL + (16 * MS + 4 * PP) * 256>(yb);
+#define N6_Y(PL, MS, PP) if (pl == PL && ms == MS && p == PP) return tr_read_off<PL * YPL + (16 * MS + 4 * PP) * 256>(yb);
             N6_Y(0, 0, 0) N6_Y(0, 0, 1) N6_Y(0, 1, 0) N6_Y(0, 1, 1) N6_Y(1, 0, 0) N6_Y(1, 0, 1) N6_Y(1, 1, 0) N6_Y(1, 1, 1) N6_Y(2, 0, 0) N6_Y(2, 0, 1) N6_Y(2, 1, 0) N6_Y(2, 1, 1)
 #undef N6_Y
             return uint2{0u, 0u};
         };
         auto tr_x = [&](int pl, int j, int ms, int p) -> uint2 {
             const unsigned xb = j == 0 ? xb0 : j == 1 ? xb1 : xb2;
-#define N6_X(PL, MS, PP) if (pl == PL && ms == MS && p == PP) return n6_tr_read<PL * XPL + (16 * MS + 4 * PP) * XCH * 16>(xb);
+#define N6_X(PL, MS, PP) if (pl == PL && ms == MS && p == PP) return tr_read_off<PL * XPL + (16 * MS + 4 * PP) * XCH * 16>(xb);
             N6_X(0, 0, 0) N6_X(0, 0, 1) N6_X(0, 1, 0) N6_X(0, 1, 1) N6_X(1, 0, 0) N6_X(1, 0, 1) N6_X(1, 1, 0) N6_X(1, 1, 1) N6_X(2, 0, 0) N6_X(2, 0, 1) N6_X(2, 1, 0) N6_X(2, 1, 1)
 #undef N6_X
             return uint2{0u, 0u};
@@ -471,7 +428,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_n6(GemmP g, int rows_per_block
                     const int pb = pr == 0 ? 0 : pr == 1 ? 1 : pr == 2 ? 0 : pr == 3 ? 1 : pr == 4 ? 2 : 0;      // X plane:   h m h m l h
 #pragma unroll
                     for (int j = 0; j < 3; ++j)
-                        if (j < nj) acc[j] = n6_mfma(a[pa], b[pb][j], acc[j]);
+                        if (j < nj) acc[j] = mfma_bf16(a[pa], b[pb][j], acc[j]);
                 }
             };
             if (KT - KH == KH || nk == KH) { if (KH == 3) products(3); else products(2); }
@@ -510,10 +467,8 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_n6(GemmP g, int rows_per_block
 
 // Eligibility decided by the caller (gemm.hip): gW is 128 x {128, 160}, both streamed operands fp32 with 16-byte-aligned rows.
 int clift_wgrad_n6_launch(const GemmP& p, hipStream_t st) {
-    const int tiles = cdiv(p.K, N6_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(p.K, blocks), N6_ROWS) * N6_ROWS;
-    if (p.N == 128) k_wgrad_n6<4><<<cdiv(p.K, rpb), 512, 0, st>>>(p, rpb);
-    else k_wgrad_n6<5><<<cdiv(p.K, rpb), 512, 0, st>>>(p, rpb);
+    const RowRanges r = persistent_ranges(p.K, N6_ROWS);
+    if (p.N == 128) k_wgrad_n6<4><<<r.grid, 512, 0, st>>>(p, r.rpb);
+    else k_wgrad_n6<5><<<r.grid, 512, 0, st>>>(p, r.rpb);
     return clift_check_launch("clift_gemm(fp32x6 128-wide wgrad)");
 }

@@ -13,56 +13,34 @@
 // Wave = one 32-column group of the output, both 32-row halves of a 64-row tile (4 or 5 waves per block, two blocks per CU).
 // LDS image of a tile is lane-linear (a DMA constraint); the bank swizzle is applied at the source address: 256-byte rows (16 chunks of
 // 16 B): chunk c of row r in slot c ^ (r & 15); 320-byte rows (20 chunks; consecutive rows already start 16 banks apart): c ^ ((r >> 2) & 3).
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_nb16)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int NB_ROWS = 64;
 
-static __device__ __forceinline__ bf16x8 nb_cvt8(const float4 a, const float4 b) {
-    bf16x8 r;
-    r[0] = (__bf16)a.x; r[1] = (__bf16)a.y; r[2] = (__bf16)a.z; r[3] = (__bf16)a.w;
-    r[4] = (__bf16)b.x; r[5] = (__bf16)b.y; r[6] = (__bf16)b.z; r[7] = (__bf16)b.w;
-    return r;
-}
-static __device__ __forceinline__ unsigned nb_pack(float lo, float hi) {
-    return (unsigned)float_to_bf16_bits(lo) | ((unsigned)float_to_bf16_bits(hi) << 16);
-}
-static __device__ __forceinline__ unsigned nb_keep_positive(unsigned v, unsigned mk) {      // per 16-bit half: v where the mask half is > 0
-    const unsigned lo = bf16_bits_positive((unsigned short)(mk & 0xffffu)) ? 0x0000ffffu : 0u;
-    const unsigned hi = bf16_bits_positive((unsigned short)(mk >> 16)) ? 0xffff0000u : 0u;
-    return v & (lo | hi);
-}
-template <int N>
-static __device__ __forceinline__ void nb_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // allow at most n (wave-uniform) of this wave's vector-memory instructions to be outstanding; rounding down only waits longer
 static __device__ __forceinline__ void nb_wait_upto(int n) {
-    if (n >= 40) nb_wait<40>();
-    else if (n >= 32) nb_wait<32>();
-    else if (n >= 28) nb_wait<28>();
-    else if (n >= 24) nb_wait<24>();
-    else if (n >= 20) nb_wait<20>();
-    else if (n >= 18) nb_wait<18>();
-    else if (n >= 16) nb_wait<16>();
-    else if (n >= 14) nb_wait<14>();
-    else if (n >= 12) nb_wait<12>();
-    else if (n >= 10) nb_wait<10>();
-    else if (n >= 9) nb_wait<9>();
-    else if (n >= 8) nb_wait<8>();
-    else if (n >= 7) nb_wait<7>();
-    else if (n >= 6) nb_wait<6>();
-    else if (n >= 5) nb_wait<5>();
-    else if (n >= 4) nb_wait<4>();
-    else if (n >= 3) nb_wait<3>();
-    else if (n >= 2) nb_wait<2>();
-    else if (n >= 1) nb_wait<1>();
-    else nb_wait<0>();
+    if (n >= 40) wait_vm<40>();
+    else if (n >= 32) wait_vm<32>();
+    else if (n >= 28) wait_vm<28>();
+    else if (n >= 24) wait_vm<24>();
+    else if (n >= 20) wait_vm<20>();
+    else if (n >= 18) wait_vm<18>();
+    else if (n >= 16) wait_vm<16>();
+    else if (n >= 14) wait_vm<14>();
+    else if (n >= 12) wait_vm<12>();
+    else if (n >= 10) wait_vm<10>();
+    else if (n >= 9) wait_vm<9>();
+    else if (n >= 8) wait_vm<8>();
+    else if (n >= 7) wait_vm<7>();
+    else if (n >= 6) wait_vm<6>();
+    else if (n >= 5) wait_vm<5>();
+    else if (n >= 4) wait_vm<4>();
+    else if (n >= 3) wait_vm<3>();
+    else if (n >= 2) wait_vm<2>();
+    else if (n >= 1) wait_vm<1>();
+    else wait_vm<0>();
 }
-template <int KCH>
-static __device__ __forceinline__ int nb_sw(int r) { return KCH == 16 ? (r & 15) : ((r >> 2) & 3); }
 
 // The fused output layer of the forward form (OUTV): the layer is the LAST hidden layer (128 -> 128) and the E <= 4 wide output layer +
 // sigmoid (tensoRF.py:397,410) is applied to the finished tile: a lane holds 16 columns of each of its two rows, 16 x E FMAs per row give its
@@ -104,11 +82,11 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_nb16(GemmP g, int rows_pe
             const int k = 16 * s + 8 * lh;
             if (!DGRAD) {
                 const float4* q = reinterpret_cast<const float4*>(g.B + (size_t)n * g.ldb + k);
-                w[s] = nb_cvt8(q[0], q[1]);
+                w[s] = cvt8(q[0], q[1]);
             } else {
                 const float* q = g.B + (size_t)k * g.ldb + n;
                 const size_t ld = (size_t)g.ldb;
-                w[s] = nb_cvt8(make_float4(q[0], q[ld], q[2 * ld], q[3 * ld]), make_float4(q[4 * ld], q[5 * ld], q[6 * ld], q[7 * ld]));
+                w[s] = cvt8(make_float4(q[0], q[ld], q[2 * ld], q[3 * ld]), make_float4(q[4 * ld], q[5 * ld], q[6 * ld], q[7 * ld]));
             }
         }
 #pragma unroll
@@ -128,7 +106,7 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_nb16(GemmP g, int rows_pe
                 for (int e = 0; e < 4; ++e) wo[c][4 * q + e] = c < op.E ? op.Wout[(size_t)c * op.ldwo + 32 * wave + 8 * q + 4 * lh + e] : 0.f;
         bo = (op.bout && (tid & 3) < op.E) ? op.bout[tid & 3] : 0.f;
     }
-    nb_wait<0>();                                                           // ordinary loads are done before the first DMA is issued
+    wait_vm<0>();                                                           // ordinary loads are done before the first DMA is issued
     const unsigned short* A16 = reinterpret_cast<const unsigned short*>(g.A);
     const unsigned short* K16 = reinterpret_cast<const unsigned short*>(g.mask);
     unsigned short* C16 = reinterpret_cast<unsigned short*>(g.C);
@@ -141,7 +119,7 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_nb16(GemmP g, int rows_pe
         for (int i = 0; i < PER; ++i) {
             const int inst = min(wave * PER + i, KCH - 1);                   // (a wave past the end repeats the last piece: same bytes, same place)
             const int q = inst * 64 + lane, row = q / KCH, slot = q - row * KCH;
-            const int c = slot ^ nb_sw<KCH>(row);
+            const int c = slot ^ bank_sw<KCH>(row);
             const int gr = min(r0 + row, rend - 1);                          // rows past the range re-read its last row (never stored)
             __builtin_amdgcn_global_load_lds(A16 + (size_t)gr * g.lda + c * 8, (lds_ptr_t)(st + inst * 64), 16, 0, 0);
         }
@@ -171,8 +149,8 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_nb16(GemmP g, int rows_pe
         const uint4* T = lds + (t % NB_NST) * TILE;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            const bf16x8 a0 = __builtin_bit_cast(bf16x8, T[li * KCH + ((2 * s + lh) ^ nb_sw<KCH>(li))]);
-            const bf16x8 a1 = __builtin_bit_cast(bf16x8, T[(li + 32) * KCH + ((2 * s + lh) ^ nb_sw<KCH>(li + 32))]);
+            const bf16x8 a0 = __builtin_bit_cast(bf16x8, T[li * KCH + ((2 * s + lh) ^ bank_sw<KCH>(li))]);
+            const bf16x8 a1 = __builtin_bit_cast(bf16x8, T[(li + 32) * KCH + ((2 * s + lh) ^ bank_sw<KCH>(li + 32))]);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[s], a0, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[s], a1, acc[1], 0, 0, 0);
         }
@@ -204,15 +182,15 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_nb16(GemmP g, int rows_pe
             } else if (!OUTV || op.store_hidden) {
 #pragma unroll
                 for (int qp = 0; qp < 2; ++qp) {
-                    const unsigned p00 = nb_pack(v[8 * qp + 0], v[8 * qp + 1]), p01 = nb_pack(v[8 * qp + 2], v[8 * qp + 3]);
-                    const unsigned p10 = nb_pack(v[8 * qp + 4], v[8 * qp + 5]), p11 = nb_pack(v[8 * qp + 6], v[8 * qp + 7]);
+                    const unsigned p00 = pack_bf16_bits(v[8 * qp + 0], v[8 * qp + 1]), p01 = pack_bf16_bits(v[8 * qp + 2], v[8 * qp + 3]);
+                    const unsigned p10 = pack_bf16_bits(v[8 * qp + 4], v[8 * qp + 5]), p11 = pack_bf16_bits(v[8 * qp + 6], v[8 * qp + 7]);
                     const u32x2 s0 = __builtin_amdgcn_permlane32_swap(p00, p10, false, false);
                     const u32x2 s1 = __builtin_amdgcn_permlane32_swap(p01, p11, false, false);
                     uint4 o = make_uint4(s0[0], s1[0], s0[1], s1[1]);          // 8 consecutive columns from 32 wave + 8 (2 qp + lh)
                     if (MASK) {
                         const uint4 k4 = mk[x][qp];
-                        o.x = nb_keep_positive(o.x, k4.x); o.y = nb_keep_positive(o.y, k4.y);
-                        o.z = nb_keep_positive(o.z, k4.z); o.w = nb_keep_positive(o.w, k4.w);
+                        o.x = keep_positive(o.x, k4.x); o.y = keep_positive(o.y, k4.y);
+                        o.z = keep_positive(o.z, k4.z); o.w = keep_positive(o.w, k4.w);
                     }
                     if (m < rend) *reinterpret_cast<uint4*>(C16 + (size_t)m * g.ldc + 32 * wave + 8 * (2 * qp + lh)) = o;
                 }
@@ -244,11 +222,9 @@ __global__ __launch_bounds__(64 * NCG, 2) void k_layer_nb16(GemmP g, int rows_pe
 
 // Eligibility is decided by the caller (gemm_bf16.hip).
 int clift_layer_nb16_launch(const GemmP& p, int b_trans, hipStream_t st) {
-    const int tiles = cdiv(p.M, NB_ROWS);
-    const int want = 2 * clift_persistent_cus();                             // two blocks per CU
-    const int blocks = tiles < want ? tiles : want;
-    const int rpb = cdiv(cdiv(p.M, blocks), NB_ROWS) * NB_ROWS;
-    const dim3 grid(cdiv(p.M, rpb));
+    const RowRanges r = persistent_ranges(p.M, NB_ROWS, 2);                  // two blocks per CU
+    const int rpb = r.rpb;
+    const dim3 grid(r.grid);
     const NbOut none = {nullptr, 0, nullptr, 0, nullptr, 0, 0, 1};
     if (!b_trans && p.K == 160) k_layer_nb16<10, 4, false, false, false, false><<<grid, 256, 0, st>>>(p, rpb, none);
     else if (!b_trans && p.K == 128) k_layer_nb16<8, 4, false, false, false, false><<<grid, 256, 0, st>>>(p, rpb, none);
@@ -272,11 +248,8 @@ extern "C" int clift_app_head_last2_bf16_fwd(const void* A, int lda, const float
     p.M = M; p.N = 128; p.K = 128; p.A = reinterpret_cast<const float*>(A); p.lda = lda; p.B = W; p.ldb = ldw;
     p.C = reinterpret_cast<float*>(hidden); p.ldc = ldh; p.bias = b; p.act = 1;
     const NbOut op = {Wout, ldwo, bout, E, out, ldo, sigmoid, hidden ? 1 : 0};
-    const int tiles = cdiv(M, NB_ROWS);
-    const int want = 2 * clift_persistent_cus();
-    const int blocks = tiles < want ? tiles : want;
-    const int rpb = cdiv(cdiv(M, blocks), NB_ROWS) * NB_ROWS;
-    k_layer_nb16<8, 4, false, false, false, true><<<cdiv(M, rpb), 256, 0, as_stream(s)>>>(p, rpb, op);
+    const RowRanges r = persistent_ranges(M, NB_ROWS, 2);
+    k_layer_nb16<8, 4, false, false, false, true><<<r.grid, 256, 0, as_stream(s)>>>(p, r.rpb, op);
     return clift_check_launch("clift_app_head_last2_bf16_fwd");
 }
 
@@ -287,13 +260,6 @@ extern "C" int clift_app_head_last2_bf16_fwd(const void* A, int lda, const float
 // dY image (256-byte rows): 16-byte chunk c of row r in slot c ^ ((r & 3) << 2), so that the four rows of a transposed read fall into four
 // different 64-byte bank spans; the X image likewise when its rows are 256 bytes, unswizzled when they are 320 (consecutive rows then start 64
 // bytes apart in the banks by themselves).
-static __device__ __forceinline__ uint2 nb_tr_read(unsigned addr) {
-    uint2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-static __device__ __forceinline__ float nb_pair_sum(unsigned u) { return __uint_as_float(u << 16) + __uint_as_float(u & 0xffff0000u); }
-
 template <int KT>
 __global__ __launch_bounds__(512, 1) void k_wgrad_nb16(GemmP g, int rows_per_block) {
     constexpr int XCH = 4 * KT;                          // chunks per X row
@@ -349,7 +315,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_nb16(GemmP g, int rows_per_blo
     constexpr int PERT = 2 + PERX;
     for (int t = 0; t < DEPTH && t < ntiles; ++t) dma(t);
     for (int t = 0; t < ntiles; ++t) {
-        if (min(t + DEPTH - 1, ntiles - 1) > t) nb_wait<PERT>(); else nb_wait<0>();           // one younger tile stays in flight
+        if (min(t + DEPTH - 1, ntiles - 1) > t) wait_vm<PERT>(); else wait_vm<0>();           // one younger tile stays in flight
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + DEPTH < ntiles) dma(t + DEPTH);
@@ -364,11 +330,11 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_nb16(GemmP g, int rows_per_blo
         for (int ms = 0; ms < 4; ++ms) {
             uint2 yr[2], xr[3][2];
 #pragma unroll
-            for (int p = 0; p < 2; ++p) yr[p] = nb_tr_read(ya + so + (unsigned)((16 * ms + 4 * p) * 256));
+            for (int p = 0; p < 2; ++p) yr[p] = tr_read(ya + so + (unsigned)((16 * ms + 4 * p) * 256));
 #pragma unroll
             for (int j = 0; j < 3; ++j)
 #pragma unroll
-                for (int p = 0; p < 2; ++p) xr[j][p] = nb_tr_read(xa[j] + so + (unsigned)((16 * ms + 4 * p) * XCH * 16));
+                for (int p = 0; p < 2; ++p) xr[j][p] = tr_read(xa[j] + so + (unsigned)((16 * ms + 4 * p) * XCH * 16));
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(yr[0]), "+v"(yr[1]), "+v"(xr[0][0]), "+v"(xr[0][1]), "+v"(xr[1][0]), "+v"(xr[1][1]), "+v"(xr[2][0]), "+v"(xr[2][1])
                          :
@@ -381,7 +347,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_nb16(GemmP g, int rows_per_blo
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
                 }
             }
-            if (g.colsum && wk == 0) csum += (nb_pair_sum(yr[0].x) + nb_pair_sum(yr[0].y)) + (nb_pair_sum(yr[1].x) + nb_pair_sum(yr[1].y));
+            if (g.colsum && wk == 0) csum += (bf16_pair_sum(yr[0].x) + bf16_pair_sum(yr[0].y)) + (bf16_pair_sum(yr[1].x) + bf16_pair_sum(yr[1].y));
         }
     }
     // lane (li, lh) holds gW rows n = 32 wn + 8 q + 4 lh + e, column k = 32 tk + li
@@ -406,11 +372,9 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_nb16(GemmP g, int rows_per_blo
 
 // Eligibility decided by the caller: gW is 128 x {128, 160}, both streamed operands bf16-stored with 16-byte-aligned rows.
 int clift_wgrad_nb16_launch(const GemmP& p, hipStream_t st) {
-    const int tiles = cdiv(p.K, NB_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(p.K, blocks), NB_ROWS) * NB_ROWS;
-    if (p.N == 128) k_wgrad_nb16<4><<<cdiv(p.K, rpb), 512, 0, st>>>(p, rpb);
-    else k_wgrad_nb16<5><<<cdiv(p.K, rpb), 512, 0, st>>>(p, rpb);
+    const RowRanges r = persistent_ranges(p.K, NB_ROWS);
+    if (p.N == 128) k_wgrad_nb16<4><<<r.grid, 512, 0, st>>>(p, r.rpb);
+    else k_wgrad_nb16<5><<<r.grid, 512, 0, st>>>(p, r.rpb);
     return clift_check_launch("clift_gemm(bf16 128-wide wgrad stream)");
 }
 
@@ -450,7 +414,7 @@ __global__ __launch_bounds__(256) void k_out_bwd_nb16(const float* __restrict__ 
 #pragma unroll
                 for (int c = 0; c < 4; ++c) aw[c][e] = fmaf(d[c], hv, aw[c][e]);
             }
-            ow[p] = nb_pack(o[0], o[1]);
+            ow[p] = pack_bf16_bits(o[0], o[1]);
         }
         if (cg == 0) { ab[0] += d[0]; ab[1] += d[1]; ab[2] += d[2]; ab[3] += d[3]; }
         *reinterpret_cast<uint4*>(dX + (size_t)m * ldx + 8 * cg) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
@@ -481,11 +445,8 @@ extern "C" int clift_out_layer_bwd_n128_bf16(const float* dOut, int ldd, int no,
     CLIFT_REQUIRE(no >= 1 && no <= 4 && ldd >= 4 && ldd % 4 == 0 && (((uintptr_t)dOut) & 15) == 0, "clift_out_layer_bwd_n128_bf16: 1 <= no <= 4, dOut rows of >= 4 floats, 16-byte aligned");
     CLIFT_REQUIRE(ldh % 8 == 0 && ldx % 8 == 0 && ldh >= 128 && ldx >= 128 && ldw >= 128 && ldgw >= 128 && (((uintptr_t)H) & 15) == 0 && (((uintptr_t)dX) & 15) == 0,
                   "clift_out_layer_bwd_n128_bf16: 16-byte aligned bf16 rows with pitches >= 128 required");
-    const int want = 4 * clift_persistent_cus();
-    const int steps = cdiv(M, 16);
-    const int blocks = steps < want ? steps : want;
-    const int rpb = cdiv(cdiv(M, blocks), 16) * 16;
-    k_out_bwd_nb16<<<cdiv(M, rpb), 256, 0, as_stream(s)>>>(dOut, ldd, no, W, ldw, reinterpret_cast<const unsigned short*>(H), ldh, M,
-                                                          reinterpret_cast<unsigned short*>(dX), ldx, gW, ldgw, gb, rpb);
+    const RowRanges r = persistent_ranges(M, 16, 4);                         // 16-row steps, four blocks per CU
+    k_out_bwd_nb16<<<r.grid, 256, 0, as_stream(s)>>>(dOut, ldd, no, W, ldw, reinterpret_cast<const unsigned short*>(H), ldh, M,
+                                                    reinterpret_cast<unsigned short*>(dX), ldx, gW, ldgw, gb, r.rpb);
     return clift_check_launch("clift_out_layer_bwd_n128_bf16");
 }

@@ -32,15 +32,8 @@
 // Nothing in the loop is conditional: rows past the end of a range are CLAMPED to its last row on the way in (DMA, mask), so their
 // results are copies of that row's and the store simply writes them to that row again; the first tile "stores" zeros to its own rows,
 // which its real results overwrite later (same wave, same addresses, program order).  tools/x6_vmcnt_model.py replays the streams.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_x6)
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // Timing probes (tools/x6_ablation.sh builds variants of the library with -DX6_ABL=<bits>; results are garbage by construction, never shipped):
 // 1 no fragment reads after a tile's first, 2 no activation split (staging reads, VALU, plane writes), 4 no k-half exchange / finish,
@@ -57,36 +50,11 @@ constexpr int X6_ROWS = 32;                         // rows per tile
 constexpr int X6_PLANE = X6_ROWS * 512;             // bytes of one bf16 plane image of a tile (32 rows x 256 k x 2 B)
 constexpr int X6_STAGE = 3 * X6_PLANE;              // 48 KB
 
-static __device__ __forceinline__ unsigned x6_pk(float lo, float hi) {        // two fp32 -> packed bf16 (RNE), `lo` in the low half
-    bf16x2 p;
-    p[0] = (__bf16)lo; p[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, p);
-}
 static __device__ __forceinline__ float x6_uniform(float v) {                  // a wave-uniform value, kept in a scalar register
     return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
 }
-static __device__ __forceinline__ float x6_lo(unsigned p) { return __uint_as_float(p << 16); }
-static __device__ __forceinline__ float x6_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
 
-// exact three-way split of a pair: planes[0..2] receive the packed (a, b) terms
-static __device__ __forceinline__ void x6_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = x6_pk(a, b);
-    const float ra = a - x6_lo(h), rb = b - x6_hi(h);
-    m = x6_pk(ra, rb);
-    const float sa = ra - x6_lo(m), sb = rb - x6_hi(m);
-    l = x6_pk(sa, sb);
-}
-
-static __device__ __forceinline__ f32x16 x6_mfma(const u32x4& w, const u32x4& a, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
-}
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 constexpr int X6_RAW = 2 * X6_STAGE;                // fp32 staging: wave w owns rows w + 4 i as 1 KB slots (w * 8 + i), 32 KB
-
-template <int N>
-static __device__ __forceinline__ void x6_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 constexpr int X6_XCH = X6_RAW + X6_ROWS * 1024;     // exchange area: [tile parity][wave][2][lane] float4 = 2 x 16 KB
 // vmcnt before the read-back of staged row i (tools/x6_vmcnt_model.py replays each stream and prints these tables), by variant:
 #ifndef X6_VM00
@@ -103,10 +71,10 @@ constexpr int X8_VM[6][4] = {
 
 template <int V>
 static __device__ __forceinline__ void x8_wait_piece(int i) {
-    if (i == 0) x6_wait_vm<X8_VM[V][0]>();
-    if (i == 1) x6_wait_vm<X8_VM[V][1]>();
-    if (i == 2) x6_wait_vm<X8_VM[V][2]>();
-    if (i == 3) x6_wait_vm<X8_VM[V][3]>();
+    if (i == 0) wait_vm<X8_VM[V][0]>();
+    if (i == 1) wait_vm<X8_VM[V][1]>();
+    if (i == 2) wait_vm<X8_VM[V][2]>();
+    if (i == 3) wait_vm<X8_VM[V][3]>();
 }
 
 // GEN (forward only): the layer is the SECOND layer of an xyz head and its input is generated, A[m][k] = relu(W0[k] . x_m + b0[k]) with K = 3
@@ -250,11 +218,11 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
     };
     auto split_a = [&]() {
         if (X6_ABL & 2) return;
-        sp_h0 = x6_pk(sp_x[0], sp_x[1]); sp_h1 = x6_pk(sp_x[2], sp_x[3]);
+        sp_h0 = pack_bf16_cast(sp_x[0], sp_x[1]); sp_h1 = pack_bf16_cast(sp_x[2], sp_x[3]);
         asm volatile("" : "+v"(sp_h0), "+v"(sp_h1));
     };
-    auto split_b0 = [&]() { if (X6_ABL & 2) return; sp_r0 = sp_x[0] - x6_lo(sp_h0); sp_r1 = sp_x[1] - x6_hi(sp_h0); };
-    auto split_b1 = [&]() { if (X6_ABL & 2) return; sp_r2 = sp_x[2] - x6_lo(sp_h1); sp_r3 = sp_x[3] - x6_hi(sp_h1); };
+    auto split_b0 = [&]() { if (X6_ABL & 2) return; sp_r0 = sp_x[0] - bf16_lo(sp_h0); sp_r1 = sp_x[1] - bf16_hi(sp_h0); };
+    auto split_b1 = [&]() { if (X6_ABL & 2) return; sp_r2 = sp_x[2] - bf16_lo(sp_h1); sp_r3 = sp_x[3] - bf16_hi(sp_h1); };
     auto wr = [&](unsigned addr, int plane, int i, unsigned a, unsigned c) {
         const u32x2 d = {a, c};
         const int off = plane * X6_PLANE + (i >> 1) * 8192;
@@ -267,16 +235,16 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
     };
     auto split_c = [&](unsigned stage, int i) {
         if (X6_ABL & 2) return;
-        sp_m0 = x6_pk(sp_r0, sp_r1); sp_m1 = x6_pk(sp_r2, sp_r3);
+        sp_m0 = pack_bf16_cast(sp_r0, sp_r1); sp_m1 = pack_bf16_cast(sp_r2, sp_r3);
         asm volatile("" : "+v"(sp_m0), "+v"(sp_m1));
         wr(wofs[i & 1] + stage, 0, i, sp_h0, sp_h1);
     };
-    auto split_d0 = [&]() { if (X6_ABL & 2) return; sp_s0 = sp_r0 - x6_lo(sp_m0); sp_s1 = sp_r1 - x6_hi(sp_m0); };
-    auto split_d1 = [&]() { if (X6_ABL & 2) return; sp_s2 = sp_r2 - x6_lo(sp_m1); sp_s3 = sp_r3 - x6_hi(sp_m1); };
+    auto split_d0 = [&]() { if (X6_ABL & 2) return; sp_s0 = sp_r0 - bf16_lo(sp_m0); sp_s1 = sp_r1 - bf16_hi(sp_m0); };
+    auto split_d1 = [&]() { if (X6_ABL & 2) return; sp_s2 = sp_r2 - bf16_lo(sp_m1); sp_s3 = sp_r3 - bf16_hi(sp_m1); };
     auto split_e = [&](unsigned stage, int i) {
         if (X6_ABL & 2) return;
         wr(wofs[i & 1] + stage, 1, i, sp_m0, sp_m1);
-        wr(wofs[i & 1] + stage, 2, i, x6_pk(sp_s0, sp_s1), x6_pk(sp_s2, sp_s3));
+        wr(wofs[i & 1] + stage, 2, i, pack_bf16_cast(sp_s0, sp_s1), pack_bf16_cast(sp_s2, sp_s3));
     };
 
     // ---- prologue: tile 0's rows -> staging -> split into stage 0; tile 1's rows on their way while the weights are prepared
@@ -286,7 +254,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
 #pragma unroll
         for (int i = 0; i < 4; ++i) dma_piece(0, i);
     }
-    x6_wait_vm<0>();
+    wait_vm<0>();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         raw_read(i, 0);
@@ -328,7 +296,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
         for (int pr = 0; pr < 4; ++pr) {
             unsigned h, m, l;
             if (X6_ABL & 128) { h = __float_as_uint(v[2 * pr]); m = __float_as_uint(v[2 * pr + 1]); l = h ^ m; }
-            else x6_split_pair(v[2 * pr], v[2 * pr + 1], h, m, l);
+            else split3_pair(v[2 * pr], v[2 * pr + 1], h, m, l);
             wh[j][pr] = h; wm[j][pr] = m; wl[j][pr] = l;
         }
     }
@@ -336,7 +304,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
     float bfin[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) bfin[e] = (!DGRAD && g.bias) ? g.bias[fcol + 8 * (e >> 2) + (e & 3)] : 0.f;
-    x6_wait_vm<0>();                     // tile 1's rows have landed: from here on every wait is counted
+    wait_vm<0>();                     // tile 1's rows have landed: from here on every wait is counted
 
     const unsigned adk = lds0 + (unsigned)(li * 512 + ((lh ^ (li & 15)) << 4) + kh * 256);          // chunk 16 kh + 2 j + lh of row li
     const unsigned xrd = lds0 + (unsigned)(X6_XCH + wave * 2048 + lane * 16);                       // what the partner sends to this wave
@@ -471,7 +439,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
             if (even) {
                 // GEN: the positions of tile t+1 left during tile t-1 (one DMA, before that tile's two stores); younger than it at any of the four
                 // read-backs: those two stores, this tile's position DMA (from i = 2 on) and first store (i = 3) -- vmcnt(2) covers all four
-                if (X6_ABL & 8) { } else if (GEN) x6_wait_vm<BM ? 3 : 2>(); else x8_wait_piece<VMV>(i);
+                if (X6_ABL & 8) { } else if (GEN) wait_vm<BM ? 3 : 2>(); else x8_wait_piece<VMV>(i);
                 // (marks for the build's listing check: the staged slot read next must not have its DMA in flight -- GEN: the positions of
                 //  tile t + 2 may be, from i = 2 on)
                 if (GEN) { if (i < 2) CLIFT_MARK_USE("pos", "0"); else CLIFT_MARK_USE("pos", "1"); }
@@ -484,7 +452,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
                 gen_values();
                 split_a();
             }
-            acc0 = x6_mfma(wh[j], f[0], acc0);
+            acc0 = mfma_bf16(wh[j], f[0], acc0);
             __builtin_amdgcn_sched_barrier(0);
             // ---- gap 1
             if (j == 0) {                                                        // the previous tile's results: what was kept + what the partner sent
@@ -496,7 +464,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
                 if (K3W) { xcur = xq; prev_ok = ok_done; ok_done = rbeg + t * X6_ROWS + li < rend; }
             } else if (even) split_e(nxt, i - 1);
             else split_b0();
-            acc1 = x6_mfma(wh[j], f[1], acc1);
+            acc1 = mfma_bf16(wh[j], f[1], acc1);
             __builtin_amdgcn_sched_barrier(0);
             // ---- gap 2
             if (even) {
@@ -523,7 +491,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
                 if (OUTV && j == 0) out_fma(0);                                  // the previous tile's rows through the output layer: steps 0, 2
                 if (OUTV && j == 2) out_fold();
             } else split_b1();
-            acc0 = x6_mfma(wm[j], f[1], acc0);
+            acc0 = mfma_bf16(wm[j], f[1], acc0);
             __builtin_amdgcn_sched_barrier(0);
             // ---- gap 3
             if (even) {
@@ -532,7 +500,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
                 if (OUTV && j == 0) out_fma(1);
                 if (K3W && j == 0) k3_col(0);
             } else split_c(nxt, i);
-            acc1 = x6_mfma(wm[j], f[0], acc1);
+            acc1 = mfma_bf16(wm[j], f[0], acc1);
             __builtin_amdgcn_sched_barrier(0);
             // ---- gap 4
             if (even) {
@@ -546,7 +514,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
                 if (!DGRAD && BM && j == 2) sb0[(size_t)tb_prev * 1024] = (unsigned char)sbyte;                                              // "B"
                 if (OUTV && j == 2 && !(X6_ABL & 16)) *reinterpret_cast<f32x2*>(pslot + (size_t)prev_m * 4) = pfold;       // "P"
             } else { split_d0(); if (j == 7) split_d1(); }
-            acc0 = x6_mfma(wh[j], f[2], acc0);
+            acc0 = mfma_bf16(wh[j], f[2], acc0);
             __builtin_amdgcn_sched_barrier(0);
             // ---- gap 5
             if (!even) {
@@ -557,7 +525,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_x6(GemmP g, int rows_per_range
                 if (K3W && j == 0) k3_col(2);
                 if (K3W && j == 2) k3_col(5);
             }
-            acc1 = x6_mfma(wl[j], f[0], acc1);
+            acc1 = mfma_bf16(wl[j], f[0], acc1);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (K3W) asm volatile("s_waitcnt vmcnt(4)" : "+v"(xq) : : "memory");

@@ -25,31 +25,14 @@
 // same SIMD beside the MFMA stream and came back with wrong lanes 48..63 (59 % of the neighbour's launches; one process alone: never).  The
 // remedy is a register ballast: every wave claims 256 registers (one asm clobber of v255), two of them fill the SIMD's file and nothing else
 // fits beside them -- 0 wrong results in 43 000 launches of the same neighbour, same speed.  k_layer_x6 carries the same ballast.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(layer_x6w)
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int XW_ROWS = 32;
 constexpr int XW_PITCH = 80;                        // bytes per column of a transposed plane image: 32 m x 2 B + 16
 constexpr int XW_PLANE = 128 * XW_PITCH;            // 10240
 constexpr int XW_STAGE = 6 * XW_PLANE;              // [operand 0 = dY, 1 = X][plane]: 61440
 constexpr int XW_RAW = 2 * XW_STAGE;                // fp32 staging: wave w: [operand][8 rows][512 B] = 8 KB
-
-static __device__ __forceinline__ unsigned xw_pk(float lo, float hi) {
-    bf16x2 p;
-    p[0] = (__bf16)lo; p[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, p);
-}
-static __device__ __forceinline__ float xw_lo(unsigned p) { return __uint_as_float(p << 16); }
-static __device__ __forceinline__ float xw_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-static __device__ __forceinline__ f32x16 xw_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // GENX (clift_xyz_head_first2_x6_wgrad): the layer is the SECOND layer of an xyz head and its input X[m][k] = relu(W0[k] . x_m + b0[k]) (K = 3,
 // tensoRF.py:475,576) is GENERATED in the split instead of streamed -- the forward never wrote it (clift_xyz_head_first2_x6_fwd).  The X rows'
@@ -150,14 +133,13 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_x6(GemmP g, int rows_per_range
     };
     auto run_split = [&](int q) {                       // pair q (rows 2 q, 2 q + 1 of the run)
         const float a = v[2 * q], c = v[2 * q + 1];
-        unsigned h = xw_pk(a, c);
+        unsigned h = pack_bf16_cast(a, c);
         asm volatile("" : "+v"(h));
-        const float ra = a - xw_lo(h), rc = c - xw_hi(h);
-        unsigned m = xw_pk(ra, rc);
+        const float ra = a - bf16_lo(h), rc = c - bf16_hi(h);
+        unsigned m = pack_bf16_cast(ra, rc);
         asm volatile("" : "+v"(m));
-        sh[q] = h; sm[q] = m; sl[q] = xw_pk(ra - xw_lo(m), rc - xw_hi(m));
+        sh[q] = h; sm[q] = m; sl[q] = pack_bf16_cast(ra - bf16_lo(m), rc - bf16_hi(m));
     };
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     auto run_write = [&](unsigned stage, int o, int u) {
         const unsigned a = lds0 + stage + (unsigned)(o * 3 * XW_PLANE + (64 * ch + lane) * XW_PITCH + (2 * ro + (lq ^ u)) * 8);
         const u32x2 dh = {sh[0], sh[1]}, dm = {sm[0], sm[1]}, dl = {sl[0], sl[1]};
@@ -228,35 +210,35 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_x6(GemmP g, int rows_per_range
             asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                     // this operand's rows (DMA'd during the previous tile) have landed
             if (o) CLIFT_MARK_USE("x", "0"); else CLIFT_MARK_USE("y", "0");
             run_read(o, 0);
-            acc[0] = xw_mfma(a[0], b0[0], acc[0]);
+            acc[0] = mfma_bf16(a[0], b0[0], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
-            acc[1] = xw_mfma(a[0], b1[0], acc[1]);
+            acc[1] = mfma_bf16(a[0], b1[0], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
             if (GENX && o == 1) gen_wait(0); else run_wait();
             run_mask(valid, o, 0);
-            acc[0] = xw_mfma(a[0], b0[1], acc[0]);
+            acc[0] = mfma_bf16(a[0], b0[1], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
             run_split(0);
-            acc[1] = xw_mfma(a[0], b1[1], acc[1]);
+            acc[1] = mfma_bf16(a[0], b1[1], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
             run_split(1);
-            acc[0] = xw_mfma(a[1], b0[0], acc[0]);
+            acc[0] = mfma_bf16(a[1], b0[0], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
             run_write(nxt, o, 0);
             run_read(o, 1);
-            acc[1] = xw_mfma(a[1], b1[0], acc[1]);
+            acc[1] = mfma_bf16(a[1], b1[0], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
-            acc[0] = xw_mfma(a[1], b0[1], acc[0]);
+            acc[0] = mfma_bf16(a[1], b0[1], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
             if (GENX && o == 1) gen_wait(1); else run_wait();
             run_mask(valid, o, 1);
-            acc[1] = xw_mfma(a[1], b1[1], acc[1]);
+            acc[1] = mfma_bf16(a[1], b1[1], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
             run_split(0);
-            acc[0] = xw_mfma(a[0], b0[2], acc[0]);
+            acc[0] = mfma_bf16(a[0], b0[2], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
             run_split(1);
-            acc[1] = xw_mfma(a[0], b1[2], acc[1]);
+            acc[1] = mfma_bf16(a[0], b1[2], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
             run_write(nxt, o, 1);
             if (s == 1) {                                                         // the next stage is complete on this wave: meet the others, then its first fragments
@@ -265,10 +247,10 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_x6(GemmP g, int rows_per_range
                 asm volatile("" ::: "memory");
                 rd(0, nxt);
             }
-            acc[0] = xw_mfma(a[2], b0[0], acc[0]);
+            acc[0] = mfma_bf16(a[2], b0[0], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
             dma(t + 2, o, 0); dma(t + 2, o, 1);                                  // both runs of this operand are read: refill its rows with tile t + 2's
-            acc[1] = xw_mfma(a[2], b1[0], acc[1]);
+            acc[1] = mfma_bf16(a[2], b1[0], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }

@@ -6,10 +6,8 @@
 // by LDS-DMA two tiles ahead, wave w owns columns 32 w .. +31 of X for ALL classes (no cross-wave reduction), each lane reads one
 // dY and one X element per MFMA step (row-contiguous, conflict-free without any swizzle).  bf16-stored X is widened in the
 // register (exact), so both storage modes give fp32 products.
-#include "gemm_common.h"
+#include "mfma_dev.h"
 CLIFT_ROWS_LIMIT_BINDER(narrow_stream)
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int NS_ROWS = 32;              // rows per tile = 16 MFMA steps of 2 rows
 constexpr int NS_DEPTH = 2;              // tiles in flight ahead of the multiply
@@ -17,17 +15,17 @@ constexpr int NS_STAGES = NS_DEPTH + 1;
 
 static __device__ __forceinline__ void ns_wait_vm(int n) {          // wave-uniform n
     switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+        case 0: wait_vm<0>(); break;
+        case 1: wait_vm<1>(); break;
+        case 2: wait_vm<2>(); break;
+        case 3: wait_vm<3>(); break;
+        case 4: wait_vm<4>(); break;
+        case 5: wait_vm<5>(); break;
+        case 6: wait_vm<6>(); break;
+        case 7: wait_vm<7>(); break;
+        case 8: wait_vm<8>(); break;
+        case 9: wait_vm<9>(); break;
+        default: wait_vm<10>(); break;
     }
 }
 
@@ -135,7 +133,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_narrow_stream(const float* __r
     }
     if (gb && wave == 0) {       // every wave read the same dY; wave 0 folds the two row parities and adds the bias gradient
         const unsigned u = __float_as_uint(bsum);
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         const u32x2 sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
         const float tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
         if (lh == 0 && li < no) unsafeAtomicAdd(gb + li, tot);
@@ -146,22 +143,18 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_narrow_stream(const float* __r
 // 16-byte-aligned rows.
 int clift_wgrad_narrow_stream_launch(const float* dY, int ldd, int no, const float* X, int ldx, int ni, int M, float* gW, int ldw, float* gb, int x_bf16,
                                      hipStream_t st) {
-    const int tiles = cdiv(M, NS_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), NS_ROWS) * NS_ROWS;
-    if (x_bf16) k_wgrad_narrow_stream<true><<<cdiv(M, rpb), 512, 0, st>>>(dY, ldd, no, X, ldx, M, rpb, gW, (long)ldw, 1L, gb, -1, nullptr, 256);
-    else k_wgrad_narrow_stream<false><<<cdiv(M, rpb), 512, 0, st>>>(dY, ldd, no, X, ldx, M, rpb, gW, (long)ldw, 1L, gb, -1, nullptr, ni);
+    const RowRanges r = persistent_ranges(M, NS_ROWS);
+    if (x_bf16) k_wgrad_narrow_stream<true><<<r.grid, 512, 0, st>>>(dY, ldd, no, X, ldx, M, r.rpb, gW, (long)ldw, 1L, gb, -1, nullptr, 256);
+    else k_wgrad_narrow_stream<false><<<r.grid, 512, 0, st>>>(dY, ldd, no, X, ldx, M, r.rpb, gW, (long)ldw, 1L, gb, -1, nullptr, ni);
     return clift_check_launch("clift_wgrad_narrow(stream)");
 }
 
 // K = 3 first-layer backward through the same kernel: dW[n][0..2] += sum_m dH[m][n] x[m][0..2], db[n] += sum_m dH[m][n]
 // (x4 = (M, 4) positions, dH = (M, 256) hidden gradient, fp32 or bf16-stored).  Eligibility decided by the caller.
 int clift_k3_bwd_stream_launch(const float* x4, const float* dH, int ldh, int M, float* dW, int ldw, float* db, int dh_bf16, hipStream_t st) {
-    const int tiles = cdiv(M, NS_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), NS_ROWS) * NS_ROWS;
-    if (dh_bf16) k_wgrad_narrow_stream<true><<<cdiv(M, rpb), 512, 0, st>>>(x4, 4, 3, dH, ldh, M, rpb, dW, 1L, (long)ldw, nullptr, 3, db, 256);
-    else k_wgrad_narrow_stream<false><<<cdiv(M, rpb), 512, 0, st>>>(x4, 4, 3, dH, ldh, M, rpb, dW, 1L, (long)ldw, nullptr, 3, db, 256);
+    const RowRanges r = persistent_ranges(M, NS_ROWS);
+    if (dh_bf16) k_wgrad_narrow_stream<true><<<r.grid, 512, 0, st>>>(x4, 4, 3, dH, ldh, M, r.rpb, dW, 1L, (long)ldw, nullptr, 3, db, 256);
+    else k_wgrad_narrow_stream<false><<<r.grid, 512, 0, st>>>(x4, 4, 3, dH, ldh, M, r.rpb, dW, 1L, (long)ldw, nullptr, 3, db, 256);
     return clift_check_launch("clift_linear_k3_bwd(stream)");
 }
 
@@ -172,9 +165,6 @@ int clift_k3_bwd_stream_launch(const float* x4, const float* dH, int ldh, int M,
 // 32-row tiles of dOut by LDS-DMA (a linear copy: the tile is contiguous in memory), the mask of a tile prefetched into registers
 // at tile start, swapped MFMA operands so a lane owns one output row and stores 16 bytes (8 when bf16-stored) at a time.
 // HB = the mask and the output are bf16-stored (bf16 mode); the products are fp32 either way.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-
 // MASK = false (fp32 only): plain dX = dOut W with N = g.N <= 256 output columns (a multiple of 4): the dgrad of the appearance basis
 // (27 -> 144, tensoRF.py:65,127-134), which the tiled kernel ran at 1.4 TB/s.  Waves whose 32 columns lie past N only help with the DMA.
 // WG (fp32, masked, N = 256 or a smaller multiple of 32 -- the 128-wide appearance head; waves past N only help with the DMA): the output layer's WEIGHT gradient in the same pass -- gW[c][n] += sum_m dOut[m][c] h[m][n], gb[c] += sum_m dOut[m][c] --
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_narrow_stream(GemmP g, int row
     // branch separates the asm loads from the asm wait that publishes their registers.  The plain masked form keeps the same-tile fetch: its
     // tiles are a handful of MFMAs long, one tile of distance hides nothing and moves the wait in front of the barrier (102 -> 116 us).
     f32x4 nk[4];
-    u32x2v nh[4];
+    u32x2 nh[4];
     // (masked form: N is a multiple of 32; a wave past N only helps with the DMA.  Its mask loads stay in the instruction stream --
     // pointed at columns that exist -- for the same reason)
     const bool wave_on = 32 * wave < g.N;
@@ -275,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_narrow_stream(GemmP g, int row
         asm volatile("" ::: "memory");
         if (t + 1 < ntiles) dma(t + 1);
         f32x4 mk[4];
-        u32x2v mh[4];
+        u32x2 mh[4];
         if (PF) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) { mk[q] = nk[q]; mh[q] = nh[q]; }
@@ -378,7 +368,7 @@ __global__ __launch_bounds__(512, 2) void k_dgrad_narrow_stream(GemmP g, int row
         }
         if (gb && wave == 0) {       // every wave read the same dOut; wave 0 folds the two row parities and adds the bias gradient
             const unsigned u = __float_as_uint(bsum);
-            const u32x2v sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+            const u32x2 sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
             const float tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             if (lh == 0 && li < no) unsafeAtomicAdd(gb + li, tot);
         }
@@ -405,21 +395,19 @@ extern "C" int clift_out_layer_bwd_nh(const float* dOut, int ldd, int no, const 
                   (((uintptr_t)H) & 15) == 0 && (((uintptr_t)dX) & 15) == 0, "clift_out_layer_bwd: 16-byte aligned rows with pitches >= the hidden width required");
     GemmP p = {};
     p.M = M; p.N = nh; p.K = no; p.A = dOut; p.lda = ldd; p.B = W; p.ldb = ldw; p.C = dX; p.ldc = ldx; p.mask = H; p.ldmask = ldh;
-    const int tiles = cdiv(M, 32);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), 32) * 32;
-    const dim3 grid(cdiv(M, rpb));
+    const RowRanges r = persistent_ranges(M, 32);
+    const dim3 grid(r.grid);
     hipStream_t st = as_stream(s);
     const int kj = cdiv(no, 8);
     if (h_bf16) {
-        if (kj <= 1) k_dgrad_narrow_stream<1, true, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-        else if (kj == 2) k_dgrad_narrow_stream<2, true, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-        else if (kj == 3) k_dgrad_narrow_stream<3, true, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-        else k_dgrad_narrow_stream<4, true, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-    } else if (kj <= 1) k_dgrad_narrow_stream<1, false, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-    else if (kj == 2) k_dgrad_narrow_stream<2, false, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-    else if (kj == 3) k_dgrad_narrow_stream<3, false, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
-    else k_dgrad_narrow_stream<4, false, true, true><<<grid, 512, 0, st>>>(p, rpb, gW, ldgw, gb, no);
+        if (kj <= 1) k_dgrad_narrow_stream<1, true, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+        else if (kj == 2) k_dgrad_narrow_stream<2, true, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+        else if (kj == 3) k_dgrad_narrow_stream<3, true, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+        else k_dgrad_narrow_stream<4, true, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+    } else if (kj <= 1) k_dgrad_narrow_stream<1, false, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+    else if (kj == 2) k_dgrad_narrow_stream<2, false, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+    else if (kj == 3) k_dgrad_narrow_stream<3, false, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
+    else k_dgrad_narrow_stream<4, false, true, true><<<grid, 512, 0, st>>>(p, r.rpb, gW, ldgw, gb, no);
     return clift_check_launch("clift_out_layer_bwd");
 }
 
@@ -427,16 +415,14 @@ extern "C" int clift_out_layer_bwd_nh(const float* dOut, int ldd, int no, const 
 // weights, no bias / activation, M >= 4096, and either N = 256 with a mask (half = bf16-stored mask and output) or no mask, fp32, N <= 256,
 // N % 4 == 0.
 int clift_dgrad_narrow_stream_launch(const GemmP& p, int half, hipStream_t st) {
-    const int tiles = cdiv(p.M, 32);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(p.M, blocks), 32) * 32;
-    const dim3 grid(cdiv(p.M, rpb));
+    const RowRanges r = persistent_ranges(p.M, 32);
+    const dim3 grid(r.grid);
     const int kj = cdiv(p.K, 8);
 #define CLIFT_DN(KJ)                                                                                     \
     do {                                                                                                 \
-        if (!p.mask) k_dgrad_narrow_stream<KJ, false, false><<<grid, 512, 0, st>>>(p, rpb);              \
-        else if (half) k_dgrad_narrow_stream<KJ, true, true><<<grid, 512, 0, st>>>(p, rpb);              \
-        else k_dgrad_narrow_stream<KJ, false, true><<<grid, 512, 0, st>>>(p, rpb);                       \
+        if (!p.mask) k_dgrad_narrow_stream<KJ, false, false><<<grid, 512, 0, st>>>(p, r.rpb);              \
+        else if (half) k_dgrad_narrow_stream<KJ, true, true><<<grid, 512, 0, st>>>(p, r.rpb);              \
+        else k_dgrad_narrow_stream<KJ, false, true><<<grid, 512, 0, st>>>(p, r.rpb);                       \
     } while (0)
     if (kj <= 1) CLIFT_DN(1);
     else if (kj == 2) CLIFT_DN(2);
@@ -602,9 +588,7 @@ extern "C" int clift_out_layer_fwd(const float* H, int ldh, const float* W, int 
     CLIFT_REQUIRE((((uintptr_t)H) & 15) == 0 && (((uintptr_t)W) & 15) == 0 && ldh % 4 == 0 && ldh >= 256 && ldw % 4 == 0 && ldw >= 256 && ldo >= no && b != nullptr,
                   "clift_out_layer_fwd: H / W must be 16-byte aligned with pitches >= 256 that are multiples of 4, ldo >= out_features, bias required");
     if (M <= 0) return 0;
-    const int tiles = cdiv(M, OF_ROWS);
-    const int blocks = tiles < clift_persistent_cus() ? tiles : clift_persistent_cus();
-    const int rpb = cdiv(cdiv(M, blocks), OF_ROWS) * OF_ROWS;
-    k_out_narrow_fwd<<<cdiv(M, rpb), 512, 0, as_stream(s)>>>(H, ldh, W, ldw, b, no, M, rpb, out, ldo, act);
+    const RowRanges r = persistent_ranges(M, OF_ROWS);
+    k_out_narrow_fwd<<<r.grid, 512, 0, as_stream(s)>>>(H, ldh, W, ldw, b, no, M, r.rpb, out, ldo, act);
     return clift_check_launch("clift_out_layer_fwd");
 }
