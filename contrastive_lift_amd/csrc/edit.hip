@@ -7,8 +7,11 @@
 // An edit PROGRAM (clift_edit_list_*) is an ordered list e_1 .. e_n of up to CLIFT_EDIT_MAX such edits in one render: scene_i is e_i applied
 // to scene_{i-1}, and a sample is evaluated in scene_n by walking the list backwards (edit_walk).  The program is a by-value kernel
 // argument: the records are the same for every lane, the trip count is wave-uniform and the records arrive through scalar loads.
+// The same walk also runs off the rays (clift_edit_list_points, clift_edit_list_dense_sigma) and, with the chain of the remaps carried beside
+// the point, gives the gradient of the EDITED density for the surface outputs of an edited scene (clift_edit_list_density_grad_*, at the end).
 #include "clift_dev.h"
 #include "lattice_dev.h"
+#include "surface_dev.h"
 #include <math.h>
 #include <stddef.h>
 CLIFT_ROWS_LIMIT_BINDER(edit)
@@ -123,7 +126,10 @@ struct EditH {
     bool kill;    // sigma = 0: some edit's kill rule named the point (p, d: where the walk stopped)
     int hops;     // how many edits remapped it (0 .. CLIFT_EDIT_MAX)
 };
-__device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], float d[3]) {
+// ``hop(e)`` is called for every edit that remaps the point, before p is replaced: what else travels with the point (the view direction,
+// the Jacobian of the chain) is turned there.
+template <class Hop>
+__device__ __forceinline__ EditH edit_walk_core(const EditL& L, float p[3], Hop hop) {
     EditH h;
     h.kill = false;
     h.hops = 0;
@@ -134,14 +140,38 @@ __device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], flo
         const bool kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !mov) : false;
         if (!h.kill && mov) {                               // (a killed sample has stopped: later tests see its last point, and change nothing)
             const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
-            const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
+            hop(e);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) { p[j] = q[j]; d[j] = v[j]; }
+            for (int j = 0; j < 3; ++j) p[j] = q[j];
             ++h.hops;
         }
         h.kill = h.kill || kill;
     }
     return h;
+}
+__device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], float d[3]) {
+    return edit_walk_core(L, p, [&](const EditP& e) {
+        const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) d[j] = v[j];
+    });
+}
+// The walk with the Jacobian of the chain beside the point: J (row-major 3x3) starts at the identity and becomes M_i J at
+// every hop, every multiply and add rounded separately, so after the walk p' = J p + b with J = M_{i_h} ... M_{i_1}.
+__device__ __forceinline__ EditH edit_walk_point_jac(const EditL& L, float p[3], float J[9]) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) J[j] = (j % 4 == 0) ? 1.f : 0.f;
+    return edit_walk_core(L, p, [&](const EditP& e) {
+        float N[9];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float col[3] = {J[c], J[3 + c], J[6 + c]};
+#pragma unroll
+            for (int r = 0; r < 3; ++r) N[3 * r + c] = row3(e.M + 3 * r, col);
+        }
+#pragma unroll
+        for (int j = 0; j < 9; ++j) J[j] = N[j];
+    });
 }
 // normalised coordinates of a walked point, every op rounded separately (sample_xn's ops)
 __device__ __forceinline__ void edit_normalise(const float p[3], const float lo[3], const float inv2[3], float xn[3]) {
@@ -468,4 +498,123 @@ extern "C" int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift
                                                                         make_float3(h_inv_ext2[0], h_inv_ext2[1], h_inv_ext2[2]), s0, s1, s2, n0, n1,
                                                                         n2, shift, out, state);
     return clift_check_launch("clift_edit_list_dense_sigma");
+}
+
+// ============================================================================ gradient of the edited density
+// sigma_e(p) = sigma_raw(p') with p' = J p + b the point the walk ends at, so grad sigma_e(p) = J^T g', g' the world gradient of the unedited
+// field at p' (k_density_grad_points with its inv2 scaling).  The two mappings of k_edit_list_dense_sigma: for the walk lane = point (each of
+// the wave's 64 points walked ONCE, J carried beside p), for the taps four passes of 16 points x 4 lanes in the lane roles of
+// k_density_grad_points (vm_density_grad_quad, the shared body), the quad fetching xn, J and the hop count of its point by __shfl at the top
+// of its pass -- registers only, no LDS.  The quad leader forms J^T g' row by row of J^T, every op rounded separately, left to right; a row
+// no edit remapped stores g' itself, so it carries all four columns of clift_density_grad_points bit for bit.  A killed point reads no table
+// and gets a row of zeros; a pass none of whose 16 points is alive is skipped.  One writer per element, no atomics.
+__device__ __forceinline__ void edit_density_grad_wave(const VmP& t, const EditL& L, float p[3], bool valid, const float lo[3], const float inv2[3],
+                                                       float shift, long base, long total, float* __restrict__ out,
+                                                       unsigned char* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    float J[9], xn[3];
+    const EditH h = edit_walk_point_jac(L, p, J);
+    edit_normalise(p, lo, inv2, xn);
+    if (valid && state != nullptr) state[base + lane] = edit_state(h);
+    const unsigned long long on = __ballot(valid && !h.kill);
+    if (on == 0) {                                                   // wave-uniform: nothing of this wave is looked up
+        if (valid) *reinterpret_cast<float4*>(out + (size_t)(base + lane) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int q = lane & 3;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int sl = pass * 16 + (lane >> 2);
+        float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
+        if ((on >> (pass * 16)) & 0xffffull) {                       // wave-uniform: some point of this pass is looked up
+            const float xq[3] = {__shfl(xn[0], sl), __shfl(xn[1], sl), __shfl(xn[2], sl)};
+            float Jq[9];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) Jq[j] = __shfl(J[j], sl);
+            const int hq = __shfl(h.hops, sl);
+            const bool mine = (on >> sl) & 1ull;
+            float acc, g[3];
+            vm_density_grad_quad(t, xq, q, mine, acc, g);
+            if (mine) {
+                const float gw[3] = {g[0] * inv2[0], g[1] * inv2[1], g[2] * inv2[2]};
+                row = make_float4(gw[0], gw[1], gw[2], acc + shift);
+                if (hq > 0) {                                        // J^T g': column c of J against g'
+                    row.x = __fadd_rn(__fadd_rn(__fmul_rn(Jq[0], gw[0]), __fmul_rn(Jq[3], gw[1])), __fmul_rn(Jq[6], gw[2]));
+                    row.y = __fadd_rn(__fadd_rn(__fmul_rn(Jq[1], gw[0]), __fmul_rn(Jq[4], gw[1])), __fmul_rn(Jq[7], gw[2]));
+                    row.z = __fadd_rn(__fadd_rn(__fmul_rn(Jq[2], gw[0]), __fmul_rn(Jq[5], gw[1])), __fmul_rn(Jq[8], gw[2]));
+                }
+            }
+        }
+        if (q == 0 && base + sl < total) *reinterpret_cast<float4*>(out + (size_t)(base + sl) * 4) = row;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_edit_list_density_grad_points(VmP t, EditL L, const float* __restrict__ pts, int ldp, long n, float3 lo,
+                                                                        float3 inv2, float shift, float* __restrict__ out,
+                                                                        unsigned char* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long base = v - lane;                                      // the wave's first row
+    if (base >= n) return;                                           // wave-uniform
+    const bool valid = v < n;
+    const long vc = valid ? v : n - 1;                               // (the tail lanes walk the last point again: no divergence around the loop)
+    const float* pi = pts + (size_t)vc * ldp;
+    float p[3] = {pi[0], pi[1], pi[2]};
+    const float l3[3] = {lo.x, lo.y, lo.z}, inv3[3] = {inv2.x, inv2.y, inv2.z};
+    edit_density_grad_wave(t, L, p, valid, l3, inv3, shift, base, n, out, state);
+}
+
+// ... at the active samples of a march: the point of row s from (rays, act_idx[s]) with the very operations of k_edit_list_active
+__global__ __launch_bounds__(256) void k_edit_list_density_grad_active(MarchP m, EditL L, VmP t, const float* __restrict__ rays,
+                                                                        const int* __restrict__ act, int M, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long total = limit_rows(M);
+    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long base = v - lane;
+    if (base >= total) return;                                       // wave-uniform
+    const bool valid = v < total;
+    const int sid = act[valid ? v : total - 1];
+    const int r = sid / m.S, k = sid - r * m.S;
+    const RayG g = load_ray(rays, r, m);
+    const float z = sample_z(g, m, k, 0.f);
+    float p[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+    edit_density_grad_wave(t, L, p, valid, m.lo, m.inv2, m.shift, base, total, out, nullptr);
+}
+
+static int edit_grad_table_check(const clift_vm_t* h_dens, const char* who) {
+    CLIFT_REQUIRE(h_dens != nullptr, "%s: NULL table record", who);
+    CLIFT_REQUIRE(h_dens->comps > 0 && h_dens->comps % 4 == 0, "%s: comps must be a positive multiple of 4 (got %d)", who, h_dens->comps);
+    CLIFT_REQUIRE(h_dens->res[0] >= 1 && h_dens->res[1] >= 1 && h_dens->res[2] >= 1, "%s: table sizes must be positive", who);
+    return 0;
+}
+
+extern "C" int clift_edit_list_density_grad_points(const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens, const float* pts, int ldp,
+                                                   long n, const float* h_lo3, const float* h_inv2, float shift, float* out,
+                                                   unsigned char* state, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_density_grad_points", &L)) return 1;
+    if (edit_grad_table_check(h_dens, "clift_edit_list_density_grad_points")) return 1;
+    CLIFT_REQUIRE(h_lo3 != nullptr && h_inv2 != nullptr, "clift_edit_list_density_grad_points: NULL lo / inv2");
+    CLIFT_REQUIRE(ldp >= 3, "clift_edit_list_density_grad_points: ldp must be >= 3 (got %d)", ldp);
+    CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "clift_edit_list_density_grad_points: %ld rows, must be in [0, 2^36)", n);
+    if (n == 0) return 0;
+    CLIFT_REQUIRE(pts != nullptr && out != nullptr, "clift_edit_list_density_grad_points: NULL pts or out");
+    k_edit_list_density_grad_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, pts, ldp, n, make_float3(h_lo3[0], h_lo3[1], h_lo3[2]),
+                                                                            make_float3(h_inv2[0], h_inv2[1], h_inv2[2]), shift, out, state);
+    return clift_check_launch("clift_edit_list_density_grad_points");
+}
+
+extern "C" int clift_edit_list_density_grad_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens,
+                                                   const float* rays, const int* act_idx, int M, float* out, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_density_grad_active", &L)) return 1;
+    if (edit_grad_table_check(h_dens, "clift_edit_list_density_grad_active")) return 1;
+    CLIFT_REQUIRE(h_m != nullptr, "clift_edit_list_density_grad_active: NULL march record");
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_density_grad_active: n_samples must be positive (got %d)", h_m->n_samples);
+    if (M <= 0) return 0;
+    CLIFT_REQUIRE(rays != nullptr && act_idx != nullptr && out != nullptr, "clift_edit_list_density_grad_active: NULL rays, act_idx or out");
+    k_edit_list_density_grad_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens), rays, act_idx, M, out);
+    return clift_check_launch("clift_edit_list_density_grad_active");
 }

@@ -168,11 +168,12 @@ class EditProgram:
     def record_bytes(self):
         return b"".join(e.record_bytes() for e in self.edits)
 
-    def _walk(self, points, dirs):
+    def _walk(self, points, dirs, jac=False):
         p = np.array(points, dtype=np.float64)
         d = None if dirs is None else np.array(dirs, dtype=np.float64)
         dead = np.zeros(p.shape[0], dtype=bool)
         hops = np.zeros(p.shape[0], dtype=np.uint8)
+        J = np.tile(np.eye(3), (p.shape[0], 1, 1)) if jac else None
         for e in reversed(self.edits):
             dead |= e.killed(p)                           # (a killed point is not walked further: its p stays where the walk stopped)
             if e.mode >= DUPLICATE:
@@ -180,8 +181,10 @@ class EditProgram:
                 p[mov] = p[mov] @ e.M.T + e.t
                 if d is not None:
                     d[mov] = d[mov] @ e.dir_inv.T
+                if J is not None:
+                    J[mov] = e.M @ J[mov]
                 hops[mov] += 1
-        return p, d, dead, hops
+        return (p, d, dead, hops, J) if jac else (p, d, dead, hops)
 
     def source_points(self, points, dirs=None):
         """Where (n, 3) fp64 world points are finally looked up -- and, with ``dirs``, (points, view directions).  Rows of killed points
@@ -191,6 +194,15 @@ class EditProgram:
 
     def killed(self, points):
         return self._walk(points, None)[2]
+
+    def jacobians(self, points):
+        """The chain of the walk at (n, 3) world points, fp64 on the host: -> (source points (n, 3), J (n, 3, 3), state (n,) uint8 as
+        ``apply_to_points`` gives it).  A point that the edits i_1 .. i_h remapped, in walk order, is looked up at p' = J p + b with
+        J = M_{i_h} ... M_{i_1} (the identity for h = 0; for a killed point the product up to where its walk stopped).  J is piecewise
+        constant in p, so the world gradient of the edited density is J^T times the field's world gradient at p' -- J^T, not an inverse:
+        the maps need not be rotations."""
+        p, _, dead, hops, J = self._walk(np.asarray(_host(points), dtype=np.float64).reshape(-1, 3), None, jac=True)
+        return p, J, hops | np.where(dead, np.uint8(STATE_KILLED), np.uint8(0))
 
     def apply_to_points(self, points, dirs=None, backend="device"):
         """The walk over arbitrary world points (n, 3), with view directions (n, 3) or without: -> (source points, source directions or

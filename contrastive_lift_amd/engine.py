@@ -715,6 +715,7 @@ class RenderCtx:
         self.N = self.S = self.M = 0
         self.capped = False                  # a sync-free chunk: M is the capacity, the row count stays on the device (ray_start[N])
         self.edited = False                  # sigma came from a caller's launch (the edit renders): xa may hold remapped positions
+        self.edit_program = None             # the resolved edit.EditProgram of an edit pass (a single Edit: a program of one)
         self.white_bg = self.softmax_mode = self.stop_grad = self.C = self.D = 0
         self.want = (False, False, False)    # (colour, semantic, instance) outputs composited
         self.xa = None                       # (M, 4) positions of the active samples
@@ -1056,6 +1057,27 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
 
 
 # ----------------------------------------------------------------------------- scene-editing forward
+def _edit_density_march(model, renderer, rays, edit, weight_thres):
+    """The march of an edit pass: a single ``Edit`` through clift_edit_density_fwd, anything else (``as_program``) through
+    clift_edit_list_density_fwd.  Returns (context, the kernel-name pattern and the leading edit arguments of that family); the context
+    keeps the resolved program (``edit_program``; a single edit as a program of one, whose list walk is that edit op for op)."""
+    N, st = rays.shape[0], stream()
+    prog = _edit.as_program(edit)
+    if isinstance(edit, _edit.Edit):
+        rec = edit.record()
+        edit_kernel, edit_args = "clift_edit_%s", (C.byref(rec),)
+    else:
+        rec = prog.records()
+        edit_kernel, edit_args = "clift_edit_list_%s", (rec, len(prog))
+
+    def density_fwd(ms, vd, sigma):
+        call(edit_kernel % "density_fwd", C.byref(ms), *edit_args, C.byref(vd), ptr(rays), N, ptr(sigma), st)
+
+    ctx = _density_march(model, renderer, rays, None, density_fwd=density_fwd, weight_thres=weight_thres)
+    ctx.edit_program = prog
+    return ctx, edit_kernel, edit_args
+
+
 @torch.no_grad()
 def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     """The reference's edit renders (renderer.py:303-623: forward_delete / _extract / _duplicate / _manipulate) for one resolved edit
@@ -1076,18 +1098,7 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
         raise NotImplementedError("edit_forward: a semantic / instance head on its own VM grid is not supported (xyz MLP heads only)")
     views = model.named_views()
     N, dev, st = rays.shape[0], rays.device, stream()
-    if isinstance(edit, _edit.Edit):
-        rec = edit.record()
-        edit_kernel, edit_args = "clift_edit_%s", (C.byref(rec),)
-    else:
-        prog = _edit.as_program(edit)
-        rec = prog.records()
-        edit_kernel, edit_args = "clift_edit_list_%s", (rec, len(prog))
-
-    def density_fwd(ms, vd, sigma):
-        call(edit_kernel % "density_fwd", C.byref(ms), *edit_args, C.byref(vd), ptr(rays), N, ptr(sigma), st)
-
-    ctx = _density_march(model, renderer, rays, None, density_fwd=density_fwd, weight_thres=weight_thres)
+    ctx, edit_kernel, edit_args = _edit_density_march(model, renderer, rays, edit, weight_thres)
     ms, M = ctx.ms, ctx.M
     Ccls = model.num_semantic_classes
     D = model.dim_feature_instance if model.render_instance_mlp is not None else 0
@@ -1434,16 +1445,26 @@ def density_grad_points(model, xyz, world=True, renderer=None):
 def _surface_launches(model, ctx, q):
     """The two launches of the surface pass over a march context whose xa is filled: the world gradient at the active samples, then the
     per-ray median hit and normal sums."""
-    N, M, dev = ctx.N, ctx.M, ctx.rays.device
+    q = _surface_quantile(q)
+    G = None
+    if ctx.M > 0:
+        views = model.named_views()
+        vd = vm_struct(views, "density", ctx.res)
+        G = torch.empty((ctx.M, 4), dtype=torch.float32, device=ctx.rays.device)
+        call("clift_density_grad_points", C.byref(vd), ptr(ctx.xa), 4, ctx.M, float(ctx.ms.density_shift), ctx.ms.inv_ext2, ptr(G), stream())
+    return _ray_surface_launch(ctx, q, G)
+
+
+def _surface_quantile(q):
     q = float(q)
     if not 0.0 < q < 1.0:
         raise _lib.CliftError(f"surface outputs: q must lie in (0, 1), got {q}")
-    G = None
-    if M > 0:
-        views = model.named_views()
-        vd = vm_struct(views, "density", ctx.res)
-        G = torch.empty((M, 4), dtype=torch.float32, device=dev)
-        call("clift_density_grad_points", C.byref(vd), ptr(ctx.xa), 4, M, float(ctx.ms.density_shift), ctx.ms.inv_ext2, ptr(G), stream())
+    return q
+
+
+def _ray_surface_launch(ctx, q, G):
+    """clift_ray_surface over what the context's march stored and the world gradients G (M, 4) at its active samples (None for M = 0)."""
+    N, M, dev = ctx.N, ctx.M, ctx.rays.device
     depth = torch.empty((N,), dtype=torch.float32, device=dev)
     k_med = torch.empty((N,), dtype=torch.int32, device=dev)
     nrm = torch.empty((N, 4), dtype=torch.float32, device=dev)
@@ -1460,14 +1481,14 @@ def surface_from_ctx(model, renderer, ctx, q=0.5):
     stored: dict(depth_median (N,), hit (N,) bool, k_median (N,) int32, normals (N, 3) = sum_k w_k n_k, un-normalised, points (N, 3) =
     o + depth_median d; depth_median and k_median are 0 and -1 where hit is False).  Two launches; the context is only read.
     Refused: a sync-free (capped) context, whose row count never reached the host, and a context of ``edit_forward``, where the gradient at a
-    remapped sample would have to be turned back through the edit."""
+    remapped sample has to be turned back through the edit: ``edit_surface_from_ctx`` does that."""
     if not isinstance(ctx, RenderCtx) or ctx.ms is None:
         raise _lib.CliftError("surface_from_ctx: not a context of render_forward / feature_forward")
     if ctx.capped:
         raise _lib.CliftError("surface_from_ctx: a sync-free (capped) context is not supported: its active-sample count stays on the device")
     if ctx.edited:
-        raise _lib.CliftError("surface_from_ctx: a context of edit_forward is not supported: normals and median depth under a scene edit "
-                              "are out of scope (the gradient at a remapped sample would have to be turned back through the edit)")
+        raise _lib.CliftError("surface_from_ctx: a context of edit_forward is not supported here (the gradient at a remapped sample has to be "
+                              "turned back through the edit): use edit_surface_from_ctx")
     if ctx.M > 0 and ctx.xa is None:
         raise _lib.CliftError("surface_from_ctx: the context holds no positions of its active samples (xa)")
     return _surface_launches(model, ctx, q)
@@ -1483,6 +1504,67 @@ def surface_forward(model, renderer, rays, jitter=None, q=0.5):
         ctx.xa = torch.empty((ctx.M, 4), dtype=torch.float32, device=rays.device)
         call("clift_active_xyz", C.byref(ctx.ms), ptr(rays), ptr(jitter), ptr(ctx.act_idx), ctx.M, ptr(ctx.xa), stream())
     out = _surface_launches(model, ctx, q)
+    out["depth"], out["opacity"] = ctx.ray_out[:, 1], ctx.ray_out[:, 0]
+    return out, ctx
+
+
+# ----------------------------------------------------------------------------- surface outputs of an edited scene
+@torch.no_grad()
+def edit_density_grad_points(model, renderer, xyz_world, edit, want_state=False):
+    """(n, 4) rows [gx, gy, gz, sigma_raw] at WORLD points of the scene ``edit`` describes (an ``edit.Edit``, an ``edit.EditProgram`` or a
+    sequence of edits): the world gradient of the edited raw density, J^T g' with J the product of the maps of the edits that remapped the
+    point and g' ``density_grad_points(world=True)`` at the point the walk ends at, and the raw density there.  A killed point gets a row
+    of zeros.  No aabb test: a point (or its source) outside ``renderer``'s box reads zero padding.  ``want_state``: also the (n,) uint8
+    state of ``EditProgram.apply_to_points``."""
+    x = _points(xyz_world)
+    reset_rows_limit(x.device)
+    prog = _edit.as_program(edit)
+    ms = march_struct(renderer, model)
+    views = model.named_views()
+    vd = vm_struct(views, "density", grid_res(views))
+    n = x.shape[0]
+    out = torch.empty((n, 4), dtype=torch.float32, device=x.device)
+    state = torch.empty((n,), dtype=torch.uint8, device=x.device) if want_state else None
+    call("clift_edit_list_density_grad_points", prog.records(), len(prog), C.byref(vd), ptr(x), x.shape[1], n, ms.lo, ms.inv_ext2,
+         float(ms.density_shift), ptr(out), ptr(state), stream())
+    return (out, state) if want_state else out
+
+
+def _edit_surface_launches(model, ctx, q):
+    """The surface pass of an edited march: the gradient of the EDITED density at the active samples (one launch, the walk recomputed from
+    the rays -- no xa is needed), then the unchanged per-ray launch."""
+    q = _surface_quantile(q)
+    G = None
+    if ctx.M > 0:
+        views = model.named_views()
+        vd = vm_struct(views, "density", ctx.res)
+        prog = ctx.edit_program
+        G = torch.empty((ctx.M, 4), dtype=torch.float32, device=ctx.rays.device)
+        call("clift_edit_list_density_grad_active", C.byref(ctx.ms), prog.records(), len(prog), C.byref(vd), ptr(ctx.rays), ptr(ctx.act_idx),
+             ctx.M, ptr(G), stream())
+    return _ray_surface_launch(ctx, q, G)
+
+
+@torch.no_grad()
+def edit_surface_from_ctx(model, renderer, ctx, q=0.5):
+    """``surface_from_ctx`` for a context that ``edit_forward`` returned: the same dict (depth_median, hit, k_median, normals, points), the
+    normals from the gradient of the edited density -- at a remapped sample the field's gradient turned back through the edits, J^T g'
+    (DESIGN.md 6h).  Two launches; the context is only read.  Any other context is refused: it belongs to ``surface_from_ctx``."""
+    if not isinstance(ctx, RenderCtx) or ctx.ms is None or not ctx.edited or ctx.edit_program is None:
+        raise _lib.CliftError("edit_surface_from_ctx: not a context of edit_forward (surface_from_ctx takes the context of an unedited pass)")
+    if ctx.capped:
+        raise _lib.CliftError("edit_surface_from_ctx: a sync-free (capped) context is not supported: its active-sample count stays on the device")
+    return _edit_surface_launches(model, ctx, q)
+
+
+@torch.no_grad()
+def edit_surface_forward(model, renderer, rays, edit, q=0.5, weight_thres=0.0):
+    """Geometry of an edited scene only: the edit's density forward, the march and the two surface launches -- no head runs and no xa is
+    made, so a field whose semantic / instance head sits on its own VM grid is fine here.  ``weight_thres`` as in ``edit_forward``.
+    Returns (the dict of ``edit_surface_from_ctx`` plus depth = the expected distance and opacity, context)."""
+    rays, _ = _check_rays(rays, None)
+    ctx, _, _ = _edit_density_march(model, renderer, rays, edit, weight_thres)
+    out = _edit_surface_launches(model, ctx, q)
     out["depth"], out["opacity"] = ctx.ray_out[:, 1], ctx.ray_out[:, 0]
     return out, ctx
 

@@ -58,6 +58,26 @@ def render_rays_surface(model, renderer, rays, chunk, white_bg=False, q=0.5):
     return tuple(torch.cat(x, 0) for x in outs)
 
 
+@torch.no_grad()
+def render_rays_edit_surface(model, renderer, rays, chunk, white_bg=False, edit=None, weight_thres=0.0, q=0.5):
+    """``render_rays_edit`` plus the surface outputs of the edited scene from every chunk's march (engine.edit_surface_from_ctx, two more
+    launches per chunk): the seven outputs of ``render_rays_surface`` -- rgb, semantics, instances, distance, distance_median, hit as float
+    0 / 1, normals -- of which the first four are ``render_rays_edit``'s own.  With ``edit``, ``weight_thres`` and ``q`` bound
+    (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``."""
+    if edit is None:
+        raise ValueError("render_rays_edit_surface: an edit is required")
+    outs = [[] for _ in range(7)]
+    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
+    for i in range(0, rays.shape[0], chunk):
+        o, ctx = engine.edit_forward(model, renderer, rays[i:i + chunk], edit, bool(white_bg), weight_thres=weight_thres)
+        s = engine.edit_surface_from_ctx(model, renderer, ctx, q)
+        for dst, x in zip(outs, (o["rgb"], o["semantics"], o["instances"], o["depth"].clone(), s["depth_median"], s["hit"].to(torch.float32),
+                                 s["normals"].contiguous())):
+            dst.append(x)
+        del ctx
+    return tuple(torch.cat(x, 0) for x in outs)
+
+
 def tile_bounds(n, world):
     """Contiguous row-tile boundaries of n rays over `world` ranks (sizes differ by at most one)."""
     return [(n * r) // world for r in range(world + 1)]

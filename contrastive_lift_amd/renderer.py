@@ -190,6 +190,11 @@ class TensoRFRenderer(nn.Module):
             inst = torch.zeros((rays.shape[0], 0), dtype=torch.float32, device=rays.device)
         return out["rgb"], out["semantics"], inst, out["depth"]
 
+    def forward_edit_surface(self, tensorf, rays, edit, q=0.5):
+        """``forward_surface`` of the scene ``edit`` describes (an ``edit.Edit``, an ``edit.EditProgram`` or a sequence of edits): the same
+        dict, the normals from the gradient of the edited density (engine.edit_surface_forward).  No head runs, no gradient."""
+        return engine.edit_surface_forward(tensorf, self, rays, edit, q)[0]
+
     def forward_delete(self, tensorf, rays, white_bg, bbox_deletion):
         """renderer.py:303-376: the scene without what is inside ``bbox_deletion`` ({"extent", "position", "orientation"}, axes = columns
         of orientation).  Returns (rgb_map, semantic_map, instance_map, depth_map); no gradient."""

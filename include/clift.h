@@ -802,6 +802,31 @@ int clift_ray_surface(const clift_march_t* h_m, const float* rays, const float* 
                       const int* ray_start, const int* act_idx, int M, const float* G, float q, float* depth_med, int* k_med, float* normal,
                       clift_stream_t s);
 
+/* ---- surface outputs of an EDITED scene (a further ABI 27 addition; csrc/edit.hip): the gradient of the raw density of the
+ * scene an edit program describes.  The walk of clift_edit_list_points remaps a world point p h times, by the edits i_1 .. i_h in walk order,
+ * and ends at p' = J p + b with J = M_{i_h} ... M_{i_1} (the identity for h = 0; formed in fp32, every multiply and add rounded separately).
+ * The edited raw density is sigma_e(p) = sigma_raw(p'), and away from box faces its world gradient is J^T g', g' the world gradient of the
+ * unedited field at p' (clift_density_grad_points with h_inv2).  J^T, not an inverse: this holds for every affine map, rigid or not.  The
+ * step of sigma_e across a box face is not part of the gradient.
+ *
+ * clift_edit_list_density_grad_points: pts (n, ldp >= 3) world points; h_lo3, h_inv2 (host, 3 floats each: lo and inv_ext2 of
+ *   clift_march_t) normalise the walked point, xn = (p' - lo) * inv2 - 1 with separately rounded ops; out (n, 4) fp32 rows
+ *   [gx, gy, gz, sigma_raw(p')], a killed row all zeros (no table is read for it); state (n) uint8 or NULL, the byte of clift_edit_list_points.
+ *   Column 3 of a row that is not killed carries the bits of clift_density_points(activation = 0) at xn; a row that is neither remapped nor
+ *   killed carries all four columns of clift_density_grad_points at xn.  No aabb test: a point outside the box reads zero padding.
+ *   Errors: the program's, comps not a positive multiple of 4, a table size < 1, ldp < 3, n < 0 or >= 2^36, a NULL buffer.  n == 0 returns 0
+ *   without a launch.
+ * clift_edit_list_density_grad_active: the same for the active samples of a march under the program (the record and rays of
+ *   clift_edit_list_active, act_idx (M) of clift_compact_fill): the point of row s is formed from its ray and sample index with the very
+ *   operations of clift_edit_list_active, lo / inv_ext2 / density_shift come from the march record; out (M, 4).  The same world point gives
+ *   the same bits in both entry points.  Rows past the dynamic row limit are not written.  M <= 0 returns 0 without a launch.
+ * Both: one writer per element, no atomics -- two runs give the same bits. */
+int clift_edit_list_density_grad_points(const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens, const float* pts, int ldp, long n,
+                                        const float* h_lo3, const float* h_inv2, float shift, float* out, unsigned char* state,
+                                        clift_stream_t s);
+int clift_edit_list_density_grad_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens,
+                                        const float* rays, const int* act_idx, int M, float* out, clift_stream_t s);
+
 /* ---- optimiser plumbing on flat fp32 ranges: torch.optim.Adam semantics (L2 weight decay folded into the
  * gradient; bias correction with step >= 1) and the slow-net EMA (trainer T:325-329). */
 int clift_adam(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,

@@ -3,7 +3,7 @@
 
     python inference/edit_scene.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt --bboxes bboxes.pkl --instance ID
                                    --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz] [--pad 0.0]
-                                   [--render_trajectory] [--image_dim H W] [--weight_thres 0]
+                                   [--render_trajectory] [--image_dim H W] [--weight_thres 0] [--save_surface [--surface_quantile 0.5]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
@@ -12,7 +12,9 @@ reference's forward_duplicate / forward_manipulate arithmetic, which is not rigi
 ``TensoRFRenderer.forward_duplicate`` / ``forward_manipulate``).  Fitted boxes hug the filtered points: ``--pad`` grows the box on every
 side.  Checkpoint loading and the frame loop are those of ``inference/render_panopli.py``; under torch.distributed.run every frame is
 rendered as row-tiles over the ranks.  Writes ``rgb/*.png``, ``pred_semantics/*.png`` (uint8) and ``depth/*.npy`` under
-``runs/<scene>_<test|trajectory>_<experiment>_edit_<op>_<id>/``.
+``runs/<scene>_<test|trajectory>_<experiment>_edit_<op>_<id>/``.  ``--save_surface`` adds the surface outputs of the EDITED scene
+(DESIGN.md 6h), in the files of ``inference/render_panopli.py --save_surface``: ``surface/<frame>.npz`` (depth_median, hit, normals) and
+``vis_normals/<frame>.png``; ``--surface_quantile Q`` moves the hit from the median (0.5) to another quantile of the ray's weight.
 
 ``--script FILE.json`` applies up to 8 edits in ONE render (``edit.EditProgram``), in file order.  The file holds a list of
 ``{"instance": id, "op": "delete|extract|copy|move", "translate": [x, y, z], "rotate_deg": [rx, ry, rz], "pad": p, "at": "moved"}``;
@@ -87,24 +89,33 @@ def resolve_program(boxes, entries):
     return ed.EditProgram(edits)
 
 
-def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0):
+def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
+                          save_surface=False, surface_quantile=0.5):
     out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}")
     device, rank = rp.distributed_device(device)
     scene, model, renderer = rp.load_for_inference(config, device)
     H, W = scene.image_dim
-    render_fn = functools.partial(inf.render_rays_edit, edit=edit, weight_thres=float(weight_thres))
+    if save_surface:
+        render_fn = functools.partial(inf.render_rays_edit_surface, edit=edit, weight_thres=float(weight_thres), q=float(surface_quantile))
+    else:
+        render_fn = functools.partial(inf.render_rays_edit, edit=edit, weight_thres=float(weight_thres))
     if rank == 0:
         for d in ("rgb", "pred_semantics", "depth"):
             (out / d).mkdir(exist_ok=True, parents=True)
     with torch.no_grad():
         for name, rays, K_frame in rp.scene_frames(scene, trajectory_name, test_only):
-            p_rgb, p_sem, _, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=render_fn)
+            p_rgb, p_sem, _, p_dist, *p_surface = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg,
+                                                                          render_fn=render_fn)
             if rank != 0:
                 continue
             rgb = (p_rgb.reshape(H, W, 3).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
             Image.fromarray(rgb).save(out / "rgb" / f"{name}.png")
             Image.fromarray(p_sem.argmax(dim=1).reshape(H, W).cpu().numpy().astype(np.uint8)).save(out / "pred_semantics" / f"{name}.png")
             np.save(out / "depth" / f"{name}.npy", inf.distance_to_depth(K_frame, p_dist.view(H, W)).reshape(H, W).cpu().numpy())
+            if save_surface:
+                p_dmed, p_hit, p_nrm = p_surface
+                rp.write_surface_frame(out, name, inf.distance_to_depth(K_frame, p_dmed.view(H, W)).reshape(H, W), (p_hit > 0.5).reshape(H, W),
+                                       p_nrm.reshape(H, W, 3))
     return out
 
 
@@ -124,6 +135,11 @@ def main(argv=None):
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384])
     ap.add_argument("--weight_thres", type=float, default=0.0,
                     help="evaluate the heads where w > this (0: every sample with weight, like the reference's edit renders; 1e-4: the plain render's threshold)")
+    ap.add_argument("--save_surface", action="store_true",
+                    help="also write surface/<frame>.npz (depth_median, hit, normals) and vis_normals/<frame>.png of the EDITED scene, as "
+                         "inference/render_panopli.py --save_surface does for the unedited one")
+    ap.add_argument("--surface_quantile", type=float, default=0.5, metavar="Q",
+                    help="--save_surface: the hit is where the ray has lost this share of its transmittance (0.5: the median depth)")
     args = ap.parse_args(argv)
     if args.script is not None and (args.instance is not None or args.op is not None):
         ap.error("--script holds the edits: give it without --instance / --op")
@@ -140,7 +156,8 @@ def main(argv=None):
             the_edit, tag = resolve_program(boxes, json.load(f)), f"script_{Path(args.script).stem}"
     else:
         the_edit, tag = resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad), f"{args.op}_{args.instance}"
-    print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres))
+    print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
+                                save_surface=args.save_surface, surface_quantile=args.surface_quantile))
 
 
 if __name__ == "__main__":

@@ -116,6 +116,20 @@ def scene_frames(scene, trajectory_name, test_only):
     return ((n, r, scene.intrinsics[0]) for n, r in scene.trajectory_set(trajectory_name))
 
 
+def write_surface_frame(out, frame_name, depth_median, hit, normals):
+    """The files of ``--save_surface`` for one frame (also of inference/edit_scene.py): ``surface/<frame>.npz`` with depth_median (H, W)
+    float32 (a z-depth, like depth/), hit (H, W) bool and normals (H, W, 3) float32 (the un-normalised sums of w n), and
+    ``vis_normals/<frame>.png``: (n / |n| + 1) / 2 where the ray hit, black elsewhere.  Tensors on any device."""
+    for d in ("surface", "vis_normals"):
+        (out / d).mkdir(exist_ok=True)
+    hit = hit.cpu().numpy()
+    nrm = normals.cpu().numpy().astype(np.float32)
+    np.savez(out / "surface" / f"{frame_name}.npz", depth_median=depth_median.cpu().numpy().astype(np.float32), hit=hit, normals=nrm)
+    unit = nrm / np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-20)
+    vis = np.where(hit[..., None], (unit + 1.0) * 0.5, 0.0)
+    Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_normals" / f"{frame_name}.png")
+
+
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
                               cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
                               meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn", save_surface=False, pointcloud_depth="expected"):
@@ -188,15 +202,8 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
         vis = np.concatenate([rgbs[j].reshape(H, W, 3).cpu().numpy(), pal[sem_id], pal[sur_id], np.repeat(d[..., None], 3, -1)], 1)
         Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_semantics_and_surrogate" / name)
     if save_surface:
-        for d in ("surface", "vis_normals"):
-            (out / d).mkdir(exist_ok=True)
         for j, frame_name in enumerate(names):
-            hit = hits[j].reshape(H, W).cpu().numpy()
-            nrm = normals[j].reshape(H, W, 3).numpy().astype(np.float32)
-            np.savez(out / "surface" / f"{frame_name}.npz", depth_median=depths_med[j].reshape(H, W).numpy().astype(np.float32), hit=hit, normals=nrm)
-            unit = nrm / np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-20)
-            vis = np.where(hit[..., None], (unit + 1.0) * 0.5, 0.0)
-            Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_normals" / f"{frame_name}.png")
+            write_surface_frame(out, frame_name, depths_med[j].reshape(H, W), hits[j].reshape(H, W), normals[j].reshape(H, W, 3))
     if save_pointcloud:
         # the layout visualize_bboxes.py:269-275 loads: points (P, 3), instances (P,) = the ids written to pred_surrogateid (0 = stuff)
         cloud = {"points": torch.cat(points, 0).numpy().astype(np.float32),
