@@ -1010,7 +1010,10 @@ __global__ __launch_bounds__(256) void k_composite_bwd_sample_act(const float* _
             else if (c < 2 * E) { if (d1) d1[c - E] = g; }
             if (!stop_grad) gw = fmaf(inst_s[(size_t)i * D + c], e[3 + C + c], gw);
         }
-        for (int c = E; c < ld_inst; ++c) { if (d0) d0[c] = 0.f; if (d1) d1[c] = 0.f; }
+        // every column the loop above did not reach is zero: the pads [E, ld_inst), and the columns of a half that D does not fill
+        // (D < E: dpre_i0 [D, E) and all of dpre_i1; E < D < 2 E: dpre_i1 [D - E, E))
+        if (d0) for (int c = min(D, E); c < ld_inst; ++c) d0[c] = 0.f;
+        if (d1) for (int c = max(min(D, 2 * E) - E, 0); c < ld_inst; ++c) d1[c] = 0.f;
     }
     if (g_w) g_w[sid] = gw;
 }
@@ -1078,12 +1081,15 @@ __global__ __launch_bounds__(256) void k_composite_bwd_sample_act16(const float*
     } else if (l <= 14) {
         if (inst_s)
             for (int k = 0; k < 4; ++k) {
-                const int c = c0 + k;                 // instance column: [0, E) -> dpre_i0, [E, 2E) -> dpre_i1, pads zero
+                const int c = c0 + k;                 // instance column: [0, E) -> dpre_i0, [E, 2E) -> dpre_i1, everything else zero
+                if (c >= D) continue;
                 if (c < E) { if (dpre_i0) dpre_i0[(size_t)i * ld_inst + c] = g[k]; }
-                else if (c < 2 * E && c < D) { if (dpre_i1) dpre_i1[(size_t)i * ld_inst + c - E] = g[k]; }
+                else if (c < 2 * E) { if (dpre_i1) dpre_i1[(size_t)i * ld_inst + c - E] = g[k]; }
             }
-        if (l == 13 && inst_s)
-            for (int c = E; c < ld_inst; ++c) { if (dpre_i0) dpre_i0[(size_t)i * ld_inst + c] = 0.f; if (dpre_i1) dpre_i1[(size_t)i * ld_inst + c] = 0.f; }
+        if (l == 13 && inst_s) {                      // the pads [E, ld_inst) and the columns of a half that D does not fill, as in the scalar form
+            if (dpre_i0) for (int c = min(D, E); c < ld_inst; ++c) dpre_i0[(size_t)i * ld_inst + c] = 0.f;
+            if (dpre_i1) for (int c = max(min(D, 2 * E) - E, 0); c < ld_inst; ++c) dpre_i1[(size_t)i * ld_inst + c] = 0.f;
+        }
     }
 }
 

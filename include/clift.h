@@ -520,7 +520,11 @@ int clift_composite_bwd(const float* w, const int* ray_start, const int* act_idx
  * PRE-activation outputs of the heads' last layers, in the zero-padded rows their backward kernels take -- dpre_rgb (M, ld_rgb): sigmoid backward
  * (tensoRF.py:398); dpre_sem (M, ld_sem): sem_kind 2 = softmax backward over the row (tensoRF.py:37,593), 0 = identity; dpre_i0 / dpre_i1
  * (M, ld_inst): instance columns [0, E) / [E, 2E) (fast / slow half, tensoRF.py:505-511; each nullable) -- so no clift_rows_act_bwd launch
- * follows.  The head buffers rgb_s / sem_s / inst_s must be given for the heads whose gradient is wanted. */
+ * follows.  The head buffers rgb_s / sem_s / inst_s must be given for the heads whose gradient is wanted.
+ * Every column of [0, ld) of a row below M is written when its head is given.  E >= 1 and D <= 2 E (anything else is refused); D need be
+ * neither E nor 2 E: a half that D does not fill is zero in the columns D does not reach, like the pads -- D < E leaves dpre_i0 [D, ld_inst)
+ * and all of dpre_i1 zero, E < D < 2 E leaves dpre_i1 [D - E, ld_inst) zero -- so the next launch can take the rows as a gradient operand
+ * as they are. */
 int clift_composite_bwd_act(const float* w, const int* act_idx, int N, int S, int M, int C, int D, const float* rgb_s, const float* sem_s,
                             const float* inst_s, const float* rgb_raw, const float* sem_raw, int softmax_mode, int white_bg, int stop_grad,
                             const float* g_rgb, const float* g_sem, const float* g_inst, float* ge_work, int sem_kind, float* dpre_rgb,

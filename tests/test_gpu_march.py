@@ -40,12 +40,13 @@ def _d(a, dtype=torch.float32):
 
 class Table:
     """Rows of ``yardstick | device error | bound``; ``hold`` records a row and remembers a break; ``close`` prints the worst row of each
-    (kernel, quantity, call) and every break."""
+    (kernel, quantity, call) and every break.  ``cases``: the case module whose references and bounds apply."""
 
-    def __init__(self):
-        self.rows, self.broken = {}, []
+    def __init__(self, cases=mc):
+        self.rows, self.broken, self.cases = {}, [], cases
 
     def hold(self, case, q, dev, how="raw"):
+        mc = self.cases
         yard, err, bnd = mc.yardstick(case, q), mc.max_error(dev, mc.reference(case)[q]), mc.bound_for(case, q)
         row = f"{case.kernel:7s} {case.name:34s} {q:8s} {how:12s} | {yard:9.3e} | {err:9.3e} | {bnd:9.3e}"
         key, ratio = (case.kernel, q, how), (err / bnd if bnd > 0 else (0.0 if err == 0 else float("inf")))
