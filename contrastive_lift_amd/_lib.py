@@ -157,6 +157,8 @@ _SIGNATURES = {
     "clift_cc_label": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
     "clift_density_grad_points": ([_P, _P, _I, _L, _F, _P, _P, _P], C.c_int),
     "clift_ray_surface": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P, _P], C.c_int),
+    "clift_sample_slots": ([_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _L, _P, _P], C.c_int),
+    "clift_ray_layers": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P], C.c_int),
     "clift_edit_list_density_grad_points": ([_P, _I, _P, _P, _I, _L, _P, _P, _F, _P, _P, _P], C.c_int),
     "clift_edit_list_density_grad_active": ([_P, _P, _I, _P, _P, _P, _I, _P, _P], C.c_int),
     "clift_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P], C.c_int),

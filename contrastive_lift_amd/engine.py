@@ -15,6 +15,7 @@ import contextlib
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -727,6 +728,8 @@ class RenderCtx:
         self.soak = None                     # SOAK_KEEP: references to the appearance chain's intermediates
         self.sem_acts = self.inst_fast_acts = self.inst_slow_acts = None        # hidden activations of the xyz heads
         self.sem_grid = self.inst_grid = None                                   # state of a head on its own grid (grid_head_fwd)
+        self.slots = self.layer_add = None   # layers_forward: the slot of every list row; with use_delta the world positions added to the features
+        self.M_render = 0                    # layers_forward: the length of the march's own list (w > threshold), which its alpha-list replaced
 
 
 INT_MAX = 2 ** 31 - 1
@@ -1506,6 +1509,65 @@ def surface_forward(model, renderer, rays, jitter=None, q=0.5):
     out = _surface_launches(model, ctx, q)
     out["depth"], out["opacity"] = ctx.ray_out[:, 1], ctx.ray_out[:, 0]
     return out, ctx
+
+
+# ----------------------------------------------------------------------------- amodal instance layers
+@torch.no_grad()
+def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, use_delta=False, cap=None):
+    """Per ray and per instance slot of ``table`` (a ``layers.SlotTable``) what that instance covers ALONE, also behind what hides it: the march,
+    its samples listed again by alpha > ``alpha_thres`` (default: renderer.raymarch_weight_thres) -- a sample behind an occluder has w ~ 0 and is
+    in no render's list --, the semantic head and the fast instance net over that list (no appearance chain, no slow net, no compositing), one
+    slot per row (clift_sample_slots) and the per-ray composite that keeps one transmittance per slot (clift_ray_layers).
+    Returns (dict(layers (N, K + 1, 4) rows [A, V, Z, zf], column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed), context).
+    The context holds the alpha-list (ray_start, act_idx, M), xa, sem_s, inst_s (the fast half), slots and, with ``use_delta`` (the feature is
+    output + world position; needs 3 feature columns), layer_add.  Refused: a sync-free pass (``cap``), a field without an instance head, a table
+    that does not fit the field.  Edited scenes are out of scope."""
+    if cap is not None:
+        raise _lib.CliftError("layers_forward: a sync-free (capped) pass is not supported: the length of the alpha-list has to reach the host")
+    if model.render_instance_mlp is None:
+        raise ValueError("layers_forward: the field has no instance head")
+    E = int(model.render_instance_mlp.output_channels)
+    if table.num_classes != model.num_semantic_classes:
+        raise ValueError(f"layers_forward: the table knows {table.num_classes} classes, the field {model.num_semantic_classes}")
+    if table.E != E and (table.mode == 1 or table.K > 0):
+        raise ValueError(f"layers_forward: the table expects {table.E} feature columns, the instance head gives {E}")
+    if use_delta and E != 3:
+        raise ValueError(f"layers_forward: use_delta adds world positions to the features, which needs 3 columns (the head gives {E})")
+    rays, jitter = _check_rays(rays, jitter)
+    views = model.named_views()
+    ctx = _density_march(model, renderer, rays, jitter)
+    N, S, dev, st = ctx.N, ctx.S, rays.device, stream()
+    K = table.K
+    # the same fp32 threshold for the count and for the fill, however torch compares a tensor with a Python number
+    thres = float(np.float32(renderer.raymarch_weight_thres if alpha_thres is None else alpha_thres))
+    n_listed = (ctx.alpha > thres).sum(1, dtype=torch.int32)
+    ray_start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    call("clift_scan_counts", ptr(n_listed), N, ptr(ray_start), st)
+    M = int(ray_start[N].item())
+    act_idx = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
+    call("clift_compact_fill", ptr(ctx.alpha), ptr(ray_start), N, S, thres, ptr(act_idx), st)
+    ctx.M_render, ctx.M, ctx.ray_start, ctx.act_idx = ctx.M, M, ray_start, act_idx
+    ctx.C, ctx.D = model.num_semantic_classes, model.dim_feature_instance
+    ctx.want = (False, False, False)
+    if M > 0:
+        ctx.xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        call("clift_active_xyz", C.byref(ctx.ms), ptr(rays), ptr(jitter), ptr(act_idx), M, ptr(ctx.xa), st)
+        br = Branches(model=model)
+        for slot, chain in _head_chains(model, views, ctx, _head_params(views), (), True):
+            if slot != 3:                   # (3: the slow xyz net, which no slot reads)
+                br.run(slot, chain)
+        br.join()
+        cls_slots, cent = table.on(dev)
+        if use_delta:
+            ctx.layer_add = ((ctx.xa[:, :3] + 1.0) / renderer.inv_box_extent + renderer.bbox_aabb[0]).contiguous()
+        ctx.slots = torch.empty((M,), dtype=torch.int32, device=dev)
+        call("clift_sample_slots", ptr(ctx.sem_s), ctx.C, ctx.C, ptr(ctx.inst_s), ctx.D, E, ptr(ctx.layer_add), 3, ptr(cls_slots), ptr(cent), K,
+             table.mode, M, ptr(ctx.slots), st)
+        ctx.inst_s = ctx.inst_s[:, :E]
+    out = torch.empty((N, K + 1, 4), dtype=torch.float32, device=dev)
+    call("clift_ray_layers", C.byref(ctx.ms), ptr(rays), ptr(jitter), N, ptr(ctx.alpha), ptr(ctx.w), ptr(ray_start), ptr(act_idx) if M > 0 else None,
+         M, ptr(ctx.slots), K, ptr(out), st)
+    return dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M), ctx
 
 
 # ----------------------------------------------------------------------------- surface outputs of an edited scene (DESIGN.md 6h)

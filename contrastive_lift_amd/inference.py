@@ -78,6 +78,24 @@ def render_rays_edit_surface(model, renderer, rays, chunk, white_bg=False, edit=
     return tuple(torch.cat(x, 0) for x in outs)
 
 
+@torch.no_grad()
+def render_rays_layers(model, renderer, rays, chunk, white_bg=False, table=None, alpha_thres=None, use_delta=False):
+    """Chunked ``engine.layers_forward``: the amodal instance layers of the rays under the slot table ``table``
+    (``layers.SlotTable``).  Returns layers (P, K + 1, 4) rows [A, V, Z, zf], opacity (P,), distance (P,) -- the last two of the whole scene, as
+    ``render_rays`` gives them.  A ray's layers depend on that ray alone, so the chunking changes no bit.  ``white_bg`` is accepted and unused
+    (no colour is formed): with ``table``, ``alpha_thres`` and ``use_delta`` bound (functools.partial) it has the ``render_fn`` signature of
+    ``render_rays_sharded``."""
+    if table is None:
+        raise ValueError("render_rays_layers: a slot table is required (layers.SlotTable)")
+    outs = [[], [], []]
+    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
+    for i in range(0, rays.shape[0], chunk):
+        o, ctx = engine.layers_forward(model, renderer, rays[i:i + chunk], table, alpha_thres=alpha_thres, use_delta=use_delta)
+        outs[0].append(o["layers"]); outs[1].append(o["opacity"].clone()); outs[2].append(o["depth"].clone())
+        del ctx
+    return tuple(torch.cat(x, 0) for x in outs)
+
+
 def tile_bounds(n, world):
     """Contiguous row-tile boundaries of n rays over `world` ranks (sizes differ by at most one)."""
     return [(n * r) // world for r in range(world + 1)]
@@ -100,7 +118,7 @@ def render_rays_sharded(model, renderer, rays, chunk, white_bg=False, render_fn=
     # a rank whose tile is empty (fewer rays than ranks) renders one ray so that it knows the output widths, and keeps none
     mine = fn(model, renderer, rays[b[rank]:b[rank + 1]] if n_mine else rays[:1], chunk, white_bg)
     mine = tuple(x[:n_mine] for x in mine)
-    widths = [int(x.shape[1]) if x.dim() == 2 else 1 for x in mine]
+    widths = [int(np.prod(x.shape[1:])) for x in mine]                    # (1 for a per-ray scalar; the layers' (K + 1, 4) rows travel flat)
     packed = torch.cat([x.reshape(n_mine, w) for x, w in zip(mine, widths)], 1)
     cap = max(b[r + 1] - b[r] for r in range(world))                      # equal-size slots: tiles differ by <= 1 ray
     slot = torch.zeros((cap, packed.shape[1]), dtype=packed.dtype, device=packed.device)
@@ -117,7 +135,7 @@ def render_rays_sharded(model, renderer, rays, chunk, white_bg=False, render_fn=
     outs, c = [], 0
     for x, w in zip(mine, widths):
         o = full[:, c:c + w]
-        outs.append(o.contiguous() if x.dim() == 2 else o.reshape(-1).contiguous())
+        outs.append(o.reshape((-1,) + tuple(x.shape[1:])).contiguous())
         c += w
     return tuple(outs)
 

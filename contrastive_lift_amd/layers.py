@@ -1,0 +1,121 @@
+"""Amodal instance layers: the slot table that numbers the instances of a scene once, and what a frame's layers say about
+every instance -- its amodal and visible pixels, how much of it is hidden, which one lies in front along a ray.
+
+A layer array is ``(N, K + 1, 4)`` fp32 from ``engine.layers_forward`` / ``inference.render_rays_layers``: per ray and per column the row
+``[A, V, Z, zf]`` -- the opacity of that column rendered alone, the weight the whole scene gives it, its un-normalised expected distance
+when alone, the distance of its first listed sample.  Columns ``0 .. K - 1`` are the table's instance slots, column ``K`` is the rest
+(stuff, unassigned, out of range).
+"""
+import numpy as np
+import torch
+
+MAX_SLOTS = 255          # clift_ray_layers keeps K + 1 <= 256 columns in the registers of one wave
+
+
+class SlotTable:
+    """The instance slots of a scene: a FIXED numbering of (thing class, centroid index) pairs.
+
+    ``inference.assign_cluster_labels`` numbers the instances of a set of frames by the classes that happen to be present in it (every class
+    is offset by the labels seen before it), so an id means something only together with that set.  A slot table numbers every centroid of
+    every thing class once, in ascending class order, whatever a frame contains: slot ``s`` is centroid ``slot_index[s]`` of class
+    ``slot_class[s]`` in every frame and every chunk, which is what lets layers of different frames be compared.  The two numberings differ
+    as soon as a class with centroids is absent from the frames.
+
+    Attributes: ``K`` slots; ``num_classes``; ``cls_slots`` (num_classes, 2) int32, the (first slot, count) of every class, count 0 for a
+    stuff class or a class without centroids; ``slot_class`` (K) and ``slot_index`` (K) int64; ``centroids`` (K, E) fp32 or None;
+    ``mode`` 0 (nearest centroid) or 1 (the instance outputs are slot scores); ``E`` the feature width the table expects."""
+
+    def __init__(self, num_classes, cls_slots, slot_class, slot_index, centroids, mode, E):
+        self.num_classes = int(num_classes)
+        self.cls_slots = np.ascontiguousarray(cls_slots, dtype=np.int32).reshape(self.num_classes, 2)
+        self.slot_class = np.asarray(slot_class, dtype=np.int64).reshape(-1)
+        self.slot_index = np.asarray(slot_index, dtype=np.int64).reshape(-1)
+        self.K = int(self.slot_class.shape[0])
+        self.mode, self.E = int(mode), int(E)
+        if self.K > MAX_SLOTS:
+            raise ValueError(f"SlotTable: {self.K} slots, the layer kernel holds at most {MAX_SLOTS}")
+        self.centroids = None if centroids is None else np.ascontiguousarray(centroids, dtype=np.float32).reshape(self.K, self.E)
+        self._dev = {}
+
+    @classmethod
+    def from_centroids(cls, centroids, thing_classes, num_classes):
+        """From the dict of an ``all_centroids.pkl`` (class -> (k, E) array): the thing classes below ``num_classes`` that have at least one
+        centroid get consecutive slot ranges in ascending class order."""
+        num_classes = int(num_classes)
+        cls_slots = np.zeros((num_classes, 2), np.int32)
+        slot_class, slot_index, rows, E = [], [], [], None
+        for c in sorted(set(int(c) for c in thing_classes)):
+            if not 0 <= c < num_classes or c not in centroids:
+                continue
+            cent = np.asarray(centroids[c], dtype=np.float32)
+            if cent.size == 0:
+                continue
+            cent = cent.reshape(cent.shape[0], -1)
+            if E is None:
+                E = cent.shape[1]
+            elif cent.shape[1] != E:
+                raise ValueError(f"SlotTable: class {c} has centroids of width {cent.shape[1]}, earlier classes {E}")
+            cls_slots[c] = (len(slot_class), cent.shape[0])
+            slot_class += [c] * cent.shape[0]
+            slot_index += list(range(cent.shape[0]))
+            rows.append(cent)
+        E = 1 if E is None else E
+        return cls(num_classes, cls_slots, slot_class, slot_index, np.concatenate(rows, 0) if rows else np.zeros((0, E), np.float32), 0, E)
+
+    @classmethod
+    def from_scores(cls, thing_classes, num_classes, E):
+        """For models whose instance outputs are slot scores (linear assignment): every thing class gets the range [0, E), a sample's slot is the
+        first maximum of its scores.  The slots are shared by the classes: ``slot_class`` is -1."""
+        num_classes, E = int(num_classes), int(E)
+        cls_slots = np.zeros((num_classes, 2), np.int32)
+        for c in set(int(c) for c in thing_classes):
+            if 0 <= c < num_classes:
+                cls_slots[c] = (0, E)
+        return cls(num_classes, cls_slots, [-1] * E, list(range(E)), None, 1, E)
+
+    def on(self, device):
+        """(cls_slots, centroids or None) as tensors on ``device``, made once per device."""
+        key = str(device)
+        if key not in self._dev:
+            cent = None if self.centroids is None or self.K == 0 else torch.from_numpy(self.centroids).to(device)
+            self._dev[key] = (torch.from_numpy(self.cls_slots).to(device), cent)
+        return self._dev[key]
+
+
+def _check_layers(layers, table=None):
+    if layers.dim() != 3 or layers.shape[2] != 4:
+        raise ValueError(f"layers must be (N, K + 1, 4), got {tuple(layers.shape)}")
+    if table is not None and layers.shape[1] != table.K + 1:
+        raise ValueError(f"layers has {layers.shape[1]} columns, the table {table.K} slots (+ the rest column)")
+
+
+@torch.no_grad()
+def summarise(layers, table, level=0.5):
+    """Per slot of ``table`` over the rays of ``layers`` (N, K + 1, 4) (the rest column is left out), tensors of length K on the layers'
+    device: ``amodal_pixels`` = #(A > level), ``visible_pixels`` = #(V > level), ``occlusion`` = 1 - sum V / sum A (0 where sum A = 0),
+    ``mean_distance`` = the mean of Z / A over the amodal pixels (0 where there is none); with ``slot_class`` and ``slot_index``."""
+    _check_layers(layers, table)
+    K = table.K
+    A, V, Z = (layers[:, :K, i].double() for i in range(3))
+    amodal = A > level
+    sum_a, sum_v = A.sum(0), V.sum(0)
+    occ = torch.where(sum_a > 0, 1.0 - sum_v / torch.where(sum_a > 0, sum_a, torch.ones_like(sum_a)), torch.zeros_like(sum_a))
+    dist = torch.where(amodal, Z / torch.where(amodal, A, torch.ones_like(A)), torch.zeros_like(A)).sum(0)
+    n_am = amodal.sum(0)
+    return dict(amodal_pixels=n_am, visible_pixels=(V > level).sum(0), occlusion=occ,
+                mean_distance=torch.where(n_am > 0, dist / n_am.clamp(min=1), torch.zeros_like(dist)),
+                slot_class=torch.from_numpy(table.slot_class).to(layers.device), slot_index=torch.from_numpy(table.slot_index).to(layers.device))
+
+
+@torch.no_grad()
+def front_order(layers, level=0.5):
+    """Per ray the slots (instance columns; the rest column is left out) with A > level, nearest first by ``zf``, a tie by the lower slot:
+    (order (N, K) int64, padded with -1 behind the ray's last slot; count (N) int64)."""
+    _check_layers(layers)
+    K = layers.shape[1] - 1
+    A, zf = layers[:, :K, 0], layers[:, :K, 3]
+    on = A > level
+    key = torch.where(on, zf, torch.full_like(zf, float("inf")))
+    idx = torch.sort(key, dim=1, stable=True)[1]
+    order = torch.where(torch.gather(on, 1, idx), idx, torch.full_like(idx, -1))
+    return order, on.sum(1)

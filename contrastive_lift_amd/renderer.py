@@ -182,6 +182,14 @@ class TensoRFRenderer(nn.Module):
         No jitter (is_train False), no gradient."""
         return engine.surface_forward(tensorf, self, rays, None, q)[0]
 
+    # ------------------------------------------------------------------ amodal instance layers (DESIGN.md 6i)
+    @torch.no_grad()
+    def forward_layers(self, tensorf, rays, table, alpha_thres=None, use_delta=False):
+        """What every instance slot of ``table`` (``layers.SlotTable``) covers along the rays, also behind what hides it:
+        dict(layers (N, K + 1, 4) rows [A amodal opacity, V visible weight, Z amodal expected distance (un-normalised), zf first listed distance],
+        column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed).  No jitter (is_train False), no gradient."""
+        return engine.layers_forward(tensorf, self, rays, table, None, alpha_thres, use_delta)[0]
+
     # ------------------------------------------------------------------ scene edits (renderer.py:303-623)
     def _forward_edit(self, tensorf, rays, white_bg, resolved):
         out, _ = engine.edit_forward(tensorf, self, rays, resolved, white_bg)

@@ -806,6 +806,48 @@ int clift_ray_surface(const clift_march_t* h_m, const float* rays, const float* 
                       const int* ray_start, const int* act_idx, int M, const float* G, float q, float* depth_med, int* k_med, float* normal,
                       clift_stream_t s);
 
+/* ---- amodal instance layers of the ray route (a further ABI 27 addition; csrc/layers.hip): per ray and per instance slot the
+ * opacity, weight and distance of that instance ALONE, also where other things hide it.  Both work on a list of samples in the layout of
+ * clift_scan_counts / clift_compact_fill (ray_start (N + 1), act_idx (M), ordered by ray, then by sample); the engine lists by alpha > threshold
+ * rather than by w, so that samples behind an occluder are in it.
+ *
+ * clift_sample_slots: slot[row] for the n rows of a list, one thread per row, one launch.
+ *   class    cls = the index of the first maximum of sem[row, 0 .. C): c* = 0, then for c = 1 .. C - 1: if sem[c] > sem[c*] then c* = c
+ *            (a NaN never compares greater).
+ *   range    (off, cnt) = cls_slots[cls], cls_slots (C, 2) int32 in DEVICE memory.  cnt <= 0 gives -1.  The range is cut to [0, K):
+ *            lo = max(off, 0), hi = min(off + cnt, K), an empty cut gives -1; nothing outside centroids (K, E) is ever read and no slot
+ *            outside [0, K) is ever given.
+ *   feature  f_e = feat[row, e], or feat[row, e] + add[row, e] (one fp32 addition) when add (n, lda >= E) is not NULL.
+ *   mode 0   nearest centroid of centroids[lo .. hi): d = f_e - c_e, d2 = d2 + d * d over e = 0 .. E - 1, EVERY operation rounded to fp32 on its
+ *            own; the running minimum starts at +inf and is replaced on strict <, so the lowest index wins a tie and a row whose distances
+ *            are all NaN or +inf has no winner and gets -1.  The slot is the winner's index in centroids.
+ *   mode 1   for models whose instance outputs are slot scores (linear assignment): lo + the index of the first maximum (the rule of the
+ *            class) of f_0 .. f_{min(hi - lo, E) - 1}.  centroids is not read and may be NULL.
+ *   Separate rounding is deliberate: clift_nearest_centroid forms its distances with fmaf, which a numpy loop cannot restate; here an fp32
+ *   numpy loop, one operation per statement, reproduces every label exactly.  The two may therefore disagree on a near tie.
+ *   Errors: C < 1, E < 1, K < 0, K > 255, lds < C, ldf < E, lda < E with add, a mode other than 0 / 1, a NULL buffer (sem, feat, cls_slots,
+ *   slot), mode 0 with K > 0 and NULL centroids.  n <= 0 returns 0 without a launch.
+ *
+ * clift_ray_layers: out (N, K + 1, 4) fp32 for the rays of a march (the record, rays and jitter of clift_march_fwd; alpha, w (N, S) as it wrote
+ *   them).  Every list entry j carries slot[j]; a value in [0, K) is that column, anything else the rest column K.  For ray r and column c, over
+ *   the entries j = ray_start[r] .. ray_start[r + 1] - 1 in list order whose column is c, with sid = act_idx[j], k = sid - r S (an entry with k
+ *   outside [0, S) -- another ray's, or out of range -- is skipped, never followed), a = alpha[sid], z = z_k the march's own fp32 expression,
+ *   starting from Tc = 1, V = 0, Z = 0, zf = 0, seen = false, each line ONE separately rounded fp32 operation:
+ *       if !seen: zf = z, seen = true
+ *       u  = Tc * a
+ *       Z  = Z + (u * z)
+ *       V  = V + w[sid]
+ *       Tc = Tc * (1 - a)
+ *   and out[r, c] = [A = 1 - Tc, V, Z, zf]: the opacity of column c rendered alone, the weight the whole scene gives it (what is visible),
+ *   its un-normalised expected distance when alone, the distance of its first listed sample.  A column without entries is [0, 0, 0, 0].
+ *   One wave per ray, every (ray, column) written once as one float4, no atomics and no LDS: two runs give the same bits.  ray_start is
+ *   clamped to [0, M].  M = 0 (act_idx and slot may be NULL) is fine: every row is zeros.
+ *   Errors: K < 0, K > 255, S < 1, M < 0, N S >= 2^31 - 1, a NULL buffer, NULL act_idx / slot with M > 0.  N <= 0 returns 0 without a launch. */
+int clift_sample_slots(const float* sem, int lds, int C, const float* feat, int ldf, int E, const float* add, int lda, const int* cls_slots,
+                       const float* centroids, int K, int mode, long n, int* slot, clift_stream_t s);
+int clift_ray_layers(const clift_march_t* h_m, const float* rays, const float* jitter, int N, const float* alpha, const float* w,
+                     const int* ray_start, const int* act_idx, int M, const int* slot, int K, float* out /* (N, K+1, 4) */, clift_stream_t s);
+
 /* ---- surface outputs of an EDITED scene (a further ABI 27 addition; csrc/edit.hip): the gradient of the raw density of the
  * scene an edit program describes.  The walk of clift_edit_list_points remaps a world point p h times, by the edits i_1 .. i_h in walk order,
  * and ends at p' = J p + b with J = M_{i_h} ... M_{i_1} (the identity for h = 0; formed in fp32, every multiply and add rounded separately).

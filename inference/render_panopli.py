@@ -16,8 +16,14 @@ Surface outputs of the ray route (two more launches per chunk, onl
 ``surface/<frame>.npz`` (depth_median, hit, normals) and ``vis_normals/<frame>.png``; ``--pointcloud_depth median`` back-projects to the
 median-depth hit point instead of the expected distance, drops the pixels whose ray never loses half its transmittance and adds their
 normals to ``pointcloud.pkl``.
+
+Amodal instance layers (a pass of its own per frame, only when asked for): ``--save_layers [--layers_level 0.5]`` writes per
+frame ``layers/<frame>.npz`` and ``.json`` -- what every instance covers also behind the things in front of it, what of it is visible and
+where its first sample lies -- and ``vis_amodal/<frame>.png``.  It needs ``--cached_centroids_path`` (the centroids are numbered once for the
+scene) or a linear_assignment model.
 """
 import argparse
+import functools
 import os
 import pickle
 import sys
@@ -130,9 +136,58 @@ def write_surface_frame(out, frame_name, depth_median, hit, normals):
     Image.fromarray((vis.clip(0, 1) * 255).astype(np.uint8)).save(out / "vis_normals" / f"{frame_name}.png")
 
 
+def layers_table(config, scene, cached_centroids_path):
+    """The slot table of ``--save_layers``: the cached centroids numbered once for the scene (layers.SlotTable.from_centroids), or, for a
+    linear-assignment model, whose instance outputs are slot scores, one slot per output."""
+    from contrastive_lift_amd.layers import SlotTable
+    fg = scene.segmentation_data.fg_classes
+    total_classes = len(scene.segmentation_data.bg_classes) + len(fg)
+    if cached_centroids_path is not None:
+        with open(cached_centroids_path, "rb") as f:
+            return SlotTable.from_centroids(pickle.load(f), fg, total_classes)
+    if config.instance_loss_mode == "linear_assignment":
+        return SlotTable.from_scores(fg, total_classes, int(config.max_instances))
+    raise ValueError("--save_layers needs --cached_centroids_path (or a linear_assignment model): the layers are kept per centroid")
+
+
+def write_layers_frame(out, frame_name, layers, table, H, W, rgb, level=0.5):
+    """The files of ``--save_layers`` for one frame, from its layers (H W, K + 1, 4) and rendered colours (H W, 3), tensors on any device.
+    ``layers/<frame>.npz``: slots (n,) the slots with an amodal pixel (A > level) in this frame, slot_class (n,), and amodal = A, visible = V,
+    front = zf, the distance at which the slot's first sample lies, each (n, H, W) float16.  ``layers/<frame>.json``: level and per such slot
+    its class, centroid index, amodal and visible pixel counts, occlusion rate and mean amodal distance (layers.summarise).
+    ``vis_amodal/<frame>.png``: the outline of every amodal mask, in the slot's colour, over the rendered colours."""
+    import json
+    from contrastive_lift_amd import layers as ly
+    for d in ("layers", "vis_amodal"):
+        (out / d).mkdir(exist_ok=True)
+    s = ly.summarise(layers, table, level)
+    present = torch.nonzero(s["amodal_pixels"] > 0).reshape(-1)
+    sel = layers[:, present].permute(1, 0, 2).reshape(present.shape[0], H, W, 4).cpu()
+    slots = present.cpu().numpy().astype(np.int32)
+    np.savez(out / "layers" / f"{frame_name}.npz", slots=slots, slot_class=table.slot_class[slots].astype(np.int32),
+             amodal=sel[..., 0].numpy().astype(np.float16), visible=sel[..., 1].numpy().astype(np.float16),
+             front=sel[..., 3].numpy().astype(np.float16))
+    col = {k: v.cpu().numpy() for k, v in s.items()}
+    summary = dict(frame=str(frame_name), level=float(level), n_slots=int(table.K),
+                   slots=[dict(slot=int(i), slot_class=int(col["slot_class"][i]), slot_index=int(col["slot_index"][i]),
+                               amodal_pixels=int(col["amodal_pixels"][i]), visible_pixels=int(col["visible_pixels"][i]),
+                               occlusion=float(col["occlusion"][i]), mean_distance=float(col["mean_distance"][i])) for i in slots])
+    with open(out / "layers" / f"{frame_name}.json", "w") as f:
+        json.dump(summary, f, indent=1)
+    vis = rgb.reshape(H, W, 3).cpu().numpy().clip(0, 1).copy()
+    pal = glasbey(table.K + 2)
+    masks = sel[..., 0].numpy() > level
+    for i, m in zip(slots, masks):
+        inner = m.copy()                                     # 4-neighbour erosion: a mask pixel with a neighbour outside is outline
+        inner[1:] &= m[:-1]; inner[:-1] &= m[1:]; inner[:, 1:] &= m[:, :-1]; inner[:, :-1] &= m[:, 1:]
+        vis[m & ~inner] = pal[int(i) + 1]
+    Image.fromarray((vis * 255).astype(np.uint8)).save(out / "vis_amodal" / f"{frame_name}.png")
+
+
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
                               cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
-                              meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn", save_surface=False, pointcloud_depth="expected"):
+                              meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn", save_surface=False, pointcloud_depth="expected",
+                              save_layers=False, layers_level=0.5):
     if pointcloud_depth not in ("expected", "median"):
         raise ValueError(f"pointcloud_depth must be 'expected' or 'median', got {pointcloud_depth!r}")
     median_cloud = bool(save_pointcloud) and pointcloud_depth == "median"
@@ -143,6 +198,7 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
     scene, model, renderer = load_for_inference(config, device)
     H, W = scene.image_dim
     fg = scene.segmentation_data.fg_classes
+    table = layers_table(config, scene, cached_centroids_path) if save_layers else None
     rgbs, sems, depths, inst_feats, thing_feats, slow_feats, points = [], [], [], [], [], [], []
     names = []
     hits, normals, depths_med = [], [], []
@@ -158,6 +214,12 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
             else:
                 p_rgb, p_sem, p_inst, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg)
             depths.append(inf.distance_to_depth(K_frame, p_dist.view(H, W)))
+            if save_layers:         # a pass of its own over the frame; written at once: a frame's layers are large
+                fn = functools.partial(inf.render_rays_layers, table=table, use_delta=bool(config.use_delta))
+                lay = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=fn)[0]
+                if rank == 0:
+                    write_layers_frame(out, name, lay, table, H, W, p_rgb, layers_level)
+                del lay
             if save_pointcloud:
                 # (use_delta below keeps the expected distance for the instance features: only the saved points change)
                 points.append(points3d.backproject(rays, p_dmed if median_cloud else p_dist).float().cpu())
@@ -219,7 +281,7 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
     return out
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt_path", type=str, required=True)
     ap.add_argument("--render_trajectory", action="store_true")
@@ -246,7 +308,15 @@ if __name__ == "__main__":
     ap.add_argument("--pointcloud_depth", choices=("expected", "median"), default="expected",
                     help="where --save_pointcloud puts a pixel's point: at the expected distance (the reference), or at the median-depth hit "
                          "(pixels without a hit are dropped, a normals key is added)")
-    args = ap.parse_args()
+    ap.add_argument("--save_layers", action="store_true",
+                    help="also write layers/<frame>.npz and .json (amodal opacity, visible weight and front distance of every instance slot, and "
+                         "their summary) and vis_amodal/<frame>.png; needs --cached_centroids_path or a linear_assignment model")
+    ap.add_argument("--layers_level", type=float, default=0.5, help="the opacity above which --save_layers counts a pixel into a mask")
+    return ap
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
     cfg.subsample_frames = args.subsample
@@ -256,4 +326,5 @@ if __name__ == "__main__":
                                     cached_centroids_path=args.cached_centroids_path, use_silverman=args.use_silverman,
                                     cluster_size=args.cluster_size, meanshift=args.meanshift, hdbscan=args.hdbscan,
                                     save_pointcloud=args.save_pointcloud, save_surface=args.save_surface,
-                                    pointcloud_depth=args.pointcloud_depth))
+                                    pointcloud_depth=args.pointcloud_depth, save_layers=args.save_layers,
+                                    layers_level=args.layers_level))
