@@ -11,6 +11,7 @@ Per chunk of N rays (reference renderer.py:80-176):
   xyz heads: K=3 first layer -> GEMM+ReLU chain -> narrow GEMM (-> softmax)
   composite.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -136,9 +137,7 @@ def _app_precision():
         return _Precision(1)
     if MLP_PRECISION == 2 and APP_X6 and persistent_mode_ok():
         return _Precision(2)
-    if MLP_PRECISION in (1, 2):
-        return _Precision(0)
-    return _Precision(MLP_PRECISION)
+    return _Precision(0)
 
 
 def act_dtype():
@@ -220,6 +219,14 @@ def sign_bits_for(M, dev):
     return torch.empty(((M + 31) // 32 * 1024,), dtype=torch.uint8, device=dev)
 
 
+def _scratch(nbytes, dev):
+    """Stream-ordered scratch of one launch.  Launched on a side stream (Branches), the allocator must not recycle it before that stream is done."""
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if _lib._launch_stream is not None:
+        ws.record_stream(_lib._launch_stream)
+    return ws
+
+
 def gemm(M, N, K, A, lda, B, ldb, Cm, ldc, a_trans=0, b_trans=0, bias=None, act=0, mask=None, ldmask=0,
          accumulate=0, split_k=1, a_off=0, c_off=0, c_trans=0, colsum=None, sign_bits=None):
     """One clift_gemm launch.  Pitches and offsets are in ELEMENTS of the respective tensor; a tensor of dtype bfloat16 is
@@ -249,10 +256,7 @@ def gemm(M, N, K, A, lda, B, ldb, Cm, ldc, a_trans=0, b_trans=0, bias=None, act=
             # goes to the library's tiled split kernel, which needs a workspace for the split weight planes
             if route != 0:      # (route 0: an empty launch, nothing runs)
                 nbytes = int(_lib.load().clift_gemm_workspace_bytes(int(N), int(K)))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=A.device)      # split weight planes (stream-ordered scratch)
-                if _lib._launch_stream is not None:   # launched on a side stream (Branches): the allocator must not recycle it earlier
-                    ws.record_stream(_lib._launch_stream)
-                g.workspace, g.workspace_bytes = ws.data_ptr(), nbytes
+                g.workspace, g.workspace_bytes = _scratch(nbytes, A.device).data_ptr(), nbytes      # split weight planes
         else:
             # every other launch -- narrow layers (HBM streams), the remaining weight gradients -- stays on its exact-fp32 persistent kernel, which is
             # faster than the tiled split kernel the library would pick for it
@@ -354,8 +358,6 @@ def app_last2(M, H1, W2, b2, W3, b3, H2, rgb):
          ptr(H2), 128, None, 0, ptr(rgb), rgb.shape[1], 1, stream())
 
 
-
-
 def head_bf16(M, xa, l0, l1, l2, lout, h1, h2, h3, out, ldo, col_off):
     """One clift_xyz_head_bf16_fwd launch (csrc/head_bf16.hip)."""
     (W0, b0), (W1, b1), (W2, b2) = l0, l1, l2
@@ -371,12 +373,9 @@ def first2(M, xa, W0, b0, W1, b1, h1, h2):
     call("clift_xyz_head_first2_fwd", ptr(xa), ptr(W0), _pitch(W0), ptr(b0), ptr(W1), _pitch(W1), ptr(b1), M, ptr(h1), 256, ptr(h2), 256, stream())
 
 
-# The fusions of the xyz heads are not switchable (their A/Bs are settled: profiles/r02_*, r03_ab_first2_bwd.txt, r04_ab_x6_fused_ends.txt): the K = 3
-# layer is generated inside the second layer's kernel; the first activation is never written -- the backward consumes the second layer's input
-# gradient inside its kernel (first2_bwd) and regenerates the activation for the weight gradient (first2_wgrad); an E <= 4 output layer is
-# applied inside the last hidden layer's kernel; the output layer's weight and input gradient are one launch.  The tiled-only switch --
-# kernel_switches(tiled_only=True), or its environment variable (include/clift.h) read once at start -- selects the independent tiled kernels for
-# every layer instead (the cross-check the tests use).
+# The fusions of the xyz heads (xyz_head_route, _xyz_bwd_route) are not switchable one by one: their A/Bs are settled (profiles/r02_*,
+# r03_ab_first2_bwd.txt, r04_ab_x6_fused_ends.txt).  The tiled-only switch -- kernel_switches(tiled_only=True), or its environment variable
+# (include/clift.h) read once at start -- selects the independent tiled kernels for every layer instead (the cross-check the tests use).
 APP_SCATTER_XA = True       # tests clear it: clift_app_gather_bwd without the forward's positions (xa = NULL: the lane-per-(plane, channel) walk)
 DENS_BWD_SIGMA = True       # tests clear it: clift_density_bwd without the forward's sigma (sigma = NULL: the softplus derivative re-summed)
 FIRST2_BF16_BWD_FUSED = True  # tests clear it: bf16 mode, the second layer's input gradient written and the K = 3 layer's weight gradient as its own launch
@@ -417,11 +416,8 @@ def last2_x6(M, h, W, b, Wo, bo, hidden, out, ldo, col_off):
     """One clift_xyz_head_last2_x6_fwd launch (fp32x6 mode): last2 with the 256 x 256 layer on the split kernel; the output layer's partial
     sums travel through a stream-ordered scratch buffer (256 B per row)."""
     nbytes = 256 * M
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=h.device)
-    if _lib._launch_stream is not None:       # launched on a side stream (Branches): the allocator must not recycle it earlier
-        ws.record_stream(_lib._launch_stream)
     call("clift_xyz_head_last2_x6_fwd", ptr(h), h.shape[1], ptr(W), _pitch(W), ptr(b), ptr(Wo), _pitch(Wo), ptr(bo), Wo.shape[0], M, ptr(hidden), 256,
-         C.c_void_p(out.data_ptr() + 4 * col_off), ldo, ptr(ws), nbytes, stream())
+         C.c_void_p(out.data_ptr() + 4 * col_off), ldo, ptr(_scratch(nbytes, h.device)), nbytes, stream())
 
 
 def first2_wgrad(M, d, W0, b0, xa, gW1, gb1):
@@ -429,37 +425,67 @@ def first2_wgrad(M, d, W0, b0, xa, gW1, gb1):
     call("clift_xyz_head_first2_wgrad", ptr(d), d.shape[1], ptr(W0), _pitch(W0), ptr(b0), ptr(xa), M, ptr(gW1), _pitch(gW1), ptr(gb1), stream())
 
 
-def _row_softmax_inplace(out, M, n_out, ldo, col_off):
-    o = C.c_void_p(out.data_ptr() + 4 * col_off)
-    call("clift_rows_act_fwd", o, ldo, M, n_out, 2, o, ldo, stream())
-
-
 def out_layer_fwd(M, h, W, b, out, ldo, col_off, act):
     """One clift_out_layer_fwd launch: out[:, col_off:col_off+no] = act(h W^T + b), no <= 32, act 0 / 2 (row softmax) -- one read of h."""
     call("clift_out_layer_fwd", ptr(h), h.shape[1], ptr(W), _pitch(W), ptr(b), W.shape[0], M, C.c_void_p(out.data_ptr() + 4 * col_off), ldo, act, stream())
 
 
-def _out_layer(M, h, W, K, b, out, ldo, col_off, out_act):
+def _out_layer(M, h, W, K, b, out, ldo, col_off, out_act, fused=False):
     """The narrow output layer of a head over the K columns of h: out[:, col_off:col_off + n_out] = h W^T + b, then the row softmax when
-    ``out_act`` is 2."""
-    if (MLP_PRECISION in (0, 2) and W.shape[0] <= 32 and K == 256 and h.dtype == torch.float32 and h.shape[1] == 256 and out.dtype == torch.float32
-            and _pitch(W) % 4 == 0 and b is not None and persistent_ok()):
-        # the E <= 32 output layer (+ the row softmax) as one stream over the hidden activation
-        out_layer_fwd(M, h, W, b, out, ldo, col_off, out_act)
-        return
-    gemm(M, W.shape[0], K, h, h.shape[1], W, _pitch(W), out, ldo, bias=b, c_off=col_off)
-    if out_act == 2:
-        _row_softmax_inplace(out, M, W.shape[0], ldo, col_off)
+    ``out_act`` is 2.  ``fused``: a hidden layer's kernel has already written the logits, only the softmax remains."""
+    if not fused:
+        if (MLP_PRECISION in (0, 2) and W.shape[0] <= 32 and K == 256 and h.dtype == torch.float32 and h.shape[1] == 256 and out.dtype == torch.float32
+                and _pitch(W) % 4 == 0 and b is not None and persistent_ok()):
+            # the E <= 32 output layer (+ the row softmax) as one stream over the hidden activation
+            out_layer_fwd(M, h, W, b, out, ldo, col_off, out_act)
+            return
+        gemm(M, W.shape[0], K, h, h.shape[1], W, _pitch(W), out, ldo, bias=b, c_off=col_off)
+    if out_act == 2:        # in place
+        o = C.c_void_p(out.data_ptr() + 4 * col_off)
+        call("clift_rows_act_fwd", o, ldo, M, W.shape[0], 2, o, ldo, stream())
+
+
+HeadRoute = collections.namedtuple("HeadRoute", "front out_in_front tail first_stored signs")
+
+
+def xyz_head_route(layers, keep, out_dtype):
+    """The kernels the forward of an xyz head runs on, from the layer shapes, the precision that is set, the fusion flags and the cached switch
+    word: nothing is allocated, launched or asked of the library.  xyz_mlp_fwd dispatches on it and hands it to the backward in the HeadActs.
+      front         "fused3_bf16" | "first2" | "first2_x6" | "k3": what takes the K = 3 layer, with the two / the one 256 x 256 layer behind it or alone
+      out_in_front  the output layer runs inside the front end as well
+      tail          "last2" | "last2_x6" | None: the last hidden layer and the output layer in one launch
+      first_stored  a forward that keeps its activations (``keep``) writes the K = 3 layer's; False: the backward re-derives it
+      signs         the hidden activations whose signs such a forward leaves (sign_bits_for) for the next layer's masked dgrad
+    A new fused kernel adds a value here, its predicate in this function and a case in xyz_mlp_fwd."""
+    n, P = len(layers), MLP_PRECISION
+    wide = lambda i: tuple(layers[i][0].shape) == (256, 256)
+    narrow_out = layers[-1][0].shape[0] <= 4 and out_dtype == torch.float32
+    gen = n >= 3 and layers[0][0].shape[0] == 256 and wide(1)       # the K = 3 layer can be generated inside the second layer's kernel
+    if FUSE_HEAD_BF16 and P == 1 and gen and n >= 4 and wide(2) and persistent_ok():
+        # bf16 mode: K = 3 layer + two hidden layers (+ the output layer when it is <= 4 wide and follows directly) in one launch with the
+        # activations resident in LDS
+        return HeadRoute("fused3_bf16", n == 4 and narrow_out, None, True, ())
+    # (the first activation has no reader: first2_bwd / first2_wgrad re-derive it from the positions.  KEEP_FIRST_ACT stores it all the same,
+    # which only the exact kernel can: the split kernel has no output for it)
+    fused2 = P in (0, 2) and gen and persistent_mode_ok() and not (P == 2 and keep and KEEP_FIRST_ACT)
+    front = ("first2_x6" if P == 2 else "first2") if fused2 else "k3"
+    fused_tail = P in (0, 2) and n - 2 >= 1 + fused2 and narrow_out and wide(n - 2) and persistent_mode_ok()     # (a hidden layer is left for it)
+    # fp32x6, a backward will run: the persistent kernels also leave the SIGNS of their output (32 B per row), so that the next layer's masked dgrad does
+    # not stream the 1 KB-per-row activation again just to test it against zero -- but the last hidden layer's, which the output layer's backward reads as values
+    signs = tuple(i for i in range(1, n - 2) if wide(i)) if (keep and P == 2 and persistent_mode_ok()) else ()
+    return HeadRoute(front, False, ("last2_x6" if P == 2 else "last2") if fused_tail else None, front == "k3" or (front == "first2" and KEEP_FIRST_ACT), signs)
 
 
 class HeadActs(list):
     """The hidden activations an xyz head keeps for its backward (acts[i] = output of layer i, or None where the backward re-derives it), plus
     -- fp32x6 mode -- the sign bytes a persistent forward left for activation i (``signs[i]``, from sign_bits_for): held HERE, next to the tensor
-    they describe and for exactly as long, instead of as an ad-hoc attribute on the tensor object (which a view or a clone would drop silently)."""
+    they describe and for exactly as long, instead of as an ad-hoc attribute on the tensor object (which a view or a clone would drop silently).
+    ``route``: the HeadRoute the forward ran on (None for a list built by hand: every activation stored); ``kept`` False: that forward
+    retained nothing (keep_first=False), the list is [None] and a backward is refused."""
 
-    def __init__(self, *a):
+    def __init__(self, *a, route=None, kept=True):
         super().__init__(*a)
-        self.signs = {}
+        self.signs, self.route, self.kept = {}, route, kept
 
     def sign_bits_of(self, i, M):
         """The sign bytes of activation i, or None; checked against the activation they were written with."""
@@ -476,146 +502,103 @@ def xyz_mlp_fwd(layers, xa, M, out, ldo, col_off=0, keep_first=True, out_act=0):
     """layers = [(W,b)]; xa (M,4); hidden activations returned for the backward; final layer written into
     out[:, col_off:col_off+n_out] with row pitch ldo -- as logits (``out_act`` 0) or after a softmax over the row (2: the semantic head,
     tensoRF.py:37,593; applied inside the output layer's kernel where that exists, else in place by a row-activation launch).
-    ``keep_first`` = False: the caller will not run a backward through this head, so the first (K = 3) layer's activation is
-    never materialised (acts[0] is None) -- fp32 path, 256-wide heads."""
-    dev = xa.device
-    acts = HeadActs()
-    W0, b0 = layers[0]
+    ``keep_first`` = False: the caller will not run a backward through this head, so a hidden activation is written only where a following launch
+    reads it and none is retained (a frame render at 65536 rays per chunk holds ~9 GiB per hidden layer otherwise)."""
+    dev, n = xa.device, len(layers)
+    r = xyz_head_route(layers, keep_first, out.dtype)
+    acts = HeadActs(route=r)
     hdt = act_dtype()                     # bf16 mode stores the hidden activations as bf16 (half the HBM stream of these layers)
-    rest = layers[1:-1]
-    out_done = False                      # the output layer has run inside a hidden layer's kernel (logits: a softmax is still to come)
-    if (FUSE_HEAD_BF16 and MLP_PRECISION == 1 and hdt == torch.bfloat16 and len(layers) >= 4 and W0.shape[0] == 256
-            and tuple(layers[1][0].shape) == (256, 256) and tuple(layers[2][0].shape) == (256, 256) and persistent_ok()):
-        # bf16 mode: K = 3 layer + two hidden layers (+ the output layer when it is <= 4 wide and follows directly) in one launch with the
-        # activations resident in LDS; they are written (bf16) only for a backward pass
-        Wo, bo = layers[-1]
-        with_out = len(layers) == 4 and Wo.shape[0] <= 4 and out.dtype == torch.float32
-        mk = lambda: torch.empty((M, 256), dtype=torch.bfloat16, device=dev)
-        h1, h2 = (mk(), mk()) if keep_first else (None, None)
-        h3 = mk() if (keep_first or not with_out) else None
-        head_bf16(M, xa, layers[0], layers[1], layers[2], (Wo, bo) if with_out else None, h1, h2, h3, out, ldo, col_off)
-        acts += [h1, h2, h3]
-        out_done = with_out               # (then layers[3:-1] is empty)
-        h = h3
-        rest = layers[3:-1]
-    elif (MLP_PRECISION == 0 and len(layers) >= 3 and W0.shape[0] == 256 and tuple(layers[1][0].shape) == (256, 256)
-            and persistent_ok()):
-        W1, b1 = layers[1]
-        # (with the fused backward the first layer's activation has no reader: both of its uses -- the ReLU mask of the second layer's input
-        # gradient and the second layer's weight gradient -- re-derive it from the positions, so it is never written)
-        h1 = torch.empty((M, 256), dtype=torch.float32, device=dev) if (keep_first and KEEP_FIRST_ACT) else None
-        h = torch.empty((M, 256), dtype=torch.float32, device=dev)
-        first2(M, xa, W0, b0, W1, b1, h1, h)
-        acts += [h1, h]
-        rest = layers[2:-1]
-    elif (MLP_PRECISION == 2 and len(layers) >= 3 and W0.shape[0] == 256 and tuple(layers[1][0].shape) == (256, 256)
-            and (not keep_first or not KEEP_FIRST_ACT) and persistent_mode_ok()):
-        # fp32x6: the same fusion with the 256 x 256 layer on the split kernels; the first activation is never written (the backward, if any,
-        # re-derives it: first2_bwd / first2_wgrad)
-        W1, b1 = layers[1]
-        h = torch.empty((M, 256), dtype=torch.float32, device=dev)
-        # a backward will run: the kernel also leaves the SIGNS of its output (32 B per row) for the next layer's masked dgrad, which then
-        # does not stream the 1 KB-per-row activation a second time just to test it against zero
-        sb1 = sign_bits_for(M, dev) if (keep_first and len(layers) >= 4) else None
-        first2_x6(M, xa, W0, b0, W1, b1, h, sb1)
-        acts += [None, h]
-        if sb1 is not None:
-            acts.signs[1] = sb1
-        rest = layers[2:-1]
+    new = lambda on=True, width=256: torch.empty((M, width), dtype=hdt, device=dev) if on else None
+    signs = lambda i: acts.signs.setdefault(i, sign_bits_for(M, dev)) if i in r.signs else None
+    (W0, b0), (Wo, bo) = layers[0], layers[-1]
+    if r.front == "fused3_bf16":
+        acts += [new(keep_first), new(keep_first), new(keep_first or not r.out_in_front)]
+        head_bf16(M, xa, layers[0], layers[1], layers[2], (Wo, bo) if r.out_in_front else None, *acts, out, ldo, col_off)
+    elif r.front == "first2":
+        acts += [new(keep_first and r.first_stored), new()]
+        first2(M, xa, W0, b0, *layers[1], *acts)
+    elif r.front == "first2_x6":
+        acts += [None, new()]
+        first2_x6(M, xa, W0, b0, *layers[1], acts[1], signs(1))
     else:
-        h = torch.empty((M, W0.shape[0]), dtype=hdt, device=dev)
-        call("clift_linear_k3_fwd", ptr(xa), ptr(W0), _pitch(W0), ptr(b0), M, W0.shape[0], 1, ptr(h), h.shape[1], int(hdt == torch.bfloat16), stream())
-        acts.append(h)
-    Wo, bo = layers[-1]
-    fuse_out = (MLP_PRECISION in (0, 2) and len(rest) >= 1 and Wo.shape[0] <= 4 and tuple(rest[-1][0].shape) == (256, 256)
-                and h.dtype == torch.float32 and out.dtype == torch.float32 and persistent_mode_ok())
-    for li_, (W, b) in enumerate(rest):
-        if fuse_out and li_ == len(rest) - 1:
-            # last hidden layer + the narrow output layer in one launch; the hidden activation is written only for a backward
-            hn = torch.empty((M, 256), dtype=torch.float32, device=dev) if keep_first else None
-            (last2_x6 if MLP_PRECISION == 2 else last2)(M, h, W, b, Wo, bo, hn, out, ldo, col_off)
-            acts.append(hn)
-            out_done = True
-            break
-        hn = torch.empty((M, W.shape[0]), dtype=hdt, device=dev)
-        # (fp32x6, a backward will run, and this is not the last hidden layer -- whose output the output layer's backward reads as values: sign bytes too)
-        sb = (sign_bits_for(M, dev) if (keep_first and MLP_PRECISION == 2 and li_ < len(rest) - 1 and tuple(W.shape) == (256, 256) and h.dtype == torch.float32
-                                        and persistent_mode_ok()) else None)
-        gemm(M, W.shape[0], W.shape[1], h, h.shape[1], W, _pitch(W), hn, hn.shape[1], bias=b, act=1, sign_bits=sb)
+        acts.append(new(width=W0.shape[0]))
+        call("clift_linear_k3_fwd", ptr(xa), ptr(W0), _pitch(W0), ptr(b0), M, W0.shape[0], 1, ptr(acts[0]), W0.shape[0], int(hdt == torch.bfloat16), stream())
+    for li in range(len(acts), n - 1):
+        (W, b), h = layers[li], acts[-1]
+        if r.tail and li == n - 2:
+            hn = new(keep_first)
+            (last2_x6 if r.tail == "last2_x6" else last2)(M, h, W, b, Wo, bo, hn, out, ldo, col_off)
+        else:
+            hn = new(width=W.shape[0])
+            gemm(M, W.shape[0], W.shape[1], h, h.shape[1], W, _pitch(W), hn, hn.shape[1], bias=b, act=1, sign_bits=signs(li))
         acts.append(hn)
-        if sb is not None:
-            acts.signs[len(acts) - 1] = sb
-        h = hn
-    if not out_done:
-        _out_layer(M, h, Wo, Wo.shape[1], bo, out, ldo, col_off, out_act)
-    elif out_act == 2:
-        _row_softmax_inplace(out, M, Wo.shape[0], ldo, col_off)
-    # no backward through this head: nothing is retained, every hidden activation goes back to the (stream-ordered) allocator as soon
-    # as the next layer has been enqueued -- a frame render at 65536 rays per chunk holds ~9 GiB per hidden layer otherwise
-    return acts if keep_first else [None]
+    _out_layer(M, acts[-1], Wo, Wo.shape[1], bo, out, ldo, col_off, out_act, fused=r.out_in_front or r.tail is not None)
+    return acts if keep_first else HeadActs([None], route=r, kept=False)
+
+
+def _xyz_bwd_route(layers, acts, li, d, M):
+    """How layer ``li`` >= 1 of an xyz head is taken back.  What the forward stored is read from its record; the rest is the state at backward
+    time: the fusion flags, the switches, M, type and pitch of the layer's output gradient ``d``.
+      "first2" | "first2_x6" | "first2_bf16"   layers 1 and 0 together, which ends the chain: the second layer's weight gradient, then its
+                         input gradient formed and consumed by the K = 3 layer's weight gradient in one launch
+      "out" | "out_nh"   the output layer's weight gradient and masked input gradient in one pass over the hidden activation; _nh (bf16 mode):
+                         over the bf16-stored activation, the layer's width and a bf16 flag passed, the input gradient leaves bf16-stored
+      "signs" | "mask"   weight gradient, then the input gradient masked by the sign bytes the forward left / by the stored activation"""
+    W, h, P, f32 = layers[li][0], acts[li - 1], MLP_PRECISION, torch.float32
+    (no, ni), nh, wide = W.shape, P == 1, tuple(W.shape) == (256, 256)
+    if li == 1:
+        gen = wide and tuple(layers[0][0].shape) == (256, 3)
+        regen = acts.route is not None and not acts.route.first_stored        # (then the forward has checked the shapes: ``gen`` holds)
+        if regen and d.dtype != f32:
+            raise _lib.CliftError("backward through an xyz head in bf16 mode whose forward ran in another mode and stored no first activation")
+        if regen or (not KEEP_FIRST_ACT and P in (0, 2) and gen and d.dtype == f32 and h.dtype == f32 and d.shape[1] % 4 == 0 and persistent_ok()):
+            return "first2_x6" if P == 2 and persistent_x6_ok() else "first2"
+        if nh and FIRST2_BF16_BWD_FUSED and gen and h.dtype == d.dtype == torch.bfloat16 and d.shape[1] == h.shape[1] == 256 and M >= 4096 and persistent_ok():
+            return "first2_bf16"
+    if (li == len(layers) - 1 and ni == 256 and no <= 32 and d.shape[1] <= 32 and d.shape[1] % 4 == 0 and M >= 4096 and d.dtype == f32
+            and h.dtype == act_dtype() and (not nh or (OUT_BWD_BF16_FUSED and h.shape[1] == 256 and _pitch(W) >= 256))):
+        return "out_nh" if nh else "out"
+    if acts.sign_bits_of(li - 1, M) is not None and P == 2 and wide and d.dtype == f32 and d.shape[1] % 4 == 0 and persistent_x6_ok():
+        return "signs"
+    return "mask"
 
 
 def xyz_mlp_bwd(layers, glayers, xa, acts, dpre, M, keep=None):
     """dpre (M, ld) = gradient w.r.t. the last layer's pre-activation output (ld % 4 == 0, pad zero).
     ``keep``: list that receives every temporary (so a caller running this on a side stream controls their lifetime)."""
-    dev = xa.device
-    d = dpre
-    n = len(layers)
-    if acts[0] is None and len(acts) != n - 1:
+    if not acts.kept:
         raise _lib.CliftError("backward through an xyz head whose forward ran with keep_first=False (head not named in grad_heads)")
-    keep = keep if keep is not None else []
+    dev, d, keep = xa.device, dpre, keep if keep is not None else []
     keep.append(d)
-    for li in range(n - 1, 0, -1):
-        W, b = layers[li]
-        gW, gb = glayers[li]
-        h = acts[li - 1]
+    (W0, b0), (gW0, gb0) = layers[0], glayers[0]
+    for li in range(len(layers) - 1, 0, -1):
+        (W, b), (gW, gb), h = layers[li], glayers[li], acts[li - 1]
         no, ni = W.shape
-        if li == 1 and (h is None or (not KEEP_FIRST_ACT and MLP_PRECISION in (0, 2) and no == 256 and ni == 256 and tuple(layers[0][0].shape) == (256, 3) and
-                                      d.dtype == torch.float32 and h.dtype == torch.float32 and d.shape[1] % 4 == 0 and
-                                      persistent_ok())):
-            # second layer: its weight gradient (over the first layer's activation -- regenerated from the positions when the forward did not keep
-            # it), then its input gradient formed and consumed by the first layer's weight gradient in one launch
-            if no != 256 or ni != 256 or tuple(layers[0][0].shape) != (256, 3) or d.shape[1] != 256 or d.dtype != torch.float32:
-                raise _lib.CliftError("backward through an xyz head whose forward ran with keep_first=False (head not named in grad_heads)")
-            x6_ends = MLP_PRECISION == 2 and persistent_x6_ok()
-            if h is None:
-                (first2_x6_wgrad if x6_ends else first2_wgrad)(M, d, layers[0][0], layers[0][1], xa, gW, gb)
+        how = _xyz_bwd_route(layers, acts, li, d, M)
+        if how.startswith("first2"):
+            if h is None:           # (over the first layer's activation regenerated from the positions)
+                (first2_x6_wgrad if how == "first2_x6" else first2_wgrad)(M, d, W0, b0, xa, gW, gb)
             else:
                 wgrad(no, ni, M, d, d.shape[1], h, h.shape[1], gW, gb)
-            (first2_x6_bwd if x6_ends else first2_bwd)(M, d, W, layers[0][0], layers[0][1], xa, *glayers[0])
-            return
-        if (li == 1 and MLP_PRECISION == 1 and FIRST2_BF16_BWD_FUSED and h is not None and h.dtype == torch.bfloat16 and d.dtype == torch.bfloat16
-                and no == 256 and ni == 256 and tuple(layers[0][0].shape) == (256, 3) and d.shape[1] == 256 and h.shape[1] == 256 and M >= 4096
-                and persistent_ok()):
-            # bf16 mode, second layer: its weight gradient, then its input gradient formed and consumed by the K = 3 layer's weight gradient in one launch
-            wgrad(no, ni, M, d, d.shape[1], h, h.shape[1], gW, gb)
-            call("clift_xyz_head_first2_bf16_bwd", ptr(d), 256, ptr(W), _pitch(W), ptr(h), 256, ptr(xa), M, ptr(glayers[0][0]), _pitch(glayers[0][0]),
-                 ptr(glayers[0][1]), stream())
+            if how == "first2_bf16":
+                call("clift_xyz_head_first2_bf16_bwd", ptr(d), 256, ptr(W), _pitch(W), ptr(h), 256, ptr(xa), M, ptr(gW0), _pitch(gW0), ptr(gb0), stream())
+            else:
+                (first2_x6_bwd if how == "first2_x6" else first2_bwd)(M, d, W, W0, b0, xa, gW0, gb0)
             return
         dn = torch.empty((M, ni), dtype=act_dtype(), device=dev)        # bf16 mode: hidden gradients are bf16-stored as well
-        nh = MLP_PRECISION == 1
-        if (li == n - 1 and ni == 256 and no <= 32 and d.shape[1] <= 32 and d.shape[1] % 4 == 0 and M >= 4096 and d.dtype == torch.float32 and
-                h.dtype == dn.dtype and (not nh or (OUT_BWD_BF16_FUSED and h.shape[1] == 256 and _pitch(W) >= 256))):
-            # output layer: weight gradient and masked input gradient in one pass over the hidden activation; bf16 mode: the same one pass over
-            # the (bf16-stored) hidden activation -- the _nh entry point, which also takes the layer's width and a bf16 flag -- and the input
-            # gradient leaves bf16-stored
-            call("clift_out_layer_bwd_nh" if nh else "clift_out_layer_bwd", ptr(d), d.shape[1], no, ptr(W), _pitch(W), ptr(h), h.shape[1],
-                 *((ni,) if nh else ()), M, ptr(dn), ni, ptr(gW), _pitch(gW), ptr(gb), *((1,) if nh else ()), stream())
-            d = dn
-            keep.append(d)
-            continue
-        wgrad(no, ni, M, d, d.shape[1], h, h.shape[1], gW, gb)
-        sb = acts.sign_bits_of(li - 1, M) if isinstance(acts, HeadActs) else None
-        if (sb is not None and MLP_PRECISION == 2 and no == 256 and ni == 256 and d.dtype == torch.float32 and d.shape[1] % 4 == 0
-                and persistent_x6_ok()):
-            gemm(M, ni, no, d, d.shape[1], W, _pitch(W), dn, ni, b_trans=1, sign_bits=sb)      # mask = the signs the forward left behind
+        if how == "out":
+            call("clift_out_layer_bwd", ptr(d), d.shape[1], no, ptr(W), _pitch(W), ptr(h), h.shape[1], M, ptr(dn), ni, ptr(gW), _pitch(gW), ptr(gb), stream())
+        elif how == "out_nh":
+            call("clift_out_layer_bwd_nh", ptr(d), d.shape[1], no, ptr(W), _pitch(W), ptr(h), h.shape[1], ni, M, ptr(dn), ni, ptr(gW), _pitch(gW), ptr(gb), 1, stream())
         else:
-            gemm(M, ni, no, d, d.shape[1], W, _pitch(W), dn, ni, b_trans=1, mask=h, ldmask=h.shape[1])
+            wgrad(no, ni, M, d, d.shape[1], h, h.shape[1], gW, gb)
+            if how == "signs":
+                gemm(M, ni, no, d, d.shape[1], W, _pitch(W), dn, ni, b_trans=1, sign_bits=acts.signs[li - 1])
+            else:
+                gemm(M, ni, no, d, d.shape[1], W, _pitch(W), dn, ni, b_trans=1, mask=h, ldmask=h.shape[1])
         d = dn
         keep.append(d)
-    gW, gb = glayers[0]
-    call("clift_linear_k3_bwd", ptr(xa), ptr(d), d.shape[1], M, layers[0][0].shape[0], ptr(gW), _pitch(gW), ptr(gb),
-         int(d.dtype == torch.bfloat16), stream())
+    call("clift_linear_k3_bwd", ptr(xa), ptr(d), d.shape[1], M, W0.shape[0], ptr(gW0), _pitch(gW0), ptr(gb0), int(d.dtype == torch.bfloat16), stream())
 
 
 # ----------------------------------------------------------------------------- heads on their own VM grids (tensoRF.py:70-83,142-156)
@@ -948,6 +931,17 @@ def _app_tail(M, H1, W2, b2, W3, b3, hdt, rgb_s):
     return H2, pre
 
 
+def app_tail_route(layers, M, hdt):
+    """The launch that takes the last two appearance layers and the sigmoid together, inside _app_precision(): "last2" | "last2_x6" |
+    "last2_bf16" (over the bf16-stored activation, csrc/layer_nb16.hip), or None: _app_tail's three launches.  Pure, like xyz_head_route."""
+    W2, W3 = layers[1][0], layers[2][0]
+    if not (tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128 and persistent_ok()):
+        return None
+    if MLP_PRECISION in (0, 2) and hdt == torch.float32:
+        return "last2_x6" if MLP_PRECISION == 2 and persistent_x6_ok() else "last2"       # (x6: only inside _app_precision() with APP_X6)
+    return "last2_bf16" if MLP_PRECISION == 1 and hdt == torch.bfloat16 and M >= 64 else None
+
+
 def _app_layers(M, X, layers, hdt, keep_h2, keep):
     """The appearance MLP over its encoded input rows X (M, the first layer's row pitch), inside _app_precision(): H1 = relu(X W1^T + b1) stored as ``hdt``, then the
     last two layers fused where a kernel exists -- H2 is written only for a backward (``keep_h2``) -- else _app_tail (H2 written, ``keep``
@@ -957,25 +951,73 @@ def _app_layers(M, X, layers, hdt, keep_h2, keep):
     H1 = torch.empty((M, W1.shape[0]), dtype=hdt, device=dev)
     gemm(M, W1.shape[0], ldx, X, ldx, W1, ldx, H1, H1.shape[1], bias=b1, act=1)
     rgb_s = torch.empty((M, 3), dtype=torch.float32, device=dev)
-    if (MLP_PRECISION in (0, 2) and hdt == torch.float32 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4 and W3.shape[1] == 128
-            and persistent_ok()):
-        # second hidden layer + output layer + sigmoid in one launch; H2 is written only for a backward
-        H2 = torch.empty((M, 128), dtype=torch.float32, device=dev) if keep_h2 else None
-        if MLP_PRECISION == 2 and persistent_x6_ok():        # (only inside _app_precision() with APP_X6)
-            call("clift_app_head_last2_x6_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
-                 ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
-        else:
-            app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
-    elif (MLP_PRECISION == 1 and hdt == torch.bfloat16 and H1.dtype == torch.bfloat16 and tuple(W2.shape) == (128, 128) and W3.shape[0] <= 4
-            and W3.shape[1] == 128 and M >= 64 and persistent_ok()):
-        # bf16 mode: the same pair of layers over the bf16-stored activation (csrc/layer_nb16.hip)
-        H2 = torch.empty((M, 128), dtype=torch.bfloat16, device=dev) if keep_h2 else None
-        call("clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2), ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M,
-             ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
-    else:
+    tail = app_tail_route(layers, M, hdt)
+    if tail is None:
         H2, pre = _app_tail(M, H1, W2, b2, W3, b3, hdt, rgb_s)
         keep.append(pre)
+        return H1, H2, rgb_s
+    H2 = torch.empty((M, 128), dtype=hdt, device=dev) if keep_h2 else None
+    if tail == "last2":
+        app_last2(M, H1, W2, b2, W3, b3, H2, rgb_s)
+    else:
+        call("clift_app_head_last2_x6_fwd" if tail == "last2_x6" else "clift_app_head_last2_bf16_fwd", ptr(H1), 128, ptr(W2), _pitch(W2), ptr(b2),
+             ptr(W3), _pitch(W3), ptr(b3), W3.shape[0], M, ptr(H2), 128, ptr(rgb_s), 3, 1, stream())
     return H1, H2, rgb_s
+
+
+def _app_out_bwd_route(M, W3, gW3, H2, dpre):
+    """The launch that takes the appearance output layer's weight gradient and masked input gradient in one pass over the hidden activation (as in
+    the xyz heads): "nh", "n128_bf16" (bf16 mode: over the bf16-stored activation, the input gradient leaves bf16-stored), or None: two passes."""
+    n2 = W3.shape[1]
+    if not (APP_OUT_BWD_FUSED and W3.shape[0] <= 4 and _pitch(W3) >= n2 and _pitch(gW3) >= n2 and persistent_ok()):
+        return None
+    if H2.dtype == torch.float32 and n2 % 32 == 0 and n2 <= 256 and M >= 4096:
+        return "nh"
+    return "n128_bf16" if MLP_PRECISION == 1 and H2.dtype == torch.bfloat16 and n2 == 128 and dpre.shape[1] == 4 else None
+
+
+def _app_backward(model, views, gviews, ctx, layers, glayers, dpre, keep):
+    """Backward of render_forward's appearance chain from ``dpre`` (M, 4), the gradient w.r.t. the pre-sigmoid colours: the three layers, the
+    input encoding, the basis matrix and the scatter into the appearance tables.  ``keep`` receives every temporary."""
+    M, dev = ctx.M, ctx.rays.device
+    with _app_precision():
+        (W1, b1), (W2, b2), (W3, b3) = layers
+        (gW1, gb1), (gW2, gb2), (gW3, gb3) = glayers
+        H1, H2, X, ldx = ctx.H1, ctx.H2, ctx.X, ctx.ldx
+        n2 = W3.shape[1]
+        dH2 = torch.empty((M, n2), dtype=H2.dtype, device=dev)
+        how = _app_out_bwd_route(M, W3, gW3, H2, dpre)
+        if how == "nh":
+            call("clift_out_layer_bwd_nh", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), n2, n2, M, ptr(dH2), n2, ptr(gW3), _pitch(gW3),
+                 ptr(gb3), 0, stream())
+        elif how == "n128_bf16":
+            call("clift_out_layer_bwd_n128_bf16", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), 128, M, ptr(dH2), 128, ptr(gW3), _pitch(gW3),
+                 ptr(gb3), stream())
+        else:
+            wgrad(3, n2, M, dpre, 4, H2, n2, gW3, gb3)
+            gemm(M, n2, 3, dpre, 4, W3, _pitch(W3), dH2, n2, b_trans=1, mask=H2, ldmask=n2)
+        n1 = W2.shape[1]
+        wgrad(n2, n1, M, dH2, n2, H1, n1, gW2, gb2)
+        dH1 = torch.empty((M, n1), dtype=H1.dtype, device=dev)
+        gemm(M, n1, n2, dH2, n2, W2, _pitch(W2), dH1, n1, b_trans=1, mask=H1, ldmask=n1)
+        wgrad(n1, ldx, M, dH1, n1, X, ldx, gW1, gb1)
+        dX = torch.empty((M, ldx), dtype=torch.float32, device=dev)
+        gemm(M, ldx, n1, dH1, n1, W1, ldx, dX, ldx, b_trans=1)
+        nf, ldf = ctx.nf, ctx.ldf
+        Wb, gWb = views["appearance_basis_mat.weight"], gviews["appearance_basis_mat.weight"]
+        nc = Wb.shape[1]
+        va = vm_struct(views, "appearance", ctx.res)
+        ga = vm_grad_struct(model, gviews, "appearance")
+        dfeat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
+        call("clift_app_encode_bwd", ptr(ctx.feat), ldf, nf, model.pe_feat, ptr(dX), ldx, M, ptr(dfeat), ldf, stream())
+        call("clift_wgrad_narrow", ptr(dfeat), ldf, nf, ptr(ctx.F), nc, nc, M, ptr(gWb), _pitch(gWb), None, 0, stream())
+        dF = torch.empty((M, nc), dtype=torch.float32, device=dev)
+        with exact_fp32():              # (the basis Linear is not one of the bf16 layers in any mode)
+            gemm(M, nc, nf, dfeat, ldf, Wb, _pitch(Wb), dF, nc, b_trans=1)
+        call("clift_app_gather_bwd", C.byref(ctx.ms), C.byref(va), C.byref(ga), ptr(ctx.rays), ptr(ctx.jitter),
+             ptr(ctx.act_idx), M, ptr(dF), ptr(ctx.xa) if APP_SCATTER_XA else None, stream())
+        vm_grad_finish(model, gviews, "appearance", ga)
+        keep.extend([dpre, dH2, dH1, dX, dfeat, dF])
 
 
 def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_sem=True, want_inst=True, grad_heads=("app", "sem", "fast", "slow"),
@@ -1246,50 +1288,8 @@ def render_backward(model, ctx, gviews, g_rgb=None, g_sem=None, g_inst=None, g_d
         if d_rgb is not None:
             model.xcd_workspace_for("appearance")
 
-        # ---------------- appearance head
         def app_chain(keep):
-            with _app_precision():
-                (W1, b1), (W2, b2), (W3, b3) = params["app"]
-                (gW1, gb1), (gW2, gb2), (gW3, gb3) = gparams["app"]
-                dpre = _head_dpre(pre_rgb, ctx.rgb_s, d_rgb, 0, 3, 1, M)
-                H1, H2, X, ldx = ctx.H1, ctx.H2, ctx.X, ctx.ldx
-                n2 = W3.shape[1]
-                dH2 = torch.empty((M, n2), dtype=H2.dtype, device=dev)
-                if (APP_OUT_BWD_FUSED and H2.dtype == torch.float32 and n2 % 32 == 0 and n2 <= 256 and W3.shape[0] <= 4 and M >= 4096
-                        and _pitch(W3) >= n2 and _pitch(gW3) >= n2 and persistent_ok()):
-                    # output layer: weight gradient and masked input gradient in one pass over the hidden activation (as in the xyz heads)
-                    call("clift_out_layer_bwd_nh", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), n2, n2, M, ptr(dH2), n2, ptr(gW3), _pitch(gW3),
-                         ptr(gb3), 0, stream())
-                elif (APP_OUT_BWD_FUSED and MLP_PRECISION == 1 and H2.dtype == torch.bfloat16 and n2 == 128 and W3.shape[0] <= 4 and dpre.shape[1] == 4
-                        and _pitch(W3) >= 128 and _pitch(gW3) >= 128 and persistent_ok()):
-                    # bf16 mode: the same one pass over the bf16-stored activation; the input gradient leaves bf16-stored
-                    call("clift_out_layer_bwd_n128_bf16", ptr(dpre), 4, W3.shape[0], ptr(W3), _pitch(W3), ptr(H2), 128, M, ptr(dH2), 128, ptr(gW3), _pitch(gW3),
-                         ptr(gb3), stream())
-                else:
-                    wgrad(3, n2, M, dpre, 4, H2, n2, gW3, gb3)
-                    gemm(M, n2, 3, dpre, 4, W3, _pitch(W3), dH2, n2, b_trans=1, mask=H2, ldmask=n2)
-                n1 = W2.shape[1]
-                wgrad(n2, n1, M, dH2, n2, H1, n1, gW2, gb2)
-                dH1 = torch.empty((M, n1), dtype=H1.dtype, device=dev)
-                gemm(M, n1, n2, dH2, n2, W2, _pitch(W2), dH1, n1, b_trans=1, mask=H1, ldmask=n1)
-                wgrad(n1, ldx, M, dH1, n1, X, ldx, gW1, gb1)
-                dX = torch.empty((M, ldx), dtype=torch.float32, device=dev)
-                gemm(M, ldx, n1, dH1, n1, W1, ldx, dX, ldx, b_trans=1)
-                nf, ldf = ctx.nf, ctx.ldf
-                Wb, gWb = views["appearance_basis_mat.weight"], gviews["appearance_basis_mat.weight"]
-                nc = Wb.shape[1]
-                va = vm_struct(views, "appearance", ctx.res)
-                ga = vm_grad_struct(model, gviews, "appearance")
-                dfeat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
-                call("clift_app_encode_bwd", ptr(ctx.feat), ldf, nf, model.pe_feat, ptr(dX), ldx, M, ptr(dfeat), ldf, stream())
-                call("clift_wgrad_narrow", ptr(dfeat), ldf, nf, ptr(ctx.F), nc, nc, M, ptr(gWb), _pitch(gWb), None, 0, stream())
-                dF = torch.empty((M, nc), dtype=torch.float32, device=dev)
-                with exact_fp32():              # (the basis Linear is not one of the bf16 layers in any mode)
-                    gemm(M, nc, nf, dfeat, ldf, Wb, _pitch(Wb), dF, nc, b_trans=1)
-                call("clift_app_gather_bwd", C.byref(ctx.ms), C.byref(va), C.byref(ga), ptr(ctx.rays), ptr(ctx.jitter),
-                     ptr(ctx.act_idx), M, ptr(dF), ptr(ctx.xa) if APP_SCATTER_XA else None, stream())
-                vm_grad_finish(model, gviews, "appearance", ga)
-                keep.extend([dpre, dH2, dH1, dX, dfeat, dF])
+            _app_backward(model, views, gviews, ctx, params["app"], gparams["app"], _head_dpre(pre_rgb, ctx.rgb_s, d_rgb, 0, 3, 1, M), keep)
 
         # ---------------- semantic head
         def sem_chain(keep):

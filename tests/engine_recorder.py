@@ -3,8 +3,9 @@
 ``Recorder`` replaces ``engine.call`` for the duration of a ``with`` block: nothing is launched; every call is stored as
 [entry point, arguments] with integers and floats as they are, pointers as None (NULL) or [buffer number, byte offset] -- buffers numbered by
 first appearance in the record -- and structs (Gemm, VM, VMGrad, March, EditRec) as {field: value} in the same form, a struct inside a struct
-likewise; a host array of structs (the ``edits`` of the clift_edit_list_* entry points) as the list of them.  A clift_gemm launch also carries
-the name of the route clift_gemm_route gives its descriptor (the real library: it loads without a GPU).
+likewise; a host array of structs (the ``edits`` of the clift_edit_list_* entry points) as the list of them, a host array of scalars (the
+``c_float * 3`` box factors of the density-gradient launches) as the list of its values.  A clift_gemm launch also carries the name of the
+route clift_gemm_route gives its descriptor (the real library: it loads without a GPU).
 
 A pointer is resolved against the storages the recorder knows and keeps alive until it is dropped, so that no address is used twice within a
 record: everything the engine allocates (``engine.torch`` is a proxy whose empty / zeros / empty_like / zeros_like / tensor register their
@@ -12,7 +13,8 @@ result), every tensor handed to ``engine.ptr``, and the ``roots`` of the case (p
 scratch).  A pointer into none of them is an error.
 
 Stand-ins for what the sequencing reads back from the device: clift_scan_counts / clift_scan_counts_capped write ``active`` into
-ray_start[N]; ``engine._rows_limit`` holds a CPU tensor so that the sync-free path never reaches torch.cuda.synchronize.
+ray_start[N] -- a sequence gives one count per scan, in order (the layer pass scans twice: the march's list, then its alpha-list);
+``engine._rows_limit`` holds a CPU tensor so that the sync-free path never reaches torch.cuda.synchronize.
 """
 import bisect
 import ctypes as C
@@ -43,10 +45,11 @@ def _f32_any_device(t, what="tensor"):
 
 class Recorder:
     def __init__(self, active=0, roots=lambda: (), launch=None, pointers=True):
-        """``active``: the count the scan stand-ins report.  ``roots``: callable giving tensors a pointer may point into without the engine having
+        """``active``: the count the scan stand-ins report, or a sequence of them, one per scan.  ``roots``: callable giving tensors a pointer may point into without the engine having
         allocated them.  ``launch``: the real ``call`` to forward every launch to (GPU cross-check; no stand-ins then).  ``pointers`` False: record
         names and scalars only."""
-        self.active, self.roots, self.launch, self.pointers = int(active), roots, launch, pointers
+        self.active = [int(a) for a in active] if isinstance(active, (list, tuple)) else int(active)
+        self.roots, self.launch, self.pointers = roots, launch, pointers
         self.launches = []
         self._starts, self._spans, self._numbers = [], [], {}
         self._saved = None
@@ -102,6 +105,10 @@ class Recorder:
             raise AssertionError(f"launch {len(self.launches)}: pointer {p:#x} is in no tensor the recorder knows")
         return [self._numbers.setdefault(base, len(self._numbers)), p - base]
 
+    def buffer_number(self, t):
+        """The number the record gave the buffer ``t`` lives in, or -1 for one no launch has pointed into."""
+        return self._numbers.get(t.untyped_storage().data_ptr(), -1)
+
     # ------------------------------------------------------------------ one launch
     def _struct(self, s):
         out = {}
@@ -132,6 +139,8 @@ class Recorder:
                 rec.append(self._struct(a._obj))
             elif isinstance(a, C.Array) and issubclass(a._type_, C.Structure):        # host array of structs: by content, no device pointer
                 rec.append([self._struct(x) for x in a])
+            elif isinstance(a, C.Array):                 # host array of scalars: by content
+                rec.append(list(a))
             elif self.pointers:
                 rec.append(self._pointer(a.value if isinstance(a, C.c_void_p) else a))
         entry = [name, rec]
@@ -143,4 +152,5 @@ class Recorder:
         if self.launch is not None:
             self.launch(name, *args)
         elif name in ("clift_scan_counts", "clift_scan_counts_capped"):
-            C.c_int.from_address(args[2].value + 4 * int(args[1])).value = self.active          # ray_start[N]
+            active = self.active.pop(0) if isinstance(self.active, list) else self.active
+            C.c_int.from_address(args[2].value + 4 * int(args[1])).value = active          # ray_start[N]
