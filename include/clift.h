@@ -303,7 +303,17 @@ int clift_app_front_fwd_x(const clift_march_t* h_m, const clift_vm_t* h_app, con
  *   rows streamed by LDS-DMA); in precision 1 with bf16-stored A / C (/ mask) the same forms and the 256 x 256 wgrad run as
  *   streaming kernels (csrc/layer_bf16.hip).  Everything else takes the tiled kernels (csrc/gemm*.hip).  clift_gemm_route (below) names the
  *   kernel a descriptor goes to.  CLIFT_SWITCH_TILED_ONLY forces the tiled kernels (A/B comparisons in tests/test_gpu_parity.py): the
- *   environment variable CLIFT_NO_PERSISTENT=1, read once at start, or clift_set_switches at run time. */
+ *   environment variable CLIFT_NO_PERSISTENT=1, read once at start, or clift_set_switches at run time.
+ * Pad columns of the operands, i.e. [K, lda) of a row of A and [K, ldb) of a row of B (a_trans / b_trans: [M, lda), [N, ldb)): no kernel
+ *   lets them into a result, and all but one never read them -- they may hold anything, NaN included.  The exception is the narrow-K input
+ *   gradient (a_trans = 0, b_trans = 1, K <= lda <= 32, M >= 4096, no bias / act: CLIFT_GEMM_ROUTE_DGRAD_NARROW and _DGRAD_NARROW_BF16,
+ *   csrc/narrow_stream.hip): it copies whole rows of A into LDS and multiplies the columns [K, lda) by zero weights, so there the pad columns
+ *   of A must be FINITE (the engine's producers write zeros: clift_rows_act_bwd, clift_composite_bwd_act, clift_app_encode_bwd); a NaN or Inf
+ *   in them becomes a NaN in that row of C, where the tiled kernel would have returned a number.  Rows of A / B / mask past the row count
+ *   are never read, and nothing is written to the pad columns [N, ldc) of C (c_trans: [M, ldc)).
+ * mask: an entry is ON if and only if its value is > 0 -- +0.0, -0.0, negative values and negative denormals are off; positive denormals
+ *   and +inf are on.  A mask must be NaN-FREE: the fp32 comparison treats a NaN as off, the sign test of a bf16-stored mask (mask_bf16)
+ *   treats a NaN with a clear sign bit as on. */
 typedef struct {
     int M, N, K;
     const float* A; int lda; int a_trans;
