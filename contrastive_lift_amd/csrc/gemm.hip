@@ -644,7 +644,8 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ dY, in
                                                  float* __restrict__ db) {
     const int n = blockIdx.y * 256 + threadIdx.x;
     if (n >= N) return;
-    const int mb = blockIdx.x * rows_per_block, me = min(M, mb + rows_per_block);
+    const int mb = blockIdx.x * rows_per_block, me = min(limit_rows(M), mb + rows_per_block);
+    if (mb >= me) return;                          // (a capacity-sized grid: this block's rows lie past the device row limit)
     float a = 0.f;
     for (int m = mb; m < me; ++m) a += dY[(size_t)m * ld + n];
     unsafeAtomicAdd(db + n, a);

@@ -226,7 +226,12 @@ int clift_compact_fill(const float* w, const int* ray_start, int N, int S, float
  * persistent kernels re-balance their row ranges over the true count.  The caller keeps INT_MAX in *limit outside a
  * pass; clift_scan_counts_capped writes min(total, cap) into it (limit_out = the bound address), clamps the offsets to
  * cap and records total in *overflow when total > cap (samples past the capacity are dropped -- memory-safe, and the
- * caller is expected to raise the capacity); clift_compact_fill_capped writes only rows < cap. */
+ * caller is expected to raise the capacity); clift_compact_fill_capped writes only rows < cap.
+ * Of the MLP-head entry points below, the bf16-mode kernels of csrc/layer_bf16.hip, layer_nb16.hip and head_bf16.hip do NOT clamp:
+ * clift_xyz_head_bf16_fwd, clift_app_head_last2_bf16_fwd (forwards: the rows past the true count are computed and never read),
+ * clift_xyz_head_first2_bf16_bwd and clift_out_layer_bwd_n128_bf16 (reductions: they need the true row count as their argument), like the
+ * precision-1 routes of clift_gemm; bf16 mode does not run sync-free steps.  Every other one clamps (tests/test_gpu_head_cases.py holds each to
+ * the reference of L rows, or to the bits of its rows < L), clift_colsum included. */
 int clift_bind_rows_limit(const int* dev_limit);
 
 /* XCD-private gradient shards (ABI 12).  The kernels that end by adding a per-block partial of a small gradient tensor to memory (the weight
@@ -381,7 +386,11 @@ long clift_sign_bits_bytes(int M);
  * the hidden activation H (tensoRF.py:480-481, 593-594 backward): dX = (H > 0) . (dOut W), gW += dOut^T H, gb += column sums of dOut.
  * dOut (M, ldd) fp32 with zero pad columns (no <= ldd <= 32, ldd % 4 == 0), W (no, 256) pitch ldw, H (M, 256) pitch ldh, dX (M, 256)
  * pitch ldx, gW (no, 256) pitch ldgw (accumulated), gb (no) nullable (accumulated); 16-byte aligned rows.  Replaces one clift_wgrad_narrow +
- * one masked clift_gemm(b_trans) call, which each stream H from memory. */
+ * one masked clift_gemm(b_trans) call, which each stream H from memory.
+ * The pad columns [no, ldd) of dOut must be FINITE (the kernel is the narrow dgrad stream of clift_gemm_t: whole rows go to LDS and meet zero
+ * weights); pad columns of H / W, the rows of dOut / H past M and the rows of W past `no` are never read and may hold anything.  H is both the
+ * mask (on iff > 0: +-0 and negative denormals are off, positive denormals on; NaN-free) and an operand of gW; gb sums the UNMASKED dOut.
+ * Nothing is written outside dX[0..M)[0..nh), gW[0..no)[0..nh) and gb[0..no). */
 int clift_out_layer_bwd(const float* dOut, int ldd, int no, const float* W, int ldw, const float* H, int ldh, int M,
                         float* dX, int ldx, float* gW, int ldgw, float* gb, clift_stream_t s);
 /* ... over a hidden layer of nh units, nh % 32 == 0, nh <= 256 (ABI 16: the 128-wide appearance head, tensoRF.py:393-397 backward; its
@@ -392,13 +401,16 @@ int clift_out_layer_bwd_nh(const float* dOut, int ldd, int no, const float* W, i
 /* Forward of a narrow output layer over a 256-wide hidden activation, with the row activation that follows it, in ONE pass over H (ABI 15;
  * tensoRF.py:591-594 with :37 for the semantic head):  out[m][0..no) = act( H[m][0..256) W^T + b ),  no <= 32, act 0 = none, 2 = softmax over
  * the row.  H (M, ldh) fp32, W (no, 256) pitch ldw, b (no), out (M, ldo) -- columns [no, ldo) untouched.  Replaces clift_gemm (which streams H at
- * less than half the rate for so narrow an output) + clift_rows_act_fwd; results differ from that pair by fp32 summation order only. */
+ * less than half the rate for so narrow an output) + clift_rows_act_fwd; results differ from that pair by fp32 summation order only.
+ * Pad columns of H and W and rows of H past M are never read; a row's bits do not depend on the launch it is part of. */
 int clift_out_layer_fwd(const float* H, int ldh, const float* W, int ldw, const float* b, int no, int M, float* out, int ldo, int act,
                         clift_stream_t s);
 int clift_gemm(const clift_gemm_t* h_g, clift_stream_t s);
 
 /* First layer of the xyz heads (in_features == 3): out (M, Nout) = act(x[:, :3] W^T + b); x is (M, 4), W (Nout, 3)
- * with row pitch ldw. */
+ * with row pitch ldw.  Each output is fmaf(w2, z, fmaf(w1, y, fmaf(w0, x, b))) -- the operation order every fused kernel that re-derives the
+ * first layer's sign repeats.  x[:, 3] and the pad columns of W never enter a result (here and in every entry point below that takes x4:
+ * they may hold anything); Nout % 4 == 0, ldo % 4 == 0; columns [Nout, ldo) of out are not written. */
 int clift_linear_k3_fwd(const float* x4, const float* W, int ldw, const float* b, int M, int Nout, int relu,
                         float* out, int ldo, int out_bf16 /* out is bf16-stored (bf16 mode) */, clift_stream_t s);
 /* First TWO layers of an xyz head in one launch (tensoRF.py:475-478, 576-579; 256-wide hidden layers, fp32):
@@ -481,7 +493,8 @@ int clift_app_head_last2_bf16_fwd(const void* A, int lda, const float* W, int ld
                                   clift_stream_t s);
 /* bf16 mode (ABI 17): backward of the no <= 4 wide output layer over the bf16-stored 128-wide hidden activation H (tensoRF.py:397 backward), one
  * pass over H:  dX (M, ldx) bf16-stored = (H > 0) . (dOut W),  gW (no, 128) += dOut^T H,  gb (no) += column sums of dOut (nullable).
- * dOut (M, ldd) fp32 with ldd >= 4 (pad columns ignored), products fp32. */
+ * dOut (M, ldd) fp32 with ldd >= 4 (pad columns ignored: [no, ldd) may hold anything, NaN included), products fp32.  Does not clamp to the device
+ * row limit (see clift_bind_rows_limit). */
 int clift_out_layer_bwd_n128_bf16(const float* dOut, int ldd, int no, const float* W, int ldw, const void* H, int ldh, int M,
                                   void* dX, int ldx, float* gW, int ldgw, float* gb, clift_stream_t s);
 /* bf16 mode: the first three layers of an xyz head (K = 3 layer + two 256 x 256 hidden layers, tensoRF.py:475-479, 576-579) and,
@@ -493,19 +506,25 @@ int clift_xyz_head_bf16_fwd(const float* x4, const float* W0, int ldw0, const fl
                             const float* b1, const float* W2, int ldw2, const float* b2, const float* Wout, int ldwo,
                             const float* bout, int E, int M, void* h1, void* h2, void* h3, float* out, int ldo,
                             clift_stream_t s);
-/* dW (Nout,3; pitch ldw) += dH^T x ; db (Nout) += colsum(dH). */
+/* dW (Nout,3; pitch ldw) += dH^T x ; db (Nout) += colsum(dH).  db nullable.  Pad columns of dH, x4[:, 3] and rows past M are never read;
+ * columns [3, ldw) of dW are not written. */
 int clift_linear_k3_bwd(const float* x4, const float* dH, int ldh, int M, int Nout, float* dW, int ldw, float* db,
                         int dh_bf16 /* dH is bf16-stored */, clift_stream_t s);
 /* Narrow weight gradient (out_features no <= 32: the last layer of every head, tensoRF.py:395,480,581, and the basis
  * Linear :65 seen from its narrow side): gW (no, ni; pitch ldw) += dY^T X over M samples, gb (no; nullable) += colsum(dY).
- * A streaming VALU reduction at HBM rate instead of a mostly-padding matrix-core tile. */
+ * A streaming VALU reduction at HBM rate instead of a mostly-padding matrix-core tile (from 4096 rows on, for ni = 256 -- fp32 X: any multiple
+ * of 4 in [32, 256] -- and ldd <= 32: a matrix-core stream, csrc/narrow_stream.hip).  Pad columns [no, ldd) of dY and [ni, ldx) of X never enter
+ * a result, in either kernel, and may hold anything; rows past M are never read. */
 int clift_wgrad_narrow(const float* dY, int ldd, int no, const float* X, int ldx, int ni, int M, float* gW, int ldw,
                        float* gb, int x_bf16 /* X is bf16-stored */, clift_stream_t s);
-/* db (N) += colsum(dY (M,N)). */
+/* db (N) += colsum(dY (M,N)); dY has row pitch ld >= N, its pad columns are never read.  Clamps M to the device row limit like every
+ * per-sample kernel (a capacity-sized launch sums the true rows only). */
 int clift_colsum(const float* dY, int ld, int M, int N, float* db, clift_stream_t s);
 
 /* Row activations of the head outputs: kind 1 = sigmoid (tensoRF.py:385,410), 2 = softmax (tensoRF.py:37,593);
- * the backward also accepts kind 0 = identity (re-pitches dout (M,C) into the 4-float-aligned dpre (M,ldd)). */
+ * the backward also accepts kind 0 = identity (re-pitches dout (M,C) into the 4-float-aligned dpre (M,ldd)).  C <= 64, ldd <= 64.  The forward
+ * writes columns [0, C) of out only; the backward WRITES ZEROS into the pad columns [C, ldd) of dpre, for every kind (dpre is the finite-pad A
+ * operand of the narrow dgrad stream).  Pad columns of pre / out / dout are never read.  The softmax subtracts the row maximum. */
 int clift_rows_act_fwd(const float* pre, int ldp, int M, int C, int kind, float* out, int ldo, clift_stream_t s);
 int clift_rows_act_bwd(const float* out, int ldo, const float* dout, int lddo, int M, int C, int kind, float* dpre,
                        int ldd, clift_stream_t s);
