@@ -235,11 +235,11 @@ def test_limits():
 # ============================================================================ 5. the trainer on the reference's recorded steps
 def test_trainer_replays_the_reference_fixture_on_the_device_backend(monkeypatch):
     """golden G12l (two training_step()s recorded from the REFERENCE trainer, instance_loss_mode "linear_assignment") through the replay of
-    tests/test_gpu_parity.py with assignment_backend="device": the same tolerances as the host replay; clift_assign_loss ran, scipy did not."""
+    tests/gpu_scenes.py (replay_g12) with assignment_backend="device": the same tolerances as the host replay; clift_assign_loss ran, scipy did not."""
     import scipy.optimize
     import contrastive_lift_amd.trainer as trainer_mod
     from contrastive_lift_amd import _lib
-    from test_gpu_parity import test_g12_reference_training_steps_on_gpu
+    from gpu_scenes import replay_g12
     base = trainer_mod.default_config
     monkeypatch.setattr(trainer_mod, "default_config", lambda **over: base(**dict(over, assignment_backend="device")))
 
@@ -249,14 +249,14 @@ def test_trainer_replays_the_reference_fixture_on_the_device_backend(monkeypatch
     monkeypatch.setattr(scipy.optimize, "linear_sum_assignment", no_scipy)
     names, call = [], _lib.call
     monkeypatch.setattr(_lib, "call", lambda name, *a: (names.append(name), call(name, *a))[1])
-    test_g12_reference_training_steps_on_gpu("g12l_training_steps_linear_assignment")
+    replay_g12("g12l_training_steps_linear_assignment")
     assert names.count("clift_assign_loss") == 2, names.count("clift_assign_loss")          # one image per step, two steps
 
 
 # ============================================================================ 6. the trainer with a wide instance layer
 def _wide_setup(backend="device"):
     """The set-up of tests/test_gpu_round5.py::test_linear_assignment_mode_with_a_wide_instance_layer_against_the_oracle."""
-    from test_gpu_parity import _import, build_model, scene
+    from gpu_scenes import _import, build_model, scene
     from contrastive_lift_amd.trainer import HotPathTrainer, default_config
     cl, op, orender, ofld, olosses, orays = _import()
     res, C_, E, Bi = (20, 24, 28), 3, 40, 512

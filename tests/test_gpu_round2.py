@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from conftest import grad_close, rel_close, usable_cores, load_golden, T
-from test_gpu_parity import _import, build_model, scene, _run_forward_backward
+from gpu_scenes import _import, build_model, scene, _run_forward_backward
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from conftest import grad_close, rel_close, usable_cores
-from test_gpu_parity import DEV, _import, _run_forward_backward, build_model, scene
+from gpu_scenes import DEV, _first2_case, _import, _run_forward_backward, build_model, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -188,21 +188,6 @@ def test_fp32x6_persistent_layers_against_fp64(M):
 
 
 # ============================================================================ first two layers' backward in one launch
-def _first2_case(M, seed, cap=None):
-    from contrastive_lift_amd._lib import call, ptr, stream
-    R = cap or M
-    g = torch.Generator().manual_seed(seed)
-    d = torch.randn(R, 256, generator=g) * (torch.rand(R, 256, generator=g) > 0.4)
-    W1 = torch.randn(256, 256, generator=g) / 16
-    W0, b0 = torch.randn(256, 3, generator=g), 0.5 * torch.randn(256, generator=g)
-    x4 = torch.cat([torch.rand(R, 3, generator=g) * 2 - 1, torch.zeros(R, 1)], 1).contiguous()
-    dev = {k: v.to(DEV) for k, v in dict(d=d, W1=W1, W0=W0, b0=b0, x4=x4).items()}
-    h1 = torch.empty(R, 256, device=DEV)          # the forward's first-layer activation (its sign is what the fused kernel has to reproduce)
-    call("clift_linear_k3_fwd", ptr(dev["x4"]), ptr(dev["W0"]), 3, ptr(dev["b0"]), R, 256, 1, ptr(h1), 256, 0, stream())
-    dH1 = (d[:M].double() @ W1.double()) * (h1[:M].cpu() > 0)
-    return dev, h1, dH1.t() @ x4[:M, :3].double(), dH1.sum(0)
-
-
 @pytest.mark.parametrize("M", [1, 31, 32, 33, 64, 4097, 66001, 249000])
 def test_first2_bwd_against_fp64_and_the_unfused_pair(M):
     """clift_xyz_head_first2_bwd (ABI 11): gW0 / gb0 of the K = 3 layer from dH2, W1, (W0, b0) and the positions, without writing

@@ -12,8 +12,7 @@ import pytest
 import torch
 
 from conftest import grad_close
-from test_gpu_parity import DEV
-from test_gpu_round3 import _first2_case
+from gpu_scenes import DEV, _first2_case
 
 pytestmark = pytest.mark.gpu
 

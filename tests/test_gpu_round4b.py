@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import DEV, _import, build_model, scene
+from gpu_scenes import DEV, _import, build_model, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -266,7 +266,7 @@ def test_other_component_and_class_counts_against_the_oracle(comps, C_):
     """The appearance front end's other instantiations (16 / 32 components per plane: tensoRF.py:34-41 `num_appearance_comps`) and the
     compositing backward's one-thread-per-sample form (more than 48 classes), forward and every gradient against the CPU oracle."""
     from conftest import grad_close, rel_close
-    from test_gpu_parity import _run_forward_backward
+    from gpu_scenes import _run_forward_backward
     cl, op, orender, ofld, olosses, orays = _import()
     res, E, n_rays = (24, 28, 32), 3, 400
     aabb = torch.tensor([[-0.9, -0.8, -0.7], [0.8, 0.9, 0.75]])

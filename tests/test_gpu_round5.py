@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import rel_close
+from gpu_scenes import _scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -143,12 +144,6 @@ def test_nb16_output_layer_backward(M):
     assert float((gb.double() - (d[:, :3].double().sum(0) + 1.0)).abs().max()) <= 3e-5 * max(1.0, float(d[:, :3].double().sum(0).abs().max()))
 
 
-def _scene(C_=22, res=64):
-    from contrastive_lift_amd import synthetic
-    model, renderer, pool = synthetic.make_scene(grid=res, num_classes=C_, max_instances=3, seed=0, device=DEV, image=128)
-    return model, renderer, pool
-
-
 def test_bf16_appearance_chain_against_the_exact_chain():
     """bf16 mode with the bf16 appearance chain (the default of that mode since round 5) against bf16 mode with the appearance MLP on the exact
     kernels (rounds 2 - 4): colours within 2e-2 of their scale, appearance-head and table gradients within bf16 noise of each other; the front
@@ -211,7 +206,7 @@ def test_linear_assignment_mode_with_a_wide_instance_layer_against_the_oracle():
     instance output layer -- wider than every fused output-layer kernel takes (E <= 4) and than the narrow stream (<= 32): the layer runs on the
     generic launches, forward and backward -- three steps of the HIP trainer against the CPU oracle's (golden G12l pins the oracle and the
     6-wide case against the reference itself): loss to 1e-3, every instance-head parameter within 10 % of a learning-rate step."""
-    from test_gpu_parity import _import, build_model, scene
+    from gpu_scenes import _import, build_model, scene
     from contrastive_lift_amd.trainer import HotPathTrainer, default_config
     from oracle.train_step import CpuTrainer
     cl, op, orender, ofld, olosses, orays = _import()
@@ -281,7 +276,7 @@ def test_grid_heads_golden_g19(tag):
     instance-feature and segment-feature passes, the TV term with the grid terms; (a) both heads on grids, (b) semantic MLP + instance grid with
     the slow-fast twin.  Also the reference API of such a field: compute_semantic_feature / compute_instance_feature + the heads' forward."""
     from conftest import T, load_golden
-    from test_gpu_parity import _import, _run_forward_backward
+    from gpu_scenes import _import, _run_forward_backward
     cl, op, orender, ofld, olosses, orays = _import()
     g = load_golden("g19_grid_heads")
     res = tuple(int(x) for x in g["res"])

@@ -4,7 +4,7 @@ the device-side row limit, and the appearance chain end to end (tensoRF.py:393-4
 import pytest
 import torch
 
-from test_gpu_parity import DEV
+from gpu_scenes import DEV
 
 pytestmark = pytest.mark.gpu
 
@@ -181,7 +181,7 @@ def test_fp32x6_appearance_chain_against_the_exact_chain():
     kernels (rounds 3 - 4): colours to fp32 round-off, every gradient the appearance chain reaches within the noise floating-point atomics of
     sums of this length leave between two runs of the SAME arithmetic."""
     from contrastive_lift_amd import engine
-    from test_gpu_round5 import _scene
+    from gpu_scenes import _scene
     model, renderer, pool = _scene()
     g = torch.Generator(device="cpu").manual_seed(3)
     rays = pool[torch.randint(0, pool.shape[0], (4096,), generator=g).to(DEV)].contiguous()

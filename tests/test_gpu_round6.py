@@ -15,7 +15,7 @@ def _g21_trainer(g, tag, **over):
     import contrastive_lift_amd as cl
     from oracle import params as op
     from contrastive_lift_amd.trainer import HotPathTrainer, default_config
-    from test_gpu_parity import build_model
+    from gpu_scenes import build_model
     res = tuple(int(x) for x in g["res"])
     C_, E = int(g["C"]), int(g["E"])
     P = op.add_blob(op.make_params(int(g["seed"]), res, C_, E, grid_scale=float(g["grid_scale"])), res, 2.5, 0.3)
@@ -196,7 +196,7 @@ def test_grid_instance_head_with_slow_fast_twin():
     """with the instance head on its own VM grid AND the slow-fast twin, the EMA pairs the two MLPs only (the basis matrix
     is its own arena group, stepped by the instance optimizer at the net rate) -- two training_step()s of the reference trainer in that
     arrangement (golden G12gs)."""
-    from test_gpu_parity import test_g12_reference_training_steps_on_gpu as replay
+    from gpu_scenes import replay_g12 as replay
     replay("g12gs_training_steps_grid_heads_slow_fast")
 
 
@@ -299,7 +299,7 @@ def test_nottaconf_semantic_loss_mode():
     import contrastive_lift_amd as cl
     from oracle import params as op
     from contrastive_lift_amd.trainer import HotPathTrainer, default_config
-    from test_gpu_parity import build_model
+    from gpu_scenes import build_model
     g = load_golden("g12_training_steps")
     res = tuple(int(x) for x in g["res"])
     C_, E = int(g["C"]), int(g["E"])
@@ -326,13 +326,13 @@ def test_argmax_semantic_weight_mode(fused, monkeypatch):
     weights.  The golden (g6a) pins the small case in tests/test_gpu_parity.py; here 900 rays of the 40 x 48 x 56 scene against the oracle through
     BOTH compositing backward forms (activations folded in / separate), and the no-gradient frame form (grad_heads=()) against the training form.
     A ray whose two heaviest samples are within round-off of each other may pick either: such rays are left out (and counted)."""
-    import test_gpu_parity as tp
+    from gpu_scenes import _import, scene, build_model, _run_forward_backward
     from conftest import grad_close
     from contrastive_lift_amd import engine
-    cl, op, orender, ofld, olosses, orays = tp._import()
+    cl, op, orender, ofld, olosses, orays = _import()
     res, C_, E, n_rays = (40, 48, 56), 22, 3, 900
     aabb = torch.tensor([[-0.9, -0.8, -0.7], [0.8, 0.9, 0.75]])
-    P, rays, rng = tp.scene(op, orays, 23, res, C_, E, n_rays, amp=2.2, sg=0.4)
+    P, rays, rng = scene(op, orays, 23, res, C_, E, n_rays, amp=2.2, sg=0.4)
     jitter = torch.from_numpy(rng.uniform(0, 1, n_rays).astype(np.float32))
     cots = [torch.from_numpy(rng.standard_normal(s).astype(np.float32)) for s in ((n_rays, 3), (n_rays, C_), (n_rays, 2 * E))]
     Pg = op.clone_params(P, requires_grad=True)
@@ -347,9 +347,9 @@ def test_argmax_semantic_weight_mode(fused, monkeypatch):
     L = (o[0] * cots[0]).sum() + (o[1] * cots[1]).sum() + (o[2] * cots[2]).sum() + 3.0 * o[5]
     L.backward()
     monkeypatch.setattr(engine, "COMPOSITE_ACT_FUSED", fused)
-    m = tp.build_model(cl, P, res, C_, E, -3.0, "argmax")
+    m = build_model(cl, P, res, C_, E, -3.0, "argmax")
     r = cl.TensoRFRenderer(aabb, list(res), semantic_weight_mode="argmax").to(DEV)
-    outs, grads = tp._run_forward_backward(cl, m, r, rays, jitter, True, cots + [3.0])
+    outs, grads = _run_forward_backward(cl, m, r, rays, jitter, True, cots + [3.0])
     rel_close(outs[0], o[0].detach(), 1e-3, what="rgb")
     rel_close(outs[1].cpu()[clear], o[1].detach()[clear], 1e-3, what="sem")
     rel_close(outs[2].cpu()[clear], o[2].detach()[clear], 1e-3, what="inst")
@@ -377,7 +377,7 @@ def test_optimize_instance_only_skips_the_main_pass():
     import contrastive_lift_amd as cl
     from oracle import params as op
     from contrastive_lift_amd.trainer import HotPathTrainer, default_config
-    from test_gpu_parity import build_model
+    from gpu_scenes import build_model
     g = load_golden("g12_training_steps")
     res = tuple(int(x) for x in g["res"])
     C_, E = int(g["C"]), int(g["E"])

@@ -6,7 +6,7 @@ import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 import numpy as np, torch
-from test_gpu_parity import _import, build_model, scene, _run_forward_backward
+from gpu_scenes import _import, build_model, scene, _run_forward_backward
 cl, op, orender, ofld, olosses, orays = _import()
 res, C_, E, n_rays = (40, 48, 56), 22, 3, 900
 aabb = torch.tensor([[-0.9, -0.8, -0.7], [0.8, 0.9, 0.75]])
