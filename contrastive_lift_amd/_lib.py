@@ -78,6 +78,7 @@ _SIGNATURES = {
     "clift_edit_active": ([_P, _P, _P, _P, _I, _P, _P, _P], C.c_int),
     "clift_edit_list_density_fwd": ([_P, _P, _I, _P, _P, _I, _P, _P], C.c_int),
     "clift_edit_list_active": ([_P, _P, _I, _P, _P, _I, _P, _P, _P], C.c_int),
+    "clift_edit_list_active_origin": ([_P, _P, _I, _P, _P, _I, _P, _P, _P, _P], C.c_int),
     "clift_edit_list_points": ([_P, _I, _P, _I, _P, _I, _L, _P, _P, _P, _P], C.c_int),
     "clift_edit_list_dense_sigma": ([_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P], C.c_int),
     "clift_density_points": ([_P, _P, _I, _L, _F, _I, _P, _P], C.c_int),

@@ -126,8 +126,8 @@ struct EditH {
     bool kill;    // sigma = 0: some edit's kill rule named the point (p, d: where the walk stopped)
     int hops;     // how many edits remapped it (0 .. CLIFT_EDIT_MAX)
 };
-// ``hop(e)`` is called for every edit that remaps the point, before p is replaced: what else travels with the point (the view direction,
-// the Jacobian of the chain) is turned there.
+// ``hop(e, i)`` is called for every edit that remaps the point (i its 0-based position in the program), before p is replaced: what else
+// travels with the point (the view direction, the Jacobian of the chain, the origin of a copy) is turned there.
 template <class Hop>
 __device__ __forceinline__ EditH edit_walk_core(const EditL& L, float p[3], Hop hop) {
     EditH h;
@@ -140,7 +140,7 @@ __device__ __forceinline__ EditH edit_walk_core(const EditL& L, float p[3], Hop 
         const bool kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !mov) : false;
         if (!h.kill && mov) {                               // (a killed sample has stopped: later tests see its last point, and change nothing)
             const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
-            hop(e);
+            hop(e, i);
 #pragma unroll
             for (int j = 0; j < 3; ++j) p[j] = q[j];
             ++h.hops;
@@ -150,7 +150,7 @@ __device__ __forceinline__ EditH edit_walk_core(const EditL& L, float p[3], Hop 
     return h;
 }
 __device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], float d[3]) {
-    return edit_walk_core(L, p, [&](const EditP& e) {
+    return edit_walk_core(L, p, [&](const EditP& e, int) {
         const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
 #pragma unroll
         for (int j = 0; j < 3; ++j) d[j] = v[j];
@@ -161,7 +161,7 @@ __device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], flo
 __device__ __forceinline__ EditH edit_walk_point_jac(const EditL& L, float p[3], float J[9]) {
 #pragma unroll
     for (int j = 0; j < 9; ++j) J[j] = (j % 4 == 0) ? 1.f : 0.f;
-    return edit_walk_core(L, p, [&](const EditP& e) {
+    return edit_walk_core(L, p, [&](const EditP& e, int) {
         float N[9];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -390,6 +390,43 @@ extern "C" int clift_edit_list_active(const clift_march_t* h_m, const clift_edit
     if (M <= 0) return 0;
     k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
     return clift_check_launch("clift_edit_list_active");
+}
+
+// k_edit_list_active with the ORIGIN of the content beside the position: the 1-based position of the first edit the backward
+// walk meets that remaps the sample and is a DUPLICATE -- the last-applied copy in whose destination the sample sits -- or 0.  A later move
+// of the copy remaps the sample first and the walk goes on to the copy: the origin stays.  A killed sample has stopped and keeps what it
+// had.  No view direction is turned (no appearance chain follows); the point is walked with the ops of edit_walk, so xa has its bits.
+__global__ __launch_bounds__(256) void k_edit_list_active_origin(MarchP m, EditL L, const float* __restrict__ rays, const int* __restrict__ act,
+                                                                  int M, float* __restrict__ xa, unsigned char* __restrict__ origin,
+                                                                  unsigned char* __restrict__ state) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= limit_rows(M)) return;
+    const int sid = act[s];
+    const int r = sid / m.S, k = sid - r * m.S;
+    const RayG g = load_ray(rays, r, m);
+    const float z = sample_z(g, m, k, 0.f);
+    float p[3], xn[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+    int org = 0;
+    const EditH h = edit_walk_core(L, p, [&](const EditP& e, int i) {
+        if (org == 0 && e.mode == CLIFT_EDIT_DUPLICATE) org = i + 1;
+    });
+    edit_normalise(p, m.lo, m.inv2, xn);
+    *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
+    origin[s] = (unsigned char)org;
+    if (state != nullptr) state[s] = (unsigned char)(h.hops | (h.kill ? CLIFT_EDIT_STATE_KILLED : 0));
+}
+
+extern "C" int clift_edit_list_active_origin(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays,
+                                             const int* act_idx, int M, float* xa, unsigned char* origin, unsigned char* state, clift_stream_t s) {
+    EditL L;
+    if (edit_list_check(h_edits, n_edits, "clift_edit_list_active_origin", &L)) return 1;
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_active_origin: n_samples must be positive (got %d)", h_m->n_samples);
+    CLIFT_REQUIRE(xa != nullptr && origin != nullptr, "clift_edit_list_active_origin: xa and origin are both written (NULL given)");
+    if (M <= 0) return 0;
+    k_edit_list_active_origin<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, origin, state);
+    return clift_check_launch("clift_edit_list_active_origin");
 }
 
 // ============================================================================ the walk over arbitrary points

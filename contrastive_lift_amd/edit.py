@@ -168,13 +168,14 @@ class EditProgram:
     def record_bytes(self):
         return b"".join(e.record_bytes() for e in self.edits)
 
-    def _walk(self, points, dirs, jac=False):
+    def _walk(self, points, dirs, jac=False, origin=None):
         p = np.array(points, dtype=np.float64)
         d = None if dirs is None else np.array(dirs, dtype=np.float64)
         dead = np.zeros(p.shape[0], dtype=bool)
         hops = np.zeros(p.shape[0], dtype=np.uint8)
         J = np.tile(np.eye(3), (p.shape[0], 1, 1)) if jac else None
-        for e in reversed(self.edits):
+        for i in range(len(self.edits), 0, -1):
+            e = self.edits[i - 1]
             dead |= e.killed(p)                           # (a killed point is not walked further: its p stays where the walk stopped)
             if e.mode >= DUPLICATE:
                 mov = ~dead & e.dst.contains(p)
@@ -183,6 +184,8 @@ class EditProgram:
                     d[mov] = d[mov] @ e.dir_inv.T
                 if J is not None:
                     J[mov] = e.M @ J[mov]
+                if origin is not None and e.mode == DUPLICATE:
+                    origin[mov & (origin == 0)] = i
                 hops[mov] += 1
         return (p, d, dead, hops, J) if jac else (p, d, dead, hops)
 
@@ -203,6 +206,20 @@ class EditProgram:
         the maps need not be rotations."""
         p, _, dead, hops, J = self._walk(np.asarray(_host(points), dtype=np.float64).reshape(-1, 3), None, jac=True)
         return p, J, hops | np.where(dead, np.uint8(STATE_KILLED), np.uint8(0))
+
+    def origins(self, points):
+        """Which copy the content at (n, 3) world points came through, fp64 on the host: -> (source points (n, 3), origin (n,) uint8, state
+        (n,) uint8 as ``apply_to_points`` gives it).  origin is the 1-based position in the program of the FIRST edit the backward walk meets
+        that remaps the point and is a DUPLICATE -- the last-applied copy in whose destination the point sits -- and 0 if it meets none.  A
+        copy that a later edit moves keeps its origin, for a copy of a copy the outer one wins, a killed point keeps what it had when its
+        walk stopped (clift_edit_list_active_origin)."""
+        origin = np.zeros(np.asarray(_host(points)).reshape(-1, 3).shape[0], dtype=np.uint8)
+        p, _, dead, hops = self._walk(np.asarray(_host(points), dtype=np.float64).reshape(-1, 3), None, origin=origin)
+        return p, origin, hops | np.where(dead, np.uint8(STATE_KILLED), np.uint8(0))
+
+    def copies(self):
+        """The 0-based positions of the DUPLICATE edits, in program order."""
+        return [i for i, e in enumerate(self.edits) if e.mode == DUPLICATE]
 
     def apply_to_points(self, points, dirs=None, backend="device"):
         """The walk over arbitrary world points (n, 3), with view directions (n, 3) or without: -> (source points, source directions or

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from . import edit as _edit
+from . import layers as _layers
 from ._lib import Gemm, March, VM, VMGrad, call, ptr, stream
 
 
@@ -713,6 +714,7 @@ class RenderCtx:
         self.sem_grid = self.inst_grid = None                                   # state of a head on its own grid (grid_head_fwd)
         self.slots = self.layer_add = None   # layers_forward: the slot of every list row; with use_delta the world positions added to the features
         self.M_render = 0                    # layers_forward: the length of the march's own list (w > threshold), which its alpha-list replaced
+        self.base_slots = self.origin = self.state = None  # edit_layers_forward: the slots under the base table, and which copy a row's content came through
 
 
 INT_MAX = 2 ** 31 - 1
@@ -1512,32 +1514,24 @@ def surface_forward(model, renderer, rays, jitter=None, q=0.5):
 
 
 # ----------------------------------------------------------------------------- amodal instance layers
-@torch.no_grad()
-def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, use_delta=False, cap=None):
-    """Per ray and per instance slot of ``table`` (a ``layers.SlotTable``) what that instance covers ALONE, also behind what hides it: the march,
-    its samples listed again by alpha > ``alpha_thres`` (default: renderer.raymarch_weight_thres) -- a sample behind an occluder has w ~ 0 and is
-    in no render's list --, the semantic head and the fast instance net over that list (no appearance chain, no slow net, no compositing), one
-    slot per row (clift_sample_slots) and the per-ray composite that keeps one transmittance per slot (clift_ray_layers).
-    Returns (dict(layers (N, K + 1, 4) rows [A, V, Z, zf], column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed), context).
-    The context holds the alpha-list (ray_start, act_idx, M), xa, sem_s, inst_s (the fast half), slots and, with ``use_delta`` (the feature is
-    output + world position; needs 3 feature columns), layer_add.  Refused: a sync-free pass (``cap``), a field without an instance head, a table
-    that does not fit the field.  Edited scenes are out of scope."""
-    if cap is not None:
-        raise _lib.CliftError("layers_forward: a sync-free (capped) pass is not supported: the length of the alpha-list has to reach the host")
+def _layers_check(who, model, table, use_delta):
+    """The refusals the two layer passes share; -> E, the width of the instance head's fast half."""
     if model.render_instance_mlp is None:
-        raise ValueError("layers_forward: the field has no instance head")
+        raise ValueError(f"{who}: the field has no instance head")
     E = int(model.render_instance_mlp.output_channels)
     if table.num_classes != model.num_semantic_classes:
-        raise ValueError(f"layers_forward: the table knows {table.num_classes} classes, the field {model.num_semantic_classes}")
+        raise ValueError(f"{who}: the table knows {table.num_classes} classes, the field {model.num_semantic_classes}")
     if table.E != E and (table.mode == 1 or table.K > 0):
-        raise ValueError(f"layers_forward: the table expects {table.E} feature columns, the instance head gives {E}")
+        raise ValueError(f"{who}: the table expects {table.E} feature columns, the instance head gives {E}")
     if use_delta and E != 3:
-        raise ValueError(f"layers_forward: use_delta adds world positions to the features, which needs 3 columns (the head gives {E})")
-    rays, jitter = _check_rays(rays, jitter)
-    views = model.named_views()
-    ctx = _density_march(model, renderer, rays, jitter)
-    N, S, dev, st = ctx.N, ctx.S, rays.device, stream()
-    K = table.K
+        raise ValueError(f"{who}: use_delta adds world positions to the features, which needs 3 columns (the head gives {E})")
+    return E
+
+
+def _alpha_list(ctx, renderer, alpha_thres):
+    """The march's samples listed again by alpha > threshold (the count, clift_scan_counts, clift_compact_fill): the context's list becomes
+    the alpha-list, M_render keeps the length of the march's own."""
+    N, S, dev, st = ctx.N, ctx.S, ctx.rays.device, stream()
     # the same fp32 threshold for the count and for the fill, however torch compares a tensor with a Python number
     thres = float(np.float32(renderer.raymarch_weight_thres if alpha_thres is None else alpha_thres))
     n_listed = (ctx.alpha > thres).sum(1, dtype=torch.int32)
@@ -1547,27 +1541,110 @@ def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, 
     act_idx = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
     call("clift_compact_fill", ptr(ctx.alpha), ptr(ray_start), N, S, thres, ptr(act_idx), st)
     ctx.M_render, ctx.M, ctx.ray_start, ctx.act_idx = ctx.M, M, ray_start, act_idx
+    return M
+
+
+def _layer_heads(model, views, ctx):
+    """The semantic head and the fast instance net over the list (no appearance chain, no slow net)."""
+    br = Branches(model=model)
+    for slot, chain in _head_chains(model, views, ctx, _head_params(views), (), True):
+        if slot != 3:                   # (3: the slow xyz net, which no slot reads)
+            br.run(slot, chain)
+    br.join()
+
+
+def _sample_slots(ctx, renderer, table, E, use_delta):
+    """clift_sample_slots over the list under ``table``'s own slots -> (M,) int32; with ``use_delta`` the world position of the looked-up
+    point, de-normalised from xa, is the added term (ctx.layer_add)."""
+    M, dev = ctx.M, ctx.rays.device
+    cls_slots, cent = table.on(dev)
+    if use_delta:
+        ctx.layer_add = ((ctx.xa[:, :3] + 1.0) / renderer.inv_box_extent + renderer.bbox_aabb[0]).contiguous()
+    slots = torch.empty((M,), dtype=torch.int32, device=dev)
+    call("clift_sample_slots", ptr(ctx.sem_s), ctx.C, ctx.C, ptr(ctx.inst_s), ctx.D, E, ptr(ctx.layer_add), 3, ptr(cls_slots), ptr(cent), table.K_base,
+         table.mode, M, ptr(slots), stream())
+    ctx.inst_s = ctx.inst_s[:, :E]
+    return slots
+
+
+@torch.no_grad()
+def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, use_delta=False, cap=None):
+    """Per ray and per instance slot of ``table`` (a ``layers.SlotTable``) what that instance covers ALONE, also behind what hides it: the march,
+    its samples listed again by alpha > ``alpha_thres`` (default: renderer.raymarch_weight_thres) -- a sample behind an occluder has w ~ 0 and is
+    in no render's list --, the semantic head and the fast instance net over that list (no appearance chain, no slow net, no compositing), one
+    slot per row (clift_sample_slots) and the per-ray composite that keeps one transmittance per slot (clift_ray_layers).
+    Returns (dict(layers (N, K + 1, 4) rows [A, V, Z, zf], column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed), context).
+    The context holds the alpha-list (ray_start, act_idx, M), xa, sem_s, inst_s (the fast half), slots and, with ``use_delta`` (the feature is
+    output + world position; needs 3 feature columns), layer_add.  Refused: a sync-free pass (``cap``), a field without an instance head, a table
+    that does not fit the field.  This pass takes no edit: the layers of an edited scene are ``edit_layers_forward``'s."""
+    if cap is not None:
+        raise _lib.CliftError("layers_forward: a sync-free (capped) pass is not supported: the length of the alpha-list has to reach the host")
+    E = _layers_check("layers_forward", model, table, use_delta)
+    rays, jitter = _check_rays(rays, jitter)
+    views = model.named_views()
+    ctx = _density_march(model, renderer, rays, jitter)
+    N, dev, st = ctx.N, rays.device, stream()
+    K = table.K
+    M = _alpha_list(ctx, renderer, alpha_thres)
+    ray_start, act_idx = ctx.ray_start, ctx.act_idx
     ctx.C, ctx.D = model.num_semantic_classes, model.dim_feature_instance
     ctx.want = (False, False, False)
     if M > 0:
         ctx.xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
         call("clift_active_xyz", C.byref(ctx.ms), ptr(rays), ptr(jitter), ptr(act_idx), M, ptr(ctx.xa), st)
-        br = Branches(model=model)
-        for slot, chain in _head_chains(model, views, ctx, _head_params(views), (), True):
-            if slot != 3:                   # (3: the slow xyz net, which no slot reads)
-                br.run(slot, chain)
-        br.join()
-        cls_slots, cent = table.on(dev)
-        if use_delta:
-            ctx.layer_add = ((ctx.xa[:, :3] + 1.0) / renderer.inv_box_extent + renderer.bbox_aabb[0]).contiguous()
-        ctx.slots = torch.empty((M,), dtype=torch.int32, device=dev)
-        call("clift_sample_slots", ptr(ctx.sem_s), ctx.C, ctx.C, ptr(ctx.inst_s), ctx.D, E, ptr(ctx.layer_add), 3, ptr(cls_slots), ptr(cent), K,
-             table.mode, M, ptr(ctx.slots), st)
-        ctx.inst_s = ctx.inst_s[:, :E]
+        _layer_heads(model, views, ctx)
+        ctx.slots = _sample_slots(ctx, renderer, table, E, use_delta)
     out = torch.empty((N, K + 1, 4), dtype=torch.float32, device=dev)
     call("clift_ray_layers", C.byref(ctx.ms), ptr(rays), ptr(jitter), N, ptr(ctx.alpha), ptr(ctx.w), ptr(ray_start), ptr(act_idx) if M > 0 else None,
          M, ptr(ctx.slots), K, ptr(out), st)
     return dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M), ctx
+
+
+# ----------------------------------------------------------------------------- amodal instance layers of an edited scene (DESIGN.md 6j)
+@torch.no_grad()
+def edit_layers_forward(model, renderer, rays, edit, table, alpha_thres=None, use_delta=False):
+    """``layers_forward`` of the scene ``edit`` describes (whatever ``edit.as_program`` takes), with a column of its own for every copy:
+    ``table`` (the scene's ``layers.SlotTable``) is extended by ``table.for_program`` to K + c slots, c the DUPLICATE edits of the program.
+
+      edit march at renderer.raymarch_weight_thres (alpha, w) -> alpha-list (count, scan_counts, compact_fill) ->
+      clift_edit_list_active_origin (xa where the content is looked up, origin, state) -> semantic head and fast instance net on xa ->
+      clift_sample_slots under the BASE table -> retarget (a row with origin i > 0 and a slot goes to the column of copy i) ->
+      clift_ray_layers with K + c.
+
+    A killed sample has sigma exactly 0, so alpha 0: it is in no alpha-list (``alpha_thres`` < 0 is refused for that reason).  A moved
+    object keeps its slot; a copy that a later edit moves keeps its column.  With ``use_delta`` the added position is the world position of
+    the looked-up point.  Returns (dict(layers (N, K + c + 1, 4), opacity, depth of the edited scene, n_listed, table = the extended table),
+    context); the context holds the alpha-list, xa, sem_s, inst_s, slots (retargeted), base_slots, origin, state, edit_program and edited =
+    True.  The march always goes through the list kernel: a single ``Edit`` is walked as a program of one (clift_edit_list_density_fwd, whose
+    walk is that edit op for op), where ``edit_forward`` keeps the single-edit launches for it.  Refused: a head on its own VM grid (as
+    ``edit_forward``), and what ``layers_forward`` refuses."""
+    if model.semantic_plane is not None or model.instance_plane is not None:
+        raise NotImplementedError("edit_layers_forward: a semantic / instance head on its own VM grid is not supported (xyz MLP heads only)")
+    E = _layers_check("edit_layers_forward", model, table, use_delta)
+    if alpha_thres is not None and float(alpha_thres) < 0:
+        raise ValueError(f"edit_layers_forward: alpha_thres must be >= 0 (got {alpha_thres}): a killed sample has alpha 0 and stays out of the list")
+    prog = _edit.as_program(edit)
+    ext = table.for_program(prog)
+    rays, _ = _check_rays(rays, None)
+    views = model.named_views()
+    ctx, _, _ = _edit_density_march(model, renderer, rays, prog, renderer.raymarch_weight_thres)
+    N, dev, st = ctx.N, rays.device, stream()
+    M = _alpha_list(ctx, renderer, alpha_thres)
+    ctx.C, ctx.D = model.num_semantic_classes, model.dim_feature_instance
+    ctx.want = (False, False, False)
+    if M > 0:
+        ctx.xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        ctx.origin = torch.empty((M,), dtype=torch.uint8, device=dev)
+        ctx.state = torch.empty((M,), dtype=torch.uint8, device=dev)
+        call("clift_edit_list_active_origin", C.byref(ctx.ms), prog.records(), len(prog), ptr(rays), ptr(ctx.act_idx), M, ptr(ctx.xa),
+             ptr(ctx.origin), ptr(ctx.state), st)
+        _layer_heads(model, views, ctx)
+        ctx.base_slots = _sample_slots(ctx, renderer, table, E, use_delta)
+        ctx.slots = _layers.retarget(ctx.base_slots, ctx.origin, ext)
+    out = torch.empty((N, ext.K + 1, 4), dtype=torch.float32, device=dev)
+    call("clift_ray_layers", C.byref(ctx.ms), ptr(rays), None, N, ptr(ctx.alpha), ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx) if M > 0 else None,
+         M, ptr(ctx.slots), ext.K, ptr(out), st)
+    return dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M, table=ext), ctx
 
 
 # ----------------------------------------------------------------------------- surface outputs of an edited scene (DESIGN.md 6h)

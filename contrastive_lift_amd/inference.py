@@ -96,6 +96,25 @@ def render_rays_layers(model, renderer, rays, chunk, white_bg=False, table=None,
     return tuple(torch.cat(x, 0) for x in outs)
 
 
+@torch.no_grad()
+def render_rays_edit_layers(model, renderer, rays, chunk, white_bg=False, table=None, edit=None, alpha_thres=None, use_delta=False):
+    """Chunked ``engine.edit_layers_forward``: the amodal instance layers of the scene ``edit`` describes, under the slot table
+    ``table`` extended by one column per copy (``table.for_program(edit)`` names them).  Returns layers (P, K + c + 1, 4), opacity (P,),
+    distance (P,) like ``render_rays_layers``; a ray's layers depend on that ray alone, so the chunking changes no bit.  With ``table``,
+    ``edit``, ``alpha_thres`` and ``use_delta`` bound (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``."""
+    if table is None:
+        raise ValueError("render_rays_edit_layers: a slot table is required (layers.SlotTable)")
+    if edit is None:
+        raise ValueError("render_rays_edit_layers: an edit is required")
+    outs = [[], [], []]
+    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
+    for i in range(0, rays.shape[0], chunk):
+        o, ctx = engine.edit_layers_forward(model, renderer, rays[i:i + chunk], edit, table, alpha_thres=alpha_thres, use_delta=use_delta)
+        outs[0].append(o["layers"]); outs[1].append(o["opacity"].clone()); outs[2].append(o["depth"].clone())
+        del ctx
+    return tuple(torch.cat(x, 0) for x in outs)
+
+
 def tile_bounds(n, world):
     """Contiguous row-tile boundaries of n rays over `world` ranks (sizes differ by at most one)."""
     return [(n * r) // world for r in range(world + 1)]

@@ -190,6 +190,12 @@ class TensoRFRenderer(nn.Module):
         column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed).  No jitter (is_train False), no gradient."""
         return engine.layers_forward(tensorf, self, rays, table, None, alpha_thres, use_delta)[0]
 
+    def forward_edit_layers(self, tensorf, rays, edit, table, alpha_thres=None, use_delta=False):
+        """``forward_layers`` of the scene ``edit`` describes (an ``edit.Edit``, an ``edit.EditProgram`` or a sequence of edits): the same dict
+        with ``layers`` (N, K + c + 1, 4), one more instance column per copy of the program, and ``table``, the slot table extended by
+        those columns (engine.edit_layers_forward).  No jitter, no gradient."""
+        return engine.edit_layers_forward(tensorf, self, rays, edit, table, alpha_thres, use_delta)[0]
+
     # ------------------------------------------------------------------ scene edits (renderer.py:303-623)
     def _forward_edit(self, tensorf, rays, white_bg, resolved):
         out, _ = engine.edit_forward(tensorf, self, rays, resolved, white_bg)

@@ -194,6 +194,16 @@ int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, const float
 int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, int n_edits, const float* h_lo3, const float* h_hi3,
                                 const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2, float shift,
                                 float* out, unsigned char* state, clift_stream_t s);
+/* The walk of an alpha-list with the ORIGIN of its content (a further ABI 27 addition): clift_edit_list_active without the view
+ * directions, for the layers of an edited scene.  One thread per list row; rows past the dynamic row limit are not written.  xa (M, 4): the bits
+ * of clift_edit_list_active's xa for the same arguments, [xn, 0].  origin (M) uint8: walking the program backwards, i = n .. 1, the 1-based position
+ * of the FIRST edit met that remaps the sample and has mode CLIFT_EDIT_DUPLICATE, 0 if the walk meets none -- the last-applied copy in whose
+ * destination the sample sits.  A copy that a later edit moves keeps its origin (the move remaps the sample, then the walk meets the copy); for
+ * a copy of a copy the outer one wins; a killed sample keeps what it had when its walk stopped.  state (M) uint8 or NULL: the byte of
+ * clift_edit_list_points for the same world point.  M <= 0 returns 0 without a launch.  Errors, raised before anything is launched: the
+ * program's, n_samples < 1, a NULL xa or origin. */
+int clift_edit_list_active_origin(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
+                                  float* xa, unsigned char* origin, unsigned char* state, clift_stream_t s);
 
 /* ---- a7-a8: renderer.py:83-84,100-103,137,173-174,626-631 + eff_distloss (renderer.py:101).
  * Per sample alpha, T (transmittance before the sample), w = alpha*T, all (N, S).

@@ -4,6 +4,7 @@
     python inference/edit_scene.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt --bboxes bboxes.pkl --instance ID
                                    --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz] [--pad 0.0]
                                    [--render_trajectory] [--image_dim H W] [--weight_thres 0] [--save_surface [--surface_quantile 0.5]]
+                                   [--save_layers --cached_centroids_path C [--layers_level 0.5]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
@@ -15,6 +16,11 @@ rendered as row-tiles over the ranks.  Writes ``rgb/*.png``, ``pred_semantics/*.
 ``runs/<scene>_<test|trajectory>_<experiment>_edit_<op>_<id>/``.  ``--save_surface`` adds the surface outputs of the EDITED scene
 (DESIGN.md 6h), in the files of ``inference/render_panopli.py --save_surface``: ``surface/<frame>.npz`` (depth_median, hit, normals) and
 ``vis_normals/<frame>.png``; ``--surface_quantile Q`` moves the hit from the median (0.5) to another quantile of the ray's weight.
+``--save_layers`` adds the amodal instance layers of the EDITED scene, in the files of ``inference/render_panopli.py
+--save_layers``: ``layers/<frame>.npz``, ``layers/<frame>.json`` and ``vis_amodal/<frame>.png``, in the scene's fixed slot numbering with
+one more slot per copy of the program (slot_class -1, slot_index = the copy's 0-based position in the program), and
+``layers/<frame>_change.json``: per slot what the edit hid, revealed or removed (``layers.compare`` of the unedited and the edited frame,
+one more plain layer pass per frame).  The slots come from ``--cached_centroids_path`` (a linear-assignment model needs none).
 
 ``--script FILE.json`` applies up to 8 edits in ONE render (``edit.EditProgram``), in file order.  The file holds a list of
 ``{"instance": id, "op": "delete|extract|copy|move", "translate": [x, y, z], "rotate_deg": [rx, ry, rz], "pad": p, "at": "moved"}``;
@@ -90,11 +96,16 @@ def resolve_program(boxes, entries):
 
 
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
-                          save_surface=False, surface_quantile=0.5):
+                          save_surface=False, surface_quantile=0.5, save_layers=False, cached_centroids_path=None, layers_level=0.5):
     out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}")
     device, rank = rp.distributed_device(device)
     scene, model, renderer = rp.load_for_inference(config, device)
     H, W = scene.image_dim
+    if save_layers:
+        table = rp.layers_table(config, scene, cached_centroids_path)
+        table_edit = table.for_program(edit)
+        layers_fn = functools.partial(inf.render_rays_layers, table=table, use_delta=bool(config.use_delta))
+        edit_layers_fn = functools.partial(inf.render_rays_edit_layers, table=table, edit=edit, use_delta=bool(config.use_delta))
     if save_surface:
         render_fn = functools.partial(inf.render_rays_edit_surface, edit=edit, weight_thres=float(weight_thres), q=float(surface_quantile))
     else:
@@ -106,6 +117,9 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
         for name, rays, K_frame in rp.scene_frames(scene, trajectory_name, test_only):
             p_rgb, p_sem, _, p_dist, *p_surface = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg,
                                                                           render_fn=render_fn)
+            if save_layers:         # every rank renders its tiles of the two layer passes (each ends in a collective); rank 0 writes
+                lay_after = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=edit_layers_fn)[0]
+                lay_before = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=layers_fn)[0]
             if rank != 0:
                 continue
             rgb = (p_rgb.reshape(H, W, 3).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
@@ -116,7 +130,31 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
                 p_dmed, p_hit, p_nrm = p_surface
                 rp.write_surface_frame(out, name, inf.distance_to_depth(K_frame, p_dmed.view(H, W)).reshape(H, W), (p_hit > 0.5).reshape(H, W),
                                        p_nrm.reshape(H, W, 3))
+            if save_layers:
+                write_layers(out, name, lay_before, lay_after, table, table_edit, H, W, p_rgb, layers_level)
+                del lay_before, lay_after
     return out
+
+
+def change_summary(frame_name, before, after, table, table_edit, level):
+    """The dict of ``layers/<frame>_change.json``: ``layers.compare`` of the unedited and the edited frame, one entry per slot that has an
+    amodal pixel on either side."""
+    from contrastive_lift_amd import layers as ly
+    col = {k: v.cpu().numpy() for k, v in ly.compare(before, after, table, table_edit, level).items()}
+    keys = ("amodal_pixels_before", "amodal_pixels_after", "visible_pixels_before", "visible_pixels_after", "newly_hidden", "revealed", "gone")
+    present = np.nonzero((col["amodal_pixels_before"] > 0) | (col["amodal_pixels_after"] > 0))[0]
+    return dict(frame=str(frame_name), level=float(level), n_slots=int(table_edit.K), n_base_slots=int(table.K),
+                copy_edit=[int(i) for i in table_edit.copy_edit],
+                slots=[dict(slot=int(i), slot_class=int(col["slot_class"][i]), slot_index=int(col["slot_index"][i]),
+                            **{k: int(col[k][i]) for k in keys}) for i in present])
+
+
+def write_layers(out, name, before, after, table, table_edit, H, W, p_rgb, level):
+    """The files of ``--save_layers`` for one frame, from the layers of the unedited (``before``) and the edited (``after``) frame: the
+    edited scene's written like ``render_panopli.py --save_layers`` writes a plain one, and ``layers/<frame>_change.json``."""
+    rp.write_layers_frame(out, name, after, table_edit, H, W, p_rgb, level)
+    with open(out / "layers" / f"{name}_change.json", "w") as f:
+        json.dump(change_summary(name, before, after, table, table_edit, level), f, indent=1)
 
 
 def main(argv=None):
@@ -140,6 +178,12 @@ def main(argv=None):
                          "inference/render_panopli.py --save_surface does for the unedited one")
     ap.add_argument("--surface_quantile", type=float, default=0.5, metavar="Q",
                     help="--save_surface: the hit is where the ray has lost this share of its transmittance (0.5: the median depth)")
+    ap.add_argument("--save_layers", action="store_true",
+                    help="also write layers/<frame>.npz, layers/<frame>.json, vis_amodal/<frame>.png of the EDITED scene (one more slot per copy) "
+                         "and layers/<frame>_change.json, what the edit hid, revealed or removed per slot")
+    ap.add_argument("--cached_centroids_path", type=str, default=None,
+                    help="--save_layers: all_centroids.pkl of inference/extract_train_centroids.py (not needed for a linear_assignment model)")
+    ap.add_argument("--layers_level", type=float, default=0.5, help="the opacity above which --save_layers counts a pixel into a mask")
     args = ap.parse_args(argv)
     if args.script is not None and (args.instance is not None or args.op is not None):
         ap.error("--script holds the edits: give it without --instance / --op")
@@ -157,7 +201,8 @@ def main(argv=None):
     else:
         the_edit, tag = resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad), f"{args.op}_{args.instance}"
     print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
-                                save_surface=args.save_surface, surface_quantile=args.surface_quantile))
+                                save_surface=args.save_surface, surface_quantile=args.surface_quantile, save_layers=args.save_layers,
+                                cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level))
 
 
 if __name__ == "__main__":
