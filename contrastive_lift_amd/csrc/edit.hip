@@ -3,13 +3,16 @@
 // split_points_minimal (:785-797).  The render kernels recompute a sample's position from (ray, jitter, k), so a per-sample mask or a
 // coordinate remap cannot be injected between them from outside: an edit render has these two kernels in their place and then runs on
 // the point-wise kernels (clift_vm_products_points, clift_app_encode_points), the MLP chains and the march / compaction / compositing
-// kernels unchanged.  Edits render without jitter (perturb = 0, is_train = False in the reference's four methods).
+// kernels unchanged.  Edits render without jitter (perturb = 0, is_train = False in the reference's four methods).  The density kernel is
+// the march's own sweep body (density_sweep_dev.h) with another look-up rule, so an untouched sample has the bits of the plain pass.
 // An edit PROGRAM (clift_edit_list_*) is an ordered list e_1 .. e_n of up to CLIFT_EDIT_MAX such edits in one render: scene_i is e_i applied
 // to scene_{i-1}, and a sample is evaluated in scene_n by walking the list backwards (edit_walk).  The program is a by-value kernel
 // argument: the records are the same for every lane, the trip count is wave-uniform and the records arrive through scalar loads.
+// There is ONE kernel family, the program's: a single edit (clift_edit_density_fwd, clift_edit_active) is a program of one inside the library.
 // The same walk also runs off the rays (clift_edit_list_points, clift_edit_list_dense_sigma) and, with the chain of the remaps carried beside
 // the point, gives the gradient of the EDITED density for the surface outputs of an edited scene (clift_edit_list_density_grad_*, at the end).
 #include "clift_dev.h"
+#include "density_sweep_dev.h"
 #include "lattice_dev.h"
 #include "surface_dev.h"
 #include <math.h>
@@ -71,6 +74,14 @@ static int edit_list_check(const clift_edit_t* e, int n, const char* who, EditL*
     for (int i = 0; i < CLIFT_EDIT_MAX; ++i) out->e[i] = to_dev(e + (i < n ? i : 0));      // (the slots past n are never read)
     return 0;
 }
+// A single edit (clift_edit_density_fwd, clift_edit_active) is a program of one: the entry points keep their own checks and messages
+// (edit_check) and run the list kernels.
+static EditL edit_list_of_one(const clift_edit_t* e) {
+    EditL L;
+    L.n = 1;
+    for (int i = 0; i < CLIFT_EDIT_MAX; ++i) L.e[i] = to_dev(e);
+    return L;
+}
 
 // row-vector product of a row-major 3x3 with v, every multiply / add rounded separately, left to right
 __device__ __forceinline__ float row3(const float* a, const float v[3]) {
@@ -88,44 +99,17 @@ __device__ __forceinline__ bool in_box(const BoxP& b, const float p[3]) {
     return in;
 }
 
-// One sample under the edit.  World point and in-aabb flag from the UNEDITED sample with sample_xn's separately rounded ops (the reference
-// takes mask_xyz before it remaps, :304,457,540), box classification in fp32, then the affine remap of a sample inside the destination
-// box; xn = normalised coordinates of the (remapped) point -- the very bits of sample_xn when the sample is not remapped.
-struct EditS {
-    bool in;      // inside the aabb (before the remap)
-    bool kill;    // sigma = 0 by the edit's kill rule
-    bool moved;   // inside the destination box: position remapped, view direction turned
-};
-__device__ __forceinline__ EditS edit_sample(const RayG& g, const MarchP& m, const EditP& e, float z, float xn[3]) {
-    EditS s;
-    float p[3];
-    s.in = true;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
-        s.in = s.in && !(m.lo[i] > p[i]) && !(p[i] > m.hi[i]);
-    }
-    const bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
-    s.moved = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
-    s.kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !s.moved) : false;
-    if (s.moved) {
-        const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
-        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) xn[i] = __fsub_rn(__fmul_rn(__fsub_rn(p[i], m.lo[i]), m.inv2[i]), 1.0f);
-    return s;
-}
-
-// One sample under an edit program, walked BACKWARDS from e_n to e_1: every box test and every remap on the CURRENT point with the ops of
-// edit_sample; a killed sample stops (sigma = 0, nothing is looked up); a sample inside edit i's destination box continues at M_i p + t_i with
-// the view direction Dinv_i d.  The in-aabb flag is taken once, from the unedited point.  For n = 1 this is edit_sample, op for op; a sample
-// no edit remaps keeps the bits of sample_xn.  L lives in the kernel-argument segment and i is wave-uniform: scalar loads, no scratch copy.
+// One sample under an edit program, walked BACKWARDS from e_n to e_1: box classification in fp32 and the affine remap on the CURRENT point,
+// every multiply and add rounded separately; a killed sample stops (sigma = 0, nothing is looked up); a sample inside edit i's destination
+// box continues at M_i p + t_i with the view direction Dinv_i d.  World point and in-aabb flag come once, from the UNEDITED sample, with
+// sample_xn's separately rounded ops (the reference takes mask_xyz before it remaps, :304,457,540); a sample no edit remaps keeps the bits
+// of sample_xn.  L lives in the kernel-argument segment and i is wave-uniform: scalar loads, no scratch copy.
 // The POINT form of the walk, shared by the ray kernels (edit_walk) and the point / lattice kernels below: p and d are walked in place.
 struct EditH {
     bool kill;    // sigma = 0: some edit's kill rule named the point (p, d: where the walk stopped)
     int hops;     // how many edits remapped it (0 .. CLIFT_EDIT_MAX)
 };
+__device__ __forceinline__ unsigned char edit_state(const EditH& h) { return (unsigned char)(h.hops | (h.kill ? CLIFT_EDIT_STATE_KILLED : 0)); }
 // ``hop(e, i)`` is called for every edit that remaps the point (i its 0-based position in the program), before p is replaced: what else
 // travels with the point (the view direction, the Jacobian of the chain, the origin of a copy) is turned there.
 template <class Hop>
@@ -199,118 +183,19 @@ __device__ __forceinline__ EditW edit_walk(const RayG& g, const MarchP& m, const
 }
 
 // ============================================================================ density forward under an edit
-// The wave-per-sweep form of k_density_fwd_ray (march.hip), restated here because the tap records are built from the EDITED position: lane =
-// sample sets the ray up once, classifies and remaps its sample and writes the tap records of the three planes to the wave's LDS slot; four
-// passes of 16 samples x 4 lanes then do the 18 table reads.  Same taps, same FMA order, same quad sum as clift_density_fwd, so a sample
-// the edit neither remaps nor kills gets the very bits of the unedited pass.  A remapped point may leave the aabb: make_tap clamps every
-// index and zeroes the weight of a tap outside the table (grid_sample's zero padding), as k_density_points relies on.  A killed sample
+// The march's own wave-per-sweep body (density_sweep, density_sweep_dev.h) with another look-up rule: no jitter, and lane = sample walks the
+// program before the tap records are built from the EDITED position.  Same taps, same FMA order, same quad sum as clift_density_fwd, so a
+// sample the edit neither remaps nor kills gets the very bits of the unedited pass.  A remapped point may leave the aabb: make_tap clamps
+// every index and zeroes the weight of a tap outside the table (grid_sample's zero padding), as k_density_points relies on.  A killed sample
 // reads no table at all.  With a remap the samples that are looked up are no prefix of the ray any more: the only early exit left is a
 // sweep none of whose samples is looked up.
-struct alignas(16) EdRec {
-    int o[4];
-    float w[4];
-    int z[2];
-    float wz[2];
-};
-constexpr int EDR_WAVES = 4;
-
-// is the sample looked up (inside the aabb, not killed), and at which normalised position: under one edit, under a program
-__device__ __forceinline__ bool edit_looked_up(const RayG& g, const MarchP& m, const EditP& e, float z, float xn[3]) {
-    const EditS s = edit_sample(g, m, e, z, xn);
-    return s.in && !s.kill;
-}
-__device__ __forceinline__ bool edit_looked_up(const RayG& g, const MarchP& m, const EditL& L, float z, float xn[3]) {
-    float d[3];
-    const EditW s = edit_walk(g, m, L, z, xn, d);
-    return s.in && !s.kill;
-}
-
-// E = EditP (one edit) or EditL (a program): the two kernels differ in edit_looked_up alone
-template <class E>
-__device__ __forceinline__ void edit_density_fwd(const MarchP& m, const E& e, const VmP& t, const float* __restrict__ rays, int N,
-                                                 float* __restrict__ sigma) {
-    __shared__ EdRec recs_all[EDR_WAVES][3][64];
-    __shared__ float sig_all[EDR_WAVES][64];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nsw = (m.S + 63) / 64;                         // sweeps per ray
-    const long item = (long)blockIdx.x * EDR_WAVES + wave;
-    if (item >= (long)N * nsw) return;
-    const int r = (int)(item / nsw);
-    EdRec (*recs)[64] = recs_all[wave];
-    float* sig = sig_all[wave];
-    const RayG g = load_ray(rays, r, m);
-    const int C = t.comps;
-    float* out = sigma + (size_t)r * m.S;
-    const int k = (int)(item - (long)r * nsw) * 64 + lane;
-    float xn[3];
-    const bool on = k < m.S && edit_looked_up(g, m, e, sample_z(g, m, k, 0.f), xn);
-    const unsigned long long onmask = __ballot(on);
-    if (onmask == 0) {                                       // wave-uniform
-        if (k < m.S) out[k] = 0.f;
-        return;
-    }
-    if (on) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const VmTaps tp = vm_taps(t, i, xn);
-            int a_, b_, v_;
-            vm_axes(i, a_, b_, v_);
-            const int W = t.res[a_];
-            int4* dst = reinterpret_cast<int4*>(&recs[i][lane]);
-            dst[0] = make_int4((tp.ty.i0 * W + tp.tx.i0) * C, (tp.ty.i0 * W + tp.tx.i1) * C, (tp.ty.i1 * W + tp.tx.i0) * C, (tp.ty.i1 * W + tp.tx.i1) * C);
-            dst[1] = make_int4(__float_as_int(tp.tx.w0 * tp.ty.w0), __float_as_int(tp.tx.w1 * tp.ty.w0), __float_as_int(tp.tx.w0 * tp.ty.w1),
-                               __float_as_int(tp.tx.w1 * tp.ty.w1));
-            dst[2] = make_int4(tp.tz.i0 * C, tp.tz.i1 * C, __float_as_int(tp.tz.w0), __float_as_int(tp.tz.w1));
-        }
-    }
-    sig[lane] = 0.f;
-    __builtin_amdgcn_wave_barrier();
-    const int q = lane & 3;
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int sl = pass * 16 + (lane >> 2);
-        const bool mine = (onmask >> sl) & 1ull;
-        if ((onmask >> (pass * 16)) & 0xffffull) {           // wave-uniform: some sample of this pass is looked up
-            float acc = 0.f;
-            if (mine) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int4* rp = reinterpret_cast<const int4*>(&recs[i][sl]);
-                    const int4 o = rp[0], wi = rp[1], zi = rp[2];
-                    for (int c4 = q * 4; c4 < C; c4 += 16) {
-                        const float* pp = t.plane[i] + c4;
-                        const float* lp = t.line[i] + c4;
-                        float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
-                        pa = f4_fma(__int_as_float(wi.x), ld4(pp + (unsigned)o.x), pa);
-                        pa = f4_fma(__int_as_float(wi.y), ld4(pp + (unsigned)o.y), pa);
-                        pa = f4_fma(__int_as_float(wi.z), ld4(pp + (unsigned)o.z), pa);
-                        pa = f4_fma(__int_as_float(wi.w), ld4(pp + (unsigned)o.w), pa);
-                        float4 la = make_float4(0.f, 0.f, 0.f, 0.f);
-                        la = f4_fma(__int_as_float(zi.z), ld4(lp + (unsigned)zi.x), la);
-                        la = f4_fma(__int_as_float(zi.w), ld4(lp + (unsigned)zi.y), la);
-                        acc += f4_hsum(f4_mul(pa, la));
-                    }
-                }
-            }
-            acc += __shfl_xor(acc, 1);
-            acc += __shfl_xor(acc, 2);
-            if (q == 0 && mine) {
-                const float x = acc + m.shift;
-                sig[sl] = (x > 20.f) ? x : log1pf(expf(x));
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (k < m.S) out[k] = sig[lane];
-}
-
-__global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_density_fwd(MarchP m, EditP e, VmP t, const float* __restrict__ rays, int N,
-                                                                     float* __restrict__ sigma) {
-    edit_density_fwd(m, e, t, rays, N, sigma);
-}
-__global__ __launch_bounds__(64 * EDR_WAVES) void k_edit_list_density_fwd(MarchP m, EditL L, VmP t, const float* __restrict__ rays, int N,
-                                                                          float* __restrict__ sigma) {
-    edit_density_fwd(m, L, t, rays, N, sigma);
+__global__ __launch_bounds__(64 * SWEEP_WAVES) void k_edit_list_density_fwd(MarchP m, EditL L, VmP t, const float* __restrict__ rays, int N,
+                                                                            float* __restrict__ sigma) {
+    density_sweep(m, t, rays, nullptr, N, sigma, [&](const RayG& g, float z, float xn[3]) {
+        float d[3];
+        const EditW s = edit_walk(g, m, L, z, xn, d);
+        return s.in && !s.kill;
+    });
 }
 
 extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit, const clift_vm_t* h_dens, const float* rays, int N,
@@ -319,8 +204,8 @@ extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit
     CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
     CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
     if (N <= 0) return 0;
-    k_edit_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), EDR_WAVES), 64 * EDR_WAVES, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_edit), to_dev(h_dens),
-                                                                                                                 rays, N, sigma);
+    k_edit_list_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES), 64 * SWEEP_WAVES, 0, as_stream(s)>>>(to_dev(h_m), edit_list_of_one(h_edit),
+                                                                                                                          to_dev(h_dens), rays, N, sigma);
     return clift_check_launch("clift_edit_density_fwd");
 }
 
@@ -331,28 +216,35 @@ extern "C" int clift_edit_list_density_fwd(const clift_march_t* h_m, const clift
     CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_list_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
     CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
     if (N <= 0) return 0;
-    k_edit_list_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), EDR_WAVES), 64 * EDR_WAVES, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens), rays,
-                                                                                                                      N, sigma);
+    k_edit_list_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES), 64 * SWEEP_WAVES, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens),
+                                                                                                                          rays, N, sigma);
     return clift_check_launch("clift_edit_list_density_fwd");
 }
 
 // ============================================================================ positions and view directions of the active samples
 // The same classification, recomputed (not stored: (N, S) flags would cost more traffic than the few dozen ops).  xa feeds the xyz heads and
 // clift_vm_products_points, dirs feeds clift_app_encode_points.
-__global__ __launch_bounds__(256) void k_edit_active(MarchP m, EditP e, const float* __restrict__ rays, const int* __restrict__ act, int M,
-                                                      float* __restrict__ xa, float* __restrict__ dirs) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= limit_rows(M)) return;
+// Row s of the active list: its ray, and the UNEDITED world point of its sample (no jitter) with sample_xn's separately rounded ops.
+__device__ __forceinline__ RayG edit_active_point(const MarchP& m, const float* __restrict__ rays, const int* __restrict__ act, long s, float p[3]) {
     const int sid = act[s];
     const int r = sid / m.S, k = sid - r * m.S;
     const RayG g = load_ray(rays, r, m);
-    float xn[3];
-    const EditS es = edit_sample(g, m, e, sample_z(g, m, k, 0.f), xn);
+    const float z = sample_z(g, m, k, 0.f);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+    return g;
+}
+
+// The walk recomputed, the view direction turned by every edit that remapped the sample
+__global__ __launch_bounds__(256) void k_edit_list_active(MarchP m, EditL L, const float* __restrict__ rays, const int* __restrict__ act, int M,
+                                                           float* __restrict__ xa, float* __restrict__ dirs) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= limit_rows(M)) return;
+    float p[3], xn[3];
+    const RayG g = edit_active_point(m, rays, act, s, p);
     float d[3] = {g.d[0], g.d[1], g.d[2]};
-    if (es.moved) {
-        const float v[3] = {row3(e.Dinv, g.d), row3(e.Dinv + 3, g.d), row3(e.Dinv + 6, g.d)};
-        d[0] = v[0]; d[1] = v[1]; d[2] = v[2];
-    }
+    edit_walk_point(L, p, d);
+    edit_normalise(p, m.lo, m.inv2, xn);
     *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
     *reinterpret_cast<float4*>(dirs + (size_t)s * 4) = make_float4(d[0], d[1], d[2], 0.f);
 }
@@ -363,22 +255,8 @@ extern "C" int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h
     CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_active: n_samples must be positive (got %d)", h_m->n_samples);
     CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_active: xa and dirs are both written");
     if (M <= 0) return 0;
-    k_edit_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), to_dev(h_edit), rays, act_idx, M, xa, dirs);
+    k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), edit_list_of_one(h_edit), rays, act_idx, M, xa, dirs);
     return clift_check_launch("clift_edit_active");
-}
-
-// k_edit_active under an edit program: the walk recomputed, the view direction turned by every edit that remapped the sample
-__global__ __launch_bounds__(256) void k_edit_list_active(MarchP m, EditL L, const float* __restrict__ rays, const int* __restrict__ act, int M,
-                                                           float* __restrict__ xa, float* __restrict__ dirs) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= limit_rows(M)) return;
-    const int sid = act[s];
-    const int r = sid / m.S, k = sid - r * m.S;
-    const RayG g = load_ray(rays, r, m);
-    float xn[3], d[3];
-    edit_walk(g, m, L, sample_z(g, m, k, 0.f), xn, d);
-    *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
-    *reinterpret_cast<float4*>(dirs + (size_t)s * 4) = make_float4(d[0], d[1], d[2], 0.f);
 }
 
 extern "C" int clift_edit_list_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
@@ -401,13 +279,8 @@ __global__ __launch_bounds__(256) void k_edit_list_active_origin(MarchP m, EditL
                                                                   unsigned char* __restrict__ state) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= limit_rows(M)) return;
-    const int sid = act[s];
-    const int r = sid / m.S, k = sid - r * m.S;
-    const RayG g = load_ray(rays, r, m);
-    const float z = sample_z(g, m, k, 0.f);
     float p[3], xn[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+    edit_active_point(m, rays, act, s, p);
     int org = 0;
     const EditH h = edit_walk_core(L, p, [&](const EditP& e, int i) {
         if (org == 0 && e.mode == CLIFT_EDIT_DUPLICATE) org = i + 1;
@@ -415,7 +288,7 @@ __global__ __launch_bounds__(256) void k_edit_list_active_origin(MarchP m, EditL
     edit_normalise(p, m.lo, m.inv2, xn);
     *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
     origin[s] = (unsigned char)org;
-    if (state != nullptr) state[s] = (unsigned char)(h.hops | (h.kill ? CLIFT_EDIT_STATE_KILLED : 0));
+    if (state != nullptr) state[s] = edit_state(h);
 }
 
 extern "C" int clift_edit_list_active_origin(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays,
@@ -433,8 +306,6 @@ extern "C" int clift_edit_list_active_origin(const clift_march_t* h_m, const cli
 // One thread per row: world point (and view direction) in, the point (and direction) at which the field is to be looked up out, plus the
 // state byte.  No aabb test and no table: what "inside the scene" means is the caller's business (mesh.label_vertices, the lattice below).
 // A row no edit remaps is copied through untouched, so it keeps its input bits.  in == out is allowed (a thread reads its row, then writes it).
-__device__ __forceinline__ unsigned char edit_state(const EditH& h) { return (unsigned char)(h.hops | (h.kill ? CLIFT_EDIT_STATE_KILLED : 0)); }
-
 __global__ __launch_bounds__(256) void k_edit_list_points(EditL L, const float* pts, int ldp, const float* dirs, int ldd, long n, float* out_pts,
                                                            float* out_dirs, unsigned char* state) {
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -472,7 +343,7 @@ extern "C" int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, 
 // clift_dense_sigma (isosurface.hip) with the program in it, one launch.  k_dense_sigma gives 4 lanes to a lattice point for the 18 table
 // reads; the walk is a few hundred VALU ops per point at 8 edits and would be done four times over if every lane of the quad walked.  So
 // the two phases use two mappings of one wave's 64 points: for the walk lane = point (lattice_point, then edit_walk_point, each done ONCE
-// per point), and for the taps four passes of 16 points x 4 lanes, as in edit_density_fwd, the quad fetching its point's normalised
+// per point), and for the taps four passes of 16 points x 4 lanes, as in density_sweep, the quad fetching its point's normalised
 // position from the lane that walked it by __shfl -- registers only, no LDS.  The records arrive by scalar loads (L is a kernel
 // argument, the trip count is wave-uniform).  A killed point reads no table and gets exactly 0; a pass none of whose 16 points is alive
 // is skipped, and a wave all of whose points are killed leaves after the walk.  A point no edit remaps keeps the xn of lattice_point
@@ -610,13 +481,8 @@ __global__ __launch_bounds__(256) void k_edit_list_density_grad_active(MarchP m,
     const long base = v - lane;
     if (base >= total) return;                                       // wave-uniform
     const bool valid = v < total;
-    const int sid = act[valid ? v : total - 1];
-    const int r = sid / m.S, k = sid - r * m.S;
-    const RayG g = load_ray(rays, r, m);
-    const float z = sample_z(g, m, k, 0.f);
     float p[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+    edit_active_point(m, rays, act, valid ? v : total - 1, p);
     edit_density_grad_wave(t, L, p, valid, m.lo, m.inv2, m.shift, base, total, out, nullptr);
 }
 

@@ -112,6 +112,54 @@ def test_density_fwd_both_forms(capsys):
     t.close(capsys)
 
 
+def test_density_sweep_is_one_body_for_the_march_and_the_edits():
+    """k_density_fwd_ray and the edit density kernel run ONE sweep body (csrc/density_sweep_dev.h), and a single edit is a program of one.  At
+    every march case (S < 64, S no multiple of 64, N * ceil(S / 64) no multiple of a block's four waves, rays that miss the box), without
+    jitter and under a DELETE whose box no sample of the scene can reach: the plain pass in both forms, the single-edit entry point and the
+    program entry point with the edit once and eight times give the same bits, and none writes past row N.  Then, over the in-box samples:
+    clift_active_xyz, clift_edit_active and clift_edit_list_active give the same positions, and the view directions come back untouched."""
+    from contrastive_lift_amd import edit, engine
+    L, broken = _L(), []
+    for c in mc.march_cases():
+        ext = np.asarray(c.hi, np.float64) - np.asarray(c.lo, np.float64)
+        far = edit.Edit(edit.DELETE, edit.EditBox(np.eye(3), np.asarray(c.hi, np.float64) + 64.0 * ext, -0.5 * np.ones(3), 0.5 * np.ones(3)))
+        one, eight = far.record(), (L.EditRec * 8)(*(far.record() for _ in range(8)))
+        m, (v, tabs), rays = _march_struct(L, c), _vm(L, c), _d(c.rays)
+        sig = {k: torch.full((c.N + 1, c.S), float(SENTINEL), device=DEV) for k in ("ray", "thread", "edit", "list1", "list8")}
+        for form in (False, True):
+            with engine.kernel_switches(dens_fwd_thread=form):
+                L.call("clift_density_fwd", C.byref(m), C.byref(v), L.ptr(rays), None, c.N, L.ptr(sig["thread" if form else "ray"]), L.stream())
+        L.call("clift_edit_density_fwd", C.byref(m), C.byref(one), C.byref(v), L.ptr(rays), c.N, L.ptr(sig["edit"]), L.stream())
+        L.call("clift_edit_list_density_fwd", C.byref(m), C.byref(one), 1, C.byref(v), L.ptr(rays), c.N, L.ptr(sig["list1"]), L.stream())
+        L.call("clift_edit_list_density_fwd", C.byref(m), eight, 8, C.byref(v), L.ptr(rays), c.N, L.ptr(sig["list8"]), L.stream())
+        sig = {k: s.cpu() for k, s in sig.items()}
+        for k, s in sig.items():
+            if not torch.equal(s[:c.N].view(torch.int32), sig["ray"][:c.N].view(torch.int32)):
+                broken.append(f"{c.name}: sigma of '{k}' differs from the ray form in some bit")
+            if not bool((s[c.N] == SENTINEL).all()):
+                broken.append(f"{c.name}: '{k}' wrote past row N")
+
+        act_np = np.flatnonzero(mc.geometry(c).mask.reshape(-1)).astype(np.int32)          # row-major: sid = r * S + k
+        if act_np.size == 0:
+            continue
+        M, act = int(act_np.size), _d(act_np, torch.int32)
+        xa = {k: torch.full((M, 4), float(SENTINEL), device=DEV) for k in ("plain", "edit", "list1")}
+        dirs = {k: torch.full((M, 4), float(SENTINEL), device=DEV) for k in ("edit", "list1")}
+        L.call("clift_active_xyz", C.byref(m), L.ptr(rays), None, L.ptr(act), M, L.ptr(xa["plain"]), L.stream())
+        L.call("clift_edit_active", C.byref(m), C.byref(one), L.ptr(rays), L.ptr(act), M, L.ptr(xa["edit"]), L.ptr(dirs["edit"]), L.stream())
+        L.call("clift_edit_list_active", C.byref(m), C.byref(one), 1, L.ptr(rays), L.ptr(act), M, L.ptr(xa["list1"]), L.ptr(dirs["list1"]), L.stream())
+        want_d = torch.from_numpy(np.ascontiguousarray(c.rays[act_np // c.S, 3:6])).view(torch.int32)
+        for k in ("edit", "list1"):
+            if not torch.equal(xa[k].cpu().view(torch.int32), xa["plain"].cpu().view(torch.int32)):
+                broken.append(f"{c.name}: xa of '{k}' differs from clift_active_xyz in some bit")
+            d = dirs[k].cpu()
+            if not torch.equal(d[:, :3].contiguous().view(torch.int32), want_d):
+                broken.append(f"{c.name}: dirs[:, :3] of '{k}' are not the ray directions")
+            if not bool((d[:, 3] == 0).all()):
+                broken.append(f"{c.name}: dirs[:, 3] of '{k}' is not 0")
+    assert not broken, "not bit for bit:\n" + "\n".join(broken)
+
+
 def test_density_points(capsys):
     L, t = _L(), Table()
     for c in mc.points_cases():
