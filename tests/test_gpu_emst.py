@@ -63,6 +63,12 @@ SETS = {
     "d8": lambda: (hc.blobs(35, 300, 8), None),
     "d32": lambda: (hc.blobs(36, 300, 32), None),
     "d5_ldx": lambda: (hc.blobs(37, 261, 5), 8),
+    "d1": lambda: (hc.blobs(38, 300, 1), None),                 # d = 1, 2, 4: launch_nearest<4, false, 2>
+    "d2_ldx": lambda: (hc.blobs(39, 261, 2), 5),
+    "d4": lambda: (hc.blobs(40, 300, 4), None),
+    "d9": lambda: (hc.blobs(41, 300, 9), None),                 # d = 9 - 16: launch_nearest<16, false, 1>
+    "d16_ldx": lambda: (hc.blobs(42, 257, 16), 19),
+    "d17": lambda: (hc.blobs(43, 300, 17), None),
     "same_point": lambda: (np.tile(np.float32([[0.25, 0.5, 0.75]]), (64, 1)), None),
     "duplicates": lambda: (duplicated(), None),
     "lattice": lambda: (lattice(), None),

@@ -4,34 +4,7 @@ arithmetic (fp64 neighbour test and sum, fp32 mean, fp32 step norm)."""
 import numpy as np
 import pytest
 
-
-def numpy_shift(X, seeds, bandwidth, max_iter):
-    """What clift_meanshift computes, one seed at a time."""
-    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
-    bw2, stop = bandwidth * bandwidth, 1e-3 * bandwidth
-    S, d = np.asarray(seeds).shape
-    centers, counts, iters = np.zeros((S, d), np.float32), np.zeros(S, np.int64), np.zeros(S, np.int64)
-    for s, seed in enumerate(np.asarray(seeds, dtype=np.float32)):
-        m, it = seed.copy(), 0
-        while True:
-            nb = ((X64 - m.astype(np.float64)) ** 2).sum(1) <= bw2
-            c = int(nb.sum())
-            if c == 0:
-                break
-            nm = (X64[nb].sum(0) / c).astype(np.float32)
-            step = float(np.linalg.norm(nm - m))
-            m = nm
-            if step <= stop or it == max_iter:
-                break
-            it += 1
-        centers[s], counts[s], iters[s] = m, c, it
-    return centers, counts, iters
-
-
-def blobs(seed, n_per, d, spread=0.05, k=4):
-    rng = np.random.default_rng(seed)
-    cent = rng.uniform(0.1, 0.9, (k, d))
-    return np.concatenate([c + spread * rng.standard_normal((n_per, d)) for c in cent]).astype(np.float32)
+from meanshift_cases import blobs, numpy_shift
 
 
 def test_bin_seeds_match_sklearn():
