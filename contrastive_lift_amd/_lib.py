@@ -41,6 +41,10 @@ class EditRec(C.Structure):
                 ("dir_inv", C.c_float * 9)]
 
 
+class EditShapeRec(C.Structure):
+    _fields_ = [("words", C.c_void_p), ("dims", C.c_int * 3), ("inv_cell", C.c_float * 3)]
+
+
 class TVSet(C.Structure):
     _fields_ = [("n", C.c_int), ("plane", C.c_void_p * 8), ("grad", C.c_void_p * 8), ("H", C.c_int * 8), ("W", C.c_int * 8),
                 ("C", C.c_int * 8), ("weight", C.c_float * 8)]
@@ -162,6 +166,11 @@ _SIGNATURES = {
     "clift_ray_layers": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P], C.c_int),
     "clift_edit_list_density_grad_points": ([_P, _I, _P, _P, _I, _L, _P, _P, _F, _P, _P, _P], C.c_int),
     "clift_edit_list_density_grad_active": ([_P, _P, _I, _P, _P, _P, _I, _P, _P], C.c_int),
+    "clift_edit_shaped_density_fwd": ([_P, _P, _P, _I, _P, _P, _I, _P, _P], C.c_int),
+    "clift_edit_shaped_active": ([_P, _P, _P, _I, _P, _P, _I, _P, _P, _P], C.c_int),
+    "clift_edit_shaped_points": ([_P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _P, _P], C.c_int),
+    "clift_edit_shaped_dense_sigma": ([_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P], C.c_int),
+    "clift_shape_pack": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
     "clift_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P], C.c_int),
     "clift_ema": ([_P, _P, _L, _F, _P], C.c_int),
 }

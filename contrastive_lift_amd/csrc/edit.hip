@@ -11,12 +11,15 @@
 // There is ONE kernel family, the program's: a single edit (clift_edit_density_fwd, clift_edit_active) is a program of one inside the library.
 // The same walk also runs off the rays (clift_edit_list_points, clift_edit_list_dense_sigma) and, with the chain of the remaps carried beside
 // the point, gives the gradient of the EDITED density for the surface outputs of an edited scene (clift_edit_list_density_grad_*, at the end).
+// An edit may also carry a SHAPE, a bit lattice over its source box (clift_edit_shaped_*, clift_shape_pack): the four walk
+// kernels live in edit_kernels_dev.h and are compiled twice, for the plain program (k_edit_list_*) and for the shaped one (k_edit_shaped_*).
 #include "clift_dev.h"
 #include "density_sweep_dev.h"
 #include "lattice_dev.h"
 #include "surface_dev.h"
 #include <math.h>
 #include <stddef.h>
+#include <type_traits>
 CLIFT_ROWS_LIMIT_BINDER(edit)
 
 struct BoxP {
@@ -83,6 +86,46 @@ static EditL edit_list_of_one(const clift_edit_t* e) {
     return L;
 }
 
+// ---- shaped edits: an edit may carry a bit lattice over its SOURCE box (clift_edit_shape_t); a point is part of the edit only
+// where its cell's bit is set.  The shaped program is the plain one plus CLIFT_EDIT_MAX shape records, the same by-value kernel argument:
+// pointer, dims and cell scale are wave-uniform and arrive by scalar loads; only the word read is a per-lane load.  The kernels of the plain
+// program take EditL and never see this: their code is what it was.
+struct ShapeP {
+    const unsigned int* w;     // NULL: this edit has no shape (the box rule)
+    int G[3];
+    float inv[3];
+};
+struct EditLS {
+    EditL L;
+    ShapeP sh[CLIFT_EDIT_MAX];
+};
+static_assert(sizeof(EditLS) + sizeof(MarchP) + sizeof(VmP) + 64 < 4096, "the shaped edit program travels as one kernel argument");
+// h_shapes == NULL is the plain program (*shaped = false, out->sh untouched); else n records, each checked before anything is launched
+static int edit_shapes_check(const clift_edit_t* e, const clift_edit_shape_t* h, int n, const char* who, EditLS* out, bool* shaped) {
+    if (edit_list_check(e, n, who, &out->L)) return 1;
+    *shaped = h != nullptr;
+    if (h == nullptr) return 0;
+    for (int i = 0; i < n; ++i) {
+        if (h[i].words == nullptr) continue;
+        for (int a = 0; a < 3; ++a)
+            CLIFT_REQUIRE(h[i].dims[a] >= 1 && h[i].dims[a] <= CLIFT_SHAPE_DIM_MAX, "%s: edit %d: shape dimension %d is %d, must be in 1 .. %d", who, i, a,
+                          h[i].dims[a], CLIFT_SHAPE_DIM_MAX);
+        CLIFT_REQUIRE((long)h[i].dims[0] * h[i].dims[1] * h[i].dims[2] < (1L << 31), "%s: edit %d: the shape has %ld cells, must be < 2^31", who, i,
+                      (long)h[i].dims[0] * h[i].dims[1] * h[i].dims[2]);
+        for (int a = 0; a < 3; ++a)
+            CLIFT_REQUIRE(isfinite(h[i].inv_cell[a]) && h[i].inv_cell[a] > 0.f, "%s: edit %d: shape inv_cell[%d] must be finite and positive", who, i, a);
+    }
+    for (int i = 0; i < CLIFT_EDIT_MAX; ++i) {
+        const clift_edit_shape_t& r = h[i < n ? i : 0];                         // (the slots past n are never read)
+        ShapeP& d = out->sh[i];
+        d.w = r.words;
+        for (int a = 0; a < 3; ++a) { d.G[a] = r.words ? r.dims[a] : 1; d.inv[a] = r.words ? r.inv_cell[a] : 1.f; }
+    }
+    return 0;
+}
+__device__ __forceinline__ const EditL& edits_of(const EditL& L) { return L; }
+__device__ __forceinline__ const EditL& edits_of(const EditLS& L) { return L.L; }
+
 // row-vector product of a row-major 3x3 with v, every multiply / add rounded separately, left to right
 __device__ __forceinline__ float row3(const float* a, const float v[3]) {
     return __fadd_rn(__fadd_rn(__fmul_rn(a[0], v[0]), __fmul_rn(a[1], v[1])), __fmul_rn(a[2], v[2]));
@@ -99,6 +142,21 @@ __device__ __forceinline__ bool in_box(const BoxP& b, const float p[3]) {
     return in;
 }
 
+// The bit of world point x in the lattice over box b (the edit's SOURCE box): cell index per axis from (A (x - c) - lo) * inv, every op rounded
+// on its own, floored and CLAMPED to 0 .. G - 1 (in float first: a NaN or an overflow ends at a border cell, never outside the words), then
+// bit lin & 31 of word lin >> 5, lin = (i0 G1 + i1) G2 + i2 < 2^31.  An ordinary per-lane global load.
+__device__ __forceinline__ bool shape_bit(const ShapeP& s, const BoxP& b, const float x[3]) {
+    const float d[3] = {__fsub_rn(x[0], b.c[0]), __fsub_rn(x[1], b.c[1]), __fsub_rn(x[2], b.c[2])};
+    int idx[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float u = __fmul_rn(__fsub_rn(row3(b.A + 3 * a, d), b.lo[a]), s.inv[a]);
+        idx[a] = (int)fminf(fmaxf(floorf(u), 0.f), (float)(s.G[a] - 1));
+    }
+    const unsigned int lin = ((unsigned int)idx[0] * (unsigned int)s.G[1] + (unsigned int)idx[1]) * (unsigned int)s.G[2] + (unsigned int)idx[2];
+    return (s.w[lin >> 5] >> (lin & 31u)) & 1u;
+}
+
 // One sample under an edit program, walked BACKWARDS from e_n to e_1: box classification in fp32 and the affine remap on the CURRENT point,
 // every multiply and add rounded separately; a killed sample stops (sigma = 0, nothing is looked up); a sample inside edit i's destination
 // box continues at M_i p + t_i with the view direction Dinv_i d.  World point and in-aabb flag come once, from the UNEDITED sample, with
@@ -112,15 +170,30 @@ struct EditH {
 __device__ __forceinline__ unsigned char edit_state(const EditH& h) { return (unsigned char)(h.hops | (h.kill ? CLIFT_EDIT_STATE_KILLED : 0)); }
 // ``hop(e, i)`` is called for every edit that remaps the point (i its 0-based position in the program), before p is replaced: what else
 // travels with the point (the view direction, the Jacobian of the chain, the origin of a copy) is turned there.
-template <class Hop>
-__device__ __forceinline__ EditH edit_walk_core(const EditL& L, float p[3], Hop hop) {
+// SHAPED (the program is an EditLS): an edit whose shape has words narrows both tests by its lattice -- src also needs the bit of p, mov
+// the bit of the remapped point M p + t, both read in the SOURCE frame, and only by lanes already inside the box.  Whether edit i has words
+// is wave-uniform.  The remapped point is formed with the ops of the hop below, so the hop's q is the one that was tested.
+template <class Prog, class Hop>
+__device__ __forceinline__ EditH edit_walk_core(const Prog& P, float p[3], Hop hop) {
+    constexpr bool SHAPED = std::is_same<Prog, EditLS>::value;
+    const EditL& L = edits_of(P);
     EditH h;
     h.kill = false;
     h.hops = 0;
     for (int i = L.n - 1; i >= 0; --i) {
         const EditP& e = L.e[i];
-        const bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
-        const bool mov = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
+        bool src = e.mode != CLIFT_EDIT_DUPLICATE && in_box(e.src, p);
+        bool mov = e.mode >= CLIFT_EDIT_DUPLICATE && in_box(e.dst, p);
+        if constexpr (SHAPED) {
+            const ShapeP& sh = P.sh[i];
+            if (sh.w != nullptr) {                          // wave-uniform
+                if (src) src = shape_bit(sh, e.src, p);
+                if (mov) {
+                    const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
+                    mov = shape_bit(sh, e.src, q);
+                }
+            }
+        }
         const bool kill = e.mode == CLIFT_EDIT_DELETE ? src : e.mode == CLIFT_EDIT_EXTRACT ? !src : e.mode == CLIFT_EDIT_MANIPULATE ? (src && !mov) : false;
         if (!h.kill && mov) {                               // (a killed sample has stopped: later tests see its last point, and change nothing)
             const float q[3] = {__fadd_rn(row3(e.M, p), e.t[0]), __fadd_rn(row3(e.M + 3, p), e.t[1]), __fadd_rn(row3(e.M + 6, p), e.t[2])};
@@ -133,7 +206,8 @@ __device__ __forceinline__ EditH edit_walk_core(const EditL& L, float p[3], Hop 
     }
     return h;
 }
-__device__ __forceinline__ EditH edit_walk_point(const EditL& L, float p[3], float d[3]) {
+template <class Prog>
+__device__ __forceinline__ EditH edit_walk_point(const Prog& L, float p[3], float d[3]) {
     return edit_walk_core(L, p, [&](const EditP& e, int) {
         const float v[3] = {row3(e.Dinv, d), row3(e.Dinv + 3, d), row3(e.Dinv + 6, d)};
 #pragma unroll
@@ -167,7 +241,8 @@ struct EditW {
     bool in;      // inside the aabb (before any remap)
     bool kill;    // sigma = 0: some edit's kill rule named the sample
 };
-__device__ __forceinline__ EditW edit_walk(const RayG& g, const MarchP& m, const EditL& L, float z, float xn[3], float d[3]) {
+template <class Prog>
+__device__ __forceinline__ EditW edit_walk(const RayG& g, const MarchP& m, const Prog& L, float z, float xn[3], float d[3]) {
     EditW s;
     float p[3];
     s.in = true;
@@ -182,22 +257,32 @@ __device__ __forceinline__ EditW edit_walk(const RayG& g, const MarchP& m, const
     return s;
 }
 
-// ============================================================================ density forward under an edit
-// The march's own wave-per-sweep body (density_sweep, density_sweep_dev.h) with another look-up rule: no jitter, and lane = sample walks the
-// program before the tap records are built from the EDITED position.  Same taps, same FMA order, same quad sum as clift_density_fwd, so a
-// sample the edit neither remaps nor kills gets the very bits of the unedited pass.  A remapped point may leave the aabb: make_tap clamps
-// every index and zeroes the weight of a tap outside the table (grid_sample's zero padding), as k_density_points relies on.  A killed sample
-// reads no table at all.  With a remap the samples that are looked up are no prefix of the ray any more: the only early exit left is a
-// sweep none of whose samples is looked up.
-__global__ __launch_bounds__(64 * SWEEP_WAVES) void k_edit_list_density_fwd(MarchP m, EditL L, VmP t, const float* __restrict__ rays, int N,
-                                                                            float* __restrict__ sigma) {
-    density_sweep(m, t, rays, nullptr, N, sigma, [&](const RayG& g, float z, float xn[3]) {
-        float d[3];
-        const EditW s = edit_walk(g, m, L, z, xn, d);
-        return s.in && !s.kill;
-    });
+// Row s of the active list: its ray, and the UNEDITED world point of its sample (no jitter) with sample_xn's separately rounded ops.
+__device__ __forceinline__ RayG edit_active_point(const MarchP& m, const float* __restrict__ rays, const int* __restrict__ act, long s, float p[3]) {
+    const int sid = act[s];
+    const int r = sid / m.S, k = sid - r * m.S;
+    const RayG g = load_ray(rays, r, m);
+    const float z = sample_z(g, m, k, 0.f);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
+    return g;
 }
 
+// ============================================================================ the walk kernels, per program type
+// edit_kernels_dev.h holds k_edit_*_density_fwd, _active, _points and _dense_sigma, written once: compiled here for the plain program
+// (k_edit_list_*: the instruction stream these kernels had before shapes existed) and for the shaped one (k_edit_shaped_*).
+#define EDIT_PROG EditL
+#define EDIT_K(x) k_edit_list_##x
+#include "edit_kernels_dev.h"
+#undef EDIT_PROG
+#undef EDIT_K
+#define EDIT_PROG EditLS
+#define EDIT_K(x) k_edit_shaped_##x
+#include "edit_kernels_dev.h"
+#undef EDIT_PROG
+#undef EDIT_K
+
+// ============================================================================ density forward under an edit (the kernel: edit_kernels_dev.h)
 extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit, const clift_vm_t* h_dens, const float* rays, int N,
                                       float* sigma, clift_stream_t s) {
     if (edit_check(h_edit, "clift_edit_density_fwd")) return 1;
@@ -221,34 +306,23 @@ extern "C" int clift_edit_list_density_fwd(const clift_march_t* h_m, const clift
     return clift_check_launch("clift_edit_list_density_fwd");
 }
 
+extern "C" int clift_edit_shaped_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                                             const clift_vm_t* h_dens, const float* rays, int N, float* sigma, clift_stream_t s) {
+    EditLS L;
+    bool shaped;
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_density_fwd", &L, &shaped)) return 1;
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_shaped_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_shaped_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
+    if (N <= 0) return 0;
+    const dim3 grid(cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES)), block(64 * SWEEP_WAVES);
+    if (shaped)
+        k_edit_shaped_density_fwd<<<grid, block, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens), rays, N, sigma);
+    else
+        k_edit_list_density_fwd<<<grid, block, 0, as_stream(s)>>>(to_dev(h_m), L.L, to_dev(h_dens), rays, N, sigma);
+    return clift_check_launch("clift_edit_shaped_density_fwd");
+}
+
 // ============================================================================ positions and view directions of the active samples
-// The same classification, recomputed (not stored: (N, S) flags would cost more traffic than the few dozen ops).  xa feeds the xyz heads and
-// clift_vm_products_points, dirs feeds clift_app_encode_points.
-// Row s of the active list: its ray, and the UNEDITED world point of its sample (no jitter) with sample_xn's separately rounded ops.
-__device__ __forceinline__ RayG edit_active_point(const MarchP& m, const float* __restrict__ rays, const int* __restrict__ act, long s, float p[3]) {
-    const int sid = act[s];
-    const int r = sid / m.S, k = sid - r * m.S;
-    const RayG g = load_ray(rays, r, m);
-    const float z = sample_z(g, m, k, 0.f);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = __fadd_rn(g.o[i], __fmul_rn(g.d[i], z));
-    return g;
-}
-
-// The walk recomputed, the view direction turned by every edit that remapped the sample
-__global__ __launch_bounds__(256) void k_edit_list_active(MarchP m, EditL L, const float* __restrict__ rays, const int* __restrict__ act, int M,
-                                                           float* __restrict__ xa, float* __restrict__ dirs) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= limit_rows(M)) return;
-    float p[3], xn[3];
-    const RayG g = edit_active_point(m, rays, act, s, p);
-    float d[3] = {g.d[0], g.d[1], g.d[2]};
-    edit_walk_point(L, p, d);
-    edit_normalise(p, m.lo, m.inv2, xn);
-    *reinterpret_cast<float4*>(xa + (size_t)s * 4) = make_float4(xn[0], xn[1], xn[2], 0.f);
-    *reinterpret_cast<float4*>(dirs + (size_t)s * 4) = make_float4(d[0], d[1], d[2], 0.f);
-}
-
 extern "C" int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h_edit, const float* rays, const int* act_idx, int M, float* xa,
                                  float* dirs, clift_stream_t s) {
     if (edit_check(h_edit, "clift_edit_active")) return 1;
@@ -268,6 +342,21 @@ extern "C" int clift_edit_list_active(const clift_march_t* h_m, const clift_edit
     if (M <= 0) return 0;
     k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
     return clift_check_launch("clift_edit_list_active");
+}
+
+extern "C" int clift_edit_shaped_active(const clift_march_t* h_m, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                                        const float* rays, const int* act_idx, int M, float* xa, float* dirs, clift_stream_t s) {
+    EditLS L;
+    bool shaped;
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_active", &L, &shaped)) return 1;
+    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_shaped_active: n_samples must be positive (got %d)", h_m->n_samples);
+    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_shaped_active: xa and dirs are both written");
+    if (M <= 0) return 0;
+    if (shaped)
+        k_edit_shaped_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
+    else
+        k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L.L, rays, act_idx, M, xa, dirs);
+    return clift_check_launch("clift_edit_shaped_active");
 }
 
 // k_edit_list_active with the ORIGIN of the content beside the position: the 1-based position of the first edit the backward
@@ -303,29 +392,6 @@ extern "C" int clift_edit_list_active_origin(const clift_march_t* h_m, const cli
 }
 
 // ============================================================================ the walk over arbitrary points
-// One thread per row: world point (and view direction) in, the point (and direction) at which the field is to be looked up out, plus the
-// state byte.  No aabb test and no table: what "inside the scene" means is the caller's business (mesh.label_vertices, the lattice below).
-// A row no edit remaps is copied through untouched, so it keeps its input bits.  in == out is allowed (a thread reads its row, then writes it).
-__global__ __launch_bounds__(256) void k_edit_list_points(EditL L, const float* pts, int ldp, const float* dirs, int ldd, long n, float* out_pts,
-                                                           float* out_dirs, unsigned char* state) {
-    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const float* pi = pts + (size_t)r * ldp;
-    float p[3] = {pi[0], pi[1], pi[2]}, d[3] = {0.f, 0.f, 0.f};
-    if (dirs != nullptr) {
-        const float* di = dirs + (size_t)r * ldd;
-        d[0] = di[0]; d[1] = di[1]; d[2] = di[2];
-    }
-    const EditH h = edit_walk_point(L, p, d);
-    float* po = out_pts + (size_t)r * ldp;
-    po[0] = p[0]; po[1] = p[1]; po[2] = p[2];
-    if (dirs != nullptr) {
-        float* dout = out_dirs + (size_t)r * ldd;
-        dout[0] = d[0]; dout[1] = d[1]; dout[2] = d[2];
-    }
-    if (state != nullptr) state[r] = edit_state(h);
-}
-
 extern "C" int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, const float* pts, int ldp, const float* dirs, int ldd, long n,
                                       float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
     EditL L;
@@ -339,57 +405,24 @@ extern "C" int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, 
     return clift_check_launch("clift_edit_list_points");
 }
 
-// ============================================================================ sigma on the lattice of the edited scene
-// clift_dense_sigma (isosurface.hip) with the program in it, one launch.  k_dense_sigma gives 4 lanes to a lattice point for the 18 table
-// reads; the walk is a few hundred VALU ops per point at 8 edits and would be done four times over if every lane of the quad walked.  So
-// the two phases use two mappings of one wave's 64 points: for the walk lane = point (lattice_point, then edit_walk_point, each done ONCE
-// per point), and for the taps four passes of 16 points x 4 lanes, as in density_sweep, the quad fetching its point's normalised
-// position from the lane that walked it by __shfl -- registers only, no LDS.  The records arrive by scalar loads (L is a kernel
-// argument, the trip count is wave-uniform).  A killed point reads no table and gets exactly 0; a pass none of whose 16 points is alive
-// is skipped, and a wave all of whose points are killed leaves after the walk.  A point no edit remaps keeps the xn of lattice_point
-// and goes through vm_density_lane / vm_sigma in k_dense_sigma's lane roles: the bits of clift_dense_sigma.  A remapped point is
-// normalised with edit_walk's separately rounded ops; outside the box it reads zero padding (make_tap).  No atomics.
-__global__ __launch_bounds__(256) void k_edit_list_dense_sigma(VmP t, EditL L, float3 lo, float3 hi, float3 inv_ext2, const float* __restrict__ s0,
-                                                                const float* __restrict__ s1, const float* __restrict__ s2, int n0, int n1, int n2,
-                                                                float shift, float* __restrict__ out, unsigned char* __restrict__ state) {
-    const int lane = threadIdx.x & 63;
-    const long total = (long)n0 * n1 * n2;
-    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long base = v - lane;                                      // the wave's first point (< total: the grid is cdiv(total, 256) and 256 = 4 waves)
-    if (base >= total) return;                                       // wave-uniform
-    const bool valid = v < total;
-    const long vc = valid ? v : total - 1;                           // (the tail lanes walk the last point again: no divergence around the loop)
-    const int i2 = (int)(vc % n2), i1 = (int)((vc / n2) % n1), i0 = (int)(vc / ((long)n1 * n2));
-    float p[3], xn[3], d[3] = {0.f, 0.f, 0.f};
-    lattice_point(lo, hi, inv_ext2, s0[i0], s1[i1], s2[i2], p, xn);
-    const EditH h = edit_walk_point(L, p, d);
-    if (h.hops > 0) {
-        const float l3[3] = {lo.x, lo.y, lo.z}, inv3[3] = {inv_ext2.x, inv_ext2.y, inv_ext2.z};
-        edit_normalise(p, l3, inv3, xn);
-    }
-    if (valid && state != nullptr) state[v] = edit_state(h);
-    const unsigned long long on = __ballot(valid && !h.kill);
-    if (on == 0) {                                                   // wave-uniform: nothing of this wave is looked up
-        if (valid) out[v] = 0.f;
-        return;
-    }
-    const int q = lane & 3;
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int sl = pass * 16 + (lane >> 2);
-        float sig = 0.f;
-        if ((on >> (pass * 16)) & 0xffffull) {                       // wave-uniform: some point of this pass is looked up
-            const float xq[3] = {__shfl(xn[0], sl), __shfl(xn[1], sl), __shfl(xn[2], sl)};
-            const bool mine = (on >> sl) & 1ull;
-            float acc = mine ? vm_density_lane(t, xq, q) : 0.f;
-            acc += __shfl_xor(acc, 1);
-            acc += __shfl_xor(acc, 2);
-            if (mine) sig = vm_sigma(acc, shift);
-        }
-        if (q == 0 && base + sl < total) out[base + sl] = sig;
-    }
+extern "C" int clift_edit_shaped_points(const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits, const float* pts, int ldp,
+                                        const float* dirs, int ldd, long n, float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
+    EditLS L;
+    bool shaped;
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_points", &L, &shaped)) return 1;
+    CLIFT_REQUIRE(ldp >= 3 && (dirs == nullptr || ldd >= 3), "clift_edit_shaped_points: ldp and ldd must be >= 3 (got %d, %d)", ldp, ldd);
+    CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "clift_edit_shaped_points: %ld rows, must be in [0, 2^36)", n);
+    if (n == 0) return 0;
+    CLIFT_REQUIRE(pts != nullptr && out_pts != nullptr, "clift_edit_shaped_points: NULL pts or out_pts");
+    CLIFT_REQUIRE((dirs == nullptr) == (out_dirs == nullptr), "clift_edit_shaped_points: dirs and out_dirs come together (both or neither NULL)");
+    if (shaped)
+        k_edit_shaped_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
+    else
+        k_edit_list_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(L.L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
+    return clift_check_launch("clift_edit_shaped_points");
 }
 
+// ============================================================================ sigma on the lattice of the edited scene
 extern "C" int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, int n_edits, const float* h_lo3, const float* h_hi3,
                                            const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2,
                                            float shift, float* out, unsigned char* state, clift_stream_t s) {
@@ -406,6 +439,65 @@ extern "C" int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift
                                                                         make_float3(h_inv_ext2[0], h_inv_ext2[1], h_inv_ext2[2]), s0, s1, s2, n0, n1,
                                                                         n2, shift, out, state);
     return clift_check_launch("clift_edit_list_dense_sigma");
+}
+
+extern "C" int clift_edit_shaped_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                                             const float* h_lo3, const float* h_hi3, const float* h_inv_ext2, const float* s0, const float* s1,
+                                             const float* s2, int n0, int n1, int n2, float shift, float* out, unsigned char* state,
+                                             clift_stream_t s) {
+    EditLS L;
+    bool shaped;
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_dense_sigma", &L, &shaped)) return 1;
+    CLIFT_REQUIRE(h_dens && h_lo3 && h_hi3 && h_inv_ext2, "clift_edit_shaped_dense_sigma: NULL host record");
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_shaped_dense_sigma: comps must be a multiple of 4 (got %d)", h_dens->comps);
+    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_edit_shaped_dense_sigma: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
+    const long total = (long)n0 * n1 * n2;
+    CLIFT_REQUIRE(total < (1L << 36), "clift_edit_shaped_dense_sigma: %ld lattice points, must be < 2^36", total);
+    CLIFT_REQUIRE(s0 && s1 && s2 && out, "clift_edit_shaped_dense_sigma: NULL device buffer");
+    const float3 lo = make_float3(h_lo3[0], h_lo3[1], h_lo3[2]), hi = make_float3(h_hi3[0], h_hi3[1], h_hi3[2]),
+                 inv = make_float3(h_inv_ext2[0], h_inv_ext2[1], h_inv_ext2[2]);
+    if (shaped)
+        k_edit_shaped_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, lo, hi, inv, s0, s1, s2, n0, n1, n2, shift, out, state);
+    else
+        k_edit_list_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L.L, lo, hi, inv, s0, s1, s2, n0, n1, n2, shift, out, state);
+    return clift_check_launch("clift_edit_shaped_dense_sigma");
+}
+
+// ============================================================================ packing a shape
+// flags (g0, g1, g2) bytes, x-major -> the bit lattice: bit lin of the words is 1 iff some flag within Chebyshev distance ``grow`` of cell
+// lin is non-zero, the neighbourhood clipped at the border.  One thread per OUTPUT WORD builds its 32 bits in a register and stores the word
+// once (bits past the last cell stay 0): no atomics, the same bits every run.
+__global__ __launch_bounds__(256) void k_shape_pack(const unsigned char* __restrict__ flags, int g0, int g1, int g2, int grow, long n_words,
+                                                    unsigned int* __restrict__ words) {
+    const long wi = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (wi >= n_words) return;
+    const long total = (long)g0 * g1 * g2;
+    unsigned int word = 0;
+    for (int b = 0; b < 32; ++b) {
+        const long lin = wi * 32 + b;
+        if (lin >= total) break;
+        const int i2 = (int)(lin % g2), i1 = (int)((lin / g2) % g1), i0 = (int)(lin / ((long)g1 * g2));
+        const int a0 = max(i0 - grow, 0), b0 = min(i0 + grow, g0 - 1), a1 = max(i1 - grow, 0), b1 = min(i1 + grow, g1 - 1);
+        const int a2 = max(i2 - grow, 0), b2 = min(i2 + grow, g2 - 1);
+        bool any = false;
+        for (int j0 = a0; j0 <= b0 && !any; ++j0)
+            for (int j1 = a1; j1 <= b1 && !any; ++j1) {
+                const unsigned char* row = flags + ((long)j0 * g1 + j1) * g2;
+                for (int j2 = a2; j2 <= b2; ++j2) any = any || row[j2] != 0;
+            }
+        word |= (any ? 1u : 0u) << b;
+    }
+    words[wi] = word;
+}
+
+extern "C" int clift_shape_pack(const unsigned char* flags, int g0, int g1, int g2, int grow, unsigned int* words, clift_stream_t s) {
+    CLIFT_REQUIRE(g0 >= 1 && g0 <= CLIFT_SHAPE_DIM_MAX && g1 >= 1 && g1 <= CLIFT_SHAPE_DIM_MAX && g2 >= 1 && g2 <= CLIFT_SHAPE_DIM_MAX,
+                  "clift_shape_pack: dimensions must be in 1 .. %d (got %d x %d x %d)", CLIFT_SHAPE_DIM_MAX, g0, g1, g2);
+    CLIFT_REQUIRE(grow >= 0 && grow <= CLIFT_SHAPE_GROW_MAX, "clift_shape_pack: grow must be in 0 .. %d (got %d)", CLIFT_SHAPE_GROW_MAX, grow);
+    CLIFT_REQUIRE(flags != nullptr && words != nullptr, "clift_shape_pack: NULL flags or words");
+    const long n_words = ((long)g0 * g1 * g2 + 31) / 32;
+    k_shape_pack<<<cdiv(n_words, 256), 256, 0, as_stream(s)>>>(flags, g0, g1, g2, grow, n_words, words);
+    return clift_check_launch("clift_shape_pack");
 }
 
 // ============================================================================ gradient of the edited density

@@ -1104,13 +1104,24 @@ def render_forward(model, renderer, rays, jitter, white_bg, want_rgb=True, want_
 
 
 # ----------------------------------------------------------------------------- scene-editing forward
+def _refuse_shaped(who, prog):
+    """The passes that read ``prog.records()`` alone would silently drop the shapes of a shaped program (edit.EditShape)."""
+    if prog.is_shaped:
+        raise NotImplementedError(f"{who}: a shaped edit program (an edit with an EditShape) is not supported here: this pass walks the boxes "
+                                  "alone and would drop the shapes; render it with edit_forward, mesh it through get_dense_sigma(edit=)")
+
+
 def _edit_density_march(model, renderer, rays, edit, weight_thres):
     """The march of an edit pass: a single ``Edit`` through clift_edit_density_fwd, anything else (``as_program``) through
-    clift_edit_list_density_fwd.  Returns (context, the kernel-name pattern and the leading edit arguments of that family); the context
+    clift_edit_list_density_fwd; a program one of whose edits follows a shape (``edit.EditShape``; a single shaped ``Edit`` included)
+    through clift_edit_shaped_density_fwd, with the shape records right behind the edits.  Returns (context, the kernel-name pattern and the leading edit arguments of that family); the context
     keeps the resolved program (``edit_program``; a single edit as a program of one, whose list walk is that edit op for op)."""
     N, st = rays.shape[0], stream()
     prog = _edit.as_program(edit)
-    if isinstance(edit, _edit.Edit):
+    if prog.is_shaped:          # some edit follows a shape (edit.EditShape): the shaped list family, a single Edit as a program of one
+        rec = prog.records()
+        edit_kernel, edit_args = "clift_edit_shaped_%s", (rec, prog.shapes(rays.device), len(prog))
+    elif isinstance(edit, _edit.Edit):
         rec = edit.record()
         edit_kernel, edit_args = "clift_edit_%s", (C.byref(rec),)
     else:
@@ -1568,6 +1579,29 @@ def _sample_slots(ctx, renderer, table, E, use_delta):
 
 
 @torch.no_grad()
+def point_slots(model, renderer, points, table, use_delta=False, chunk=2 ** 20):
+    """The slot under ``table`` (a ``layers.SlotTable``) of arbitrary WORLD points (n, 3) on the device -> (n,) int32, -1 where the point's
+    class has no slot.  The semantic head and the fast instance net through the field's point-wise methods, as ``mesh.label_vertices``
+    evaluates them (xyz-MLP heads and heads on their own VM grid alike), then clift_sample_slots, ``chunk`` points at a time.  With
+    ``use_delta`` the feature is output + world position.  No aabb test: what is inside the scene is the caller's decision."""
+    E = _layers_check("point_slots", model, table, use_delta)
+    pts = _lib.f32(points, "points").reshape(-1, 3).contiguous()
+    n, dev = pts.shape[0], pts.device
+    Ccls = model.num_semantic_classes
+    cls_slots, cent = table.on(dev)
+    slots = torch.empty((n,), dtype=torch.int32, device=dev)
+    for a in range(0, n, int(chunk)):
+        b = min(n, a + int(chunk))
+        xyz = pts[a:b]
+        xn = renderer.normalize_coordinates(xyz).contiguous()
+        sem = model.render_semantic_mlp(None, model.compute_semantic_feature(xn)).float().contiguous()
+        feat = model.render_instance_mlp(None, model.compute_instance_feature(xn)).float().contiguous()
+        call("clift_sample_slots", ptr(sem), sem.shape[1], Ccls, ptr(feat), feat.shape[1], E, ptr(xyz) if use_delta else None, 3, ptr(cls_slots),
+             ptr(cent), table.K_base, table.mode, b - a, ptr(slots[a:b]), stream())
+    return slots
+
+
+@torch.no_grad()
 def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, use_delta=False, cap=None):
     """Per ray and per instance slot of ``table`` (a ``layers.SlotTable``) what that instance covers ALONE, also behind what hides it: the march,
     its samples listed again by alpha > ``alpha_thres`` (default: renderer.raymarch_weight_thres) -- a sample behind an occluder has w ~ 0 and is
@@ -1624,6 +1658,7 @@ def edit_layers_forward(model, renderer, rays, edit, table, alpha_thres=None, us
     if alpha_thres is not None and float(alpha_thres) < 0:
         raise ValueError(f"edit_layers_forward: alpha_thres must be >= 0 (got {alpha_thres}): a killed sample has alpha 0 and stays out of the list")
     prog = _edit.as_program(edit)
+    _refuse_shaped("edit_layers_forward", prog)             # (the origin walk, clift_edit_list_active_origin, reads the boxes alone)
     ext = table.for_program(prog)
     rays, _ = _check_rays(rays, None)
     views = model.named_views()
@@ -1658,6 +1693,7 @@ def edit_density_grad_points(model, renderer, xyz_world, edit, want_state=False)
     x = _points(xyz_world)
     reset_rows_limit(x.device)
     prog = _edit.as_program(edit)
+    _refuse_shaped("edit_density_grad_points", prog)
     ms = march_struct(renderer, model)
     views = model.named_views()
     vd = vm_struct(views, "density", grid_res(views))
@@ -1673,6 +1709,7 @@ def _edit_surface_launches(model, ctx, q):
     """The surface pass of an edited march: the gradient of the EDITED density at the active samples (one launch, the walk recomputed from
     the rays -- no xa is needed), then the unchanged per-ray launch."""
     q = _surface_quantile(q)
+    _refuse_shaped("edit_density_grad_active", ctx.edit_program)
     G = None
     if ctx.M > 0:
         views = model.named_views()
@@ -1693,6 +1730,7 @@ def edit_surface_from_ctx(model, renderer, ctx, q=0.5):
         raise _lib.CliftError("edit_surface_from_ctx: not a context of edit_forward (surface_from_ctx takes the context of an unedited pass)")
     if ctx.capped:
         raise _lib.CliftError("edit_surface_from_ctx: a sync-free (capped) context is not supported: its active-sample count stays on the device")
+    _refuse_shaped("edit_surface_from_ctx", ctx.edit_program)
     return _edit_surface_launches(model, ctx, q)
 
 
@@ -1702,6 +1740,7 @@ def edit_surface_forward(model, renderer, rays, edit, q=0.5, weight_thres=0.0):
     made, so a field whose semantic / instance head sits on its own VM grid is fine here.  ``weight_thres`` as in ``edit_forward``.
     Returns (the dict of ``edit_surface_from_ctx`` plus depth = the expected distance and opacity, context)."""
     rays, _ = _check_rays(rays, None)
+    _refuse_shaped("edit_surface_forward", _edit.as_program(edit))
     ctx, _, _ = _edit_density_march(model, renderer, rays, edit, weight_thres)
     out = _edit_surface_launches(model, ctx, q)
     out["depth"], out["opacity"] = ctx.ray_out[:, 1], ctx.ray_out[:, 0]

@@ -204,6 +204,50 @@ int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_
  * program's, n_samples < 1, a NULL xa or origin. */
 int clift_edit_list_active_origin(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
                                   float* xa, unsigned char* origin, unsigned char* state, clift_stream_t s);
+/* Shaped edits (further ABI 27 additions): an edit that follows an instance's shape, not its box.  A SHAPE is a bit lattice over
+ * the SOURCE box of an edit, in that box's local frame: dims = (G0, G1, G2), each in 1 .. CLIFT_SHAPE_DIM_MAX; cell i_a of axis a covers
+ * lo_a + i_a h_a .. lo_a + (i_a + 1) h_a with h_a = (hi_a - lo_a) / G_a; bits are x-major, lin = (i0 G1 + i1) G2 + i2 < 2^31, bit lin & 31 of
+ * word lin >> 5; the words are uint32 in DEVICE memory (they must stay alive until the launch has run) and the unused high bits of the last
+ * word are 0.  inv_cell[a] = fp32(G_a / (hi_a - lo_a)), formed in fp64 from the fp32 lo / hi of the record's src box.
+ *
+ * Membership of a world point x, in fp32 with every operation rounded on its own: q_a = row a of src.axes times (x - src.centre), as the box
+ * test forms it; u_a = (q_a - src.lo_a) * inv_cell_a; i_a = floor(u_a) clamped to 0 .. G_a - 1; bit(x) = the bit of cell (i0, i1, i2).
+ *
+ * The walk of a program (above) with shapes: for an edit whose words are not NULL
+ *     src = mode != DUPLICATE && p in src_i && bit(p)
+ *     mov = mode >= DUPLICATE && p in dst_i && bit(map_m_i p + map_t_i)
+ * -- the remapped point, which the walk forms anyway, is tested in the SOURCE frame; the index is clamped, so a remapped point that rounding
+ * puts just outside the source box reads its border cell -- and the kill rules read these (DELETE src; EXTRACT !src; MANIPULATE src && !mov).  A
+ * point in the destination box that is not part of the moved shape is not remapped: it keeps its own content and walks on.  An edit whose
+ * words are NULL keeps the box rule; the two kinds mix freely.  An all-ones shape gives the bits of the plain box edit; a rigid move keeps
+ * lo, hi and the local frame, so the moved object is addressed at its destination with the same words.
+ *
+ * clift_edit_shaped_*: the clift_edit_list_* entry point of the same name with h_shapes right behind h_edits: a HOST array of n_edits records
+ * (copied into the launch like the edits), or NULL for the list entry point's behaviour, bit for bit.  Errors, raised before anything is
+ * launched, the message naming the edit's index: the program's own; for a record with words, a dimension outside 1 .. CLIFT_SHAPE_DIM_MAX,
+ * a product of the dimensions >= 2^31, an inv_cell that is not finite and positive.
+ *
+ * clift_shape_pack: flags (g0 g1 g2) bytes on the device, x-major -> words (ceil(g0 g1 g2 / 32)) uint32 on the device: bit = 1 iff some flag
+ * within Chebyshev distance grow (0 .. CLIFT_SHAPE_GROW_MAX) of the cell is non-zero, the neighbourhood clipped at the lattice border (no
+ * wrap).  One thread per output word, no atomics, every word written once: two runs give the same bits.  Errors: a dimension < 1 or
+ * > CLIFT_SHAPE_DIM_MAX, grow out of range, a NULL buffer. */
+#define CLIFT_SHAPE_DIM_MAX 1024
+#define CLIFT_SHAPE_GROW_MAX 4
+typedef struct {
+    const unsigned int* words;   /* DEVICE memory; NULL: this edit has no shape (plain box edit) */
+    int dims[3];
+    float inv_cell[3];           /* fp32(G_a / (hi_a - lo_a)), formed in fp64 from the fp32 values of the record's src box */
+} clift_edit_shape_t;
+int clift_edit_shaped_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                                  const clift_vm_t* h_dens, const float* rays, int N, float* sigma, clift_stream_t s);
+int clift_edit_shaped_active(const clift_march_t* h_m, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                             const float* rays, const int* act_idx, int M, float* xa, float* dirs, clift_stream_t s);
+int clift_edit_shaped_points(const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits, const float* pts, int ldp,
+                             const float* dirs, int ldd, long n, float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s);
+int clift_edit_shaped_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                                  const float* h_lo3, const float* h_hi3, const float* h_inv_ext2, const float* s0, const float* s1,
+                                  const float* s2, int n0, int n1, int n2, float shift, float* out, unsigned char* state, clift_stream_t s);
+int clift_shape_pack(const unsigned char* flags, int g0, int g1, int g2, int grow, unsigned int* words, clift_stream_t s);
 
 /* ---- a7-a8: renderer.py:83-84,100-103,137,173-174,626-631 + eff_distloss (renderer.py:101).
  * Per sample alpha, T (transmittance before the sample), w = alpha*T, all (N, S).

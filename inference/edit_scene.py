@@ -5,6 +5,7 @@
                                    --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz] [--pad 0.0]
                                    [--render_trajectory] [--image_dim H W] [--weight_thres 0] [--save_surface [--surface_quantile 0.5]]
                                    [--save_layers --cached_centroids_path C [--layers_level 0.5]]
+                                   [--follow_shape --cached_centroids_path C [--shape_grid 32] [--shape_grow 1] [--shape_alpha 0.5]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
@@ -29,6 +30,15 @@ entries did: an entry that acts on an object after an earlier entry has moved it
 ``"at": "moved"`` -- its box is then the destination box of the most recent earlier ``move`` of that instance, so its motion composes
 with that move ("move it, then turn it where it now stands").  Without the flag a later entry addresses the place where the object
 stood at first.  Output goes to ``..._edit_script_<file stem>/``.
+
+``--follow_shape`` makes every edit follow the instance's SHAPE, not its box: the cells of a ``--shape_grid``^3 lattice over
+the box whose centre holds density (``--shape_alpha``, as ``--alpha_level`` of inference/extract_mesh.py) of the box's most frequent
+instance slot, grown by ``--shape_grow`` cells (``edit.EditShape.from_field``; the slot table is ``render_panopli.layers_table``'s, so
+``--cached_centroids_path`` is required unless the model is a linear-assignment one).  Deleting a cup then leaves the table under it,
+and a moved chair takes no floor along and covers nothing but itself at the destination.  One line per edit reports the chosen slot and
+the cells set, occupied and in all.  A script entry may say ``"shape": true|false`` (default: the flag); an ``"at": "moved"`` entry
+reuses the shape of the move it refers to and must not pad the box again.  Output names get ``_shape`` behind them.
+``--follow_shape`` cannot be combined with ``--save_surface`` or ``--save_layers``: those passes walk the boxes alone.
 """
 import argparse
 import functools
@@ -54,28 +64,81 @@ from contrastive_lift_amd.config import load_run_config               # noqa: E4
 OPS = ("delete", "extract", "copy", "move")
 
 
-def resolve_edit(boxes, instance, op, translate=(0.0, 0.0, 0.0), rotate_deg=(0.0, 0.0, 0.0), pad=0.0, box=None):
-    """One edit of the fitted box of ``instance`` -- or of ``box`` (an ``EditBox``) in its place, where the object no longer stands there."""
+def resolve_edit(boxes, instance, op, translate=(0.0, 0.0, 0.0), rotate_deg=(0.0, 0.0, 0.0), pad=0.0, box=None, shape=None):
+    """One edit of the fitted box of ``instance`` -- or of ``box`` (an ``EditBox``) in its place, where the object no longer stands there.
+    ``shape``: the ``edit.EditShape`` the edit follows (over that box), or a callable ``shape(box)`` that makes it (``field_shapes``)."""
     if instance not in boxes:
         raise SystemExit(f"instance {instance} has no box (boxes: {sorted(boxes)})")
     box = ed.EditBox.from_fitted(boxes[instance], pad=pad) if box is None else box.padded(pad)
+    if callable(shape):
+        shape = shape(box)
     if op == "delete":
-        return ed.delete(box)
+        return ed.delete(box, shape=shape)
     if op == "extract":
-        return ed.extract(box)
+        return ed.extract(box, shape=shape)
     R = ed.rotation_from_euler_deg(*rotate_deg)
-    return (ed.copy if op == "copy" else ed.move)(box, np.asarray(translate, dtype=np.float64), R)
+    return (ed.copy if op == "copy" else ed.move)(box, np.asarray(translate, dtype=np.float64), R, shape=shape)
 
 
-_ENTRY_KEYS = {"instance", "op", "translate", "rotate_deg", "pad", "at"}
+def field_shapes(model, renderer, table, grid=32, grow=1, alpha=0.5, use_delta=False):
+    """What ``--follow_shape`` hands to ``resolve_edit`` / ``resolve_program``: ``shape_of(box)`` reads the shape of the instance in ``box``
+    from the trained field (``EditShape.from_field``: the most frequent slot of ``table`` among the occupied cells) and prints one line per
+    edit.  ``alpha`` turns into the density threshold by ``extract_mesh.default_level``, so it means what ``--alpha_level`` means."""
+    import extract_mesh as xm
+    sigma_min, dims = xm.default_level(renderer, float(alpha)), (int(grid),) * 3
+
+    def shape_of(box):
+        try:
+            sh = ed.EditShape.from_field(model, renderer, box, table, dims=dims, grow=int(grow), sigma_min=sigma_min, use_delta=use_delta)
+        except ValueError as err:
+            raise SystemExit(f"--follow_shape: {err}")
+        print(f"shape: slot {sh.slot}, {sh.n_set} cells set, {sh.n_occupied} occupied, {sh.n_cells} in all (sigma >= {sigma_min:.6g}, grow {int(grow)})")
+        return sh
+    return shape_of
 
 
-def resolve_program(boxes, entries):
+def add_shape_arguments(ap):
+    """The flags of ``--follow_shape``, shared with inference/extract_mesh.py."""
+    ap.add_argument("--follow_shape", action="store_true",
+                    help="the edit follows the instance's shape, not its box: only the cells of the box that hold density of the box's main "
+                         "instance leave, arrive or stay (DESIGN.md 6k); needs the slot table of --cached_centroids_path (a linear_assignment "
+                         "model needs none)")
+    ap.add_argument("--shape_grid", type=int, default=32, metavar="G", help="--follow_shape: cells per axis of the shape lattice over the box")
+    ap.add_argument("--shape_grow", type=int, default=1, metavar="R", help="--follow_shape: grow the shape by this many cells (0 .. 4)")
+    ap.add_argument("--shape_alpha", type=float, default=0.5, metavar="A",
+                    help="--follow_shape: a cell is occupied where one training-step sample would have this opacity (what --alpha_level of "
+                         "inference/extract_mesh.py means)")
+
+
+def script_asks_for_shapes(path):
+    """Whether an entry of the ``--script`` file says ``"shape": true`` (None: no script)."""
+    if path is None:
+        return False
+    with open(path) as f:
+        entries = json.load(f)
+    return isinstance(entries, list) and any(isinstance(e, dict) and e.get("shape") is True for e in entries)
+
+
+def shape_table(config, scene, cached_centroids_path):
+    """The slot table ``--follow_shape`` reads (``render_panopli.layers_table``); without centroids and without a linear-assignment model a
+    ``SystemExit``."""
+    try:
+        return rp.layers_table(config, scene, cached_centroids_path)
+    except ValueError:
+        raise SystemExit("--follow_shape needs --cached_centroids_path (or a linear_assignment model): the shape follows one slot of the scene's table")
+
+
+_ENTRY_KEYS = {"instance", "op", "translate", "rotate_deg", "pad", "at", "shape"}
+
+
+def resolve_program(boxes, entries, follow_shape=False, shape_of=None):
     """The ``EditProgram`` of a ``--script`` list, in list order.  Every entry acts on ``boxes[instance]`` as fitted in the unedited scene;
-    with ``"at": "moved"`` on the destination box of the most recent earlier ``move`` of the same instance."""
+    with ``"at": "moved"`` on the destination box of the most recent earlier ``move`` of the same instance.  An entry follows a shape where
+    its ``"shape"`` says so (default: ``follow_shape``): ``shape_of(box)`` makes it (``field_shapes``); an ``"at": "moved"`` entry reuses
+    the shape object of the move it refers to -- a rigid move keeps the local frame --, so it must not pad the box again."""
     if not isinstance(entries, list) or not 1 <= len(entries) <= ed.MAX_EDITS:
         raise SystemExit(f"an edit script is a list of 1 to {ed.MAX_EDITS} entries")
-    edits, moved_to = [], {}
+    edits, moved_to, moved_shape = [], {}, {}
     for i, entry in enumerate(entries):
         if not isinstance(entry, dict) or not {"instance", "op"} <= set(entry) <= _ENTRY_KEYS:
             raise SystemExit(f"entry {i}: needs \"instance\" and \"op\", and may hold {sorted(_ENTRY_KEYS)} only (got {entry!r})")
@@ -87,12 +150,31 @@ def resolve_program(boxes, entries):
             raise SystemExit(f"entry {i}: \"at\" is \"fitted\" or \"moved\" (got {at!r})")
         if at == "moved" and instance not in moved_to:
             raise SystemExit(f"entry {i}: \"at\": \"moved\" needs an earlier move of instance {instance}")
+        shaped, pad, shape = entry.get("shape", bool(follow_shape)), float(entry.get("pad", 0.0)), None
+        if not isinstance(shaped, bool):
+            raise SystemExit(f"entry {i}: \"shape\" is true or false (got {shaped!r})")
+        if shaped and at == "moved":
+            if moved_shape.get(instance) is None:
+                raise SystemExit(f"entry {i}: \"shape\" with \"at\": \"moved\" reuses the shape of the move it refers to, and that move of instance "
+                                 f"{instance} follows none")
+            if pad != 0.0:
+                raise SystemExit(f"entry {i}: \"pad\": {pad} on a shaped \"at\": \"moved\" entry: the shape it reuses was made over the moved box as "
+                                 "it is; pad the move instead")
+            shape = moved_shape[instance]
+        elif shaped:
+            if shape_of is None:
+                raise SystemExit(f"entry {i}: a shaped entry needs the trained field to read the shape from (--follow_shape / \"shape\": true)")
+            shape = shape_of
         e = resolve_edit(boxes, instance, op, entry.get("translate", (0.0, 0.0, 0.0)), entry.get("rotate_deg", (0.0, 0.0, 0.0)),
-                         float(entry.get("pad", 0.0)), box=moved_to[instance] if at == "moved" else None)
+                         pad, box=moved_to[instance] if at == "moved" else None, shape=shape)
         if op == "move":
-            moved_to[instance] = e.dst
+            moved_to[instance], moved_shape[instance] = e.dst, e.shape
         edits.append(e)
     return ed.EditProgram(edits)
+
+
+SHAPE_WITH_SURFACE_OR_LAYERS = ("--follow_shape (or a script entry with \"shape\": true) cannot be combined with --save_surface or --save_layers: "
+                                "those passes walk the boxes alone and would drop the shapes (shaped surfaces and layers are not built yet)")
 
 
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
@@ -101,6 +183,10 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
     device, rank = rp.distributed_device(device)
     scene, model, renderer = rp.load_for_inference(config, device)
     H, W = scene.image_dim
+    if callable(edit):              # --follow_shape: the shapes are read from the field, so the edit is resolved once the field is loaded
+        edit = edit(scene, model, renderer)
+    if ed.as_program(edit).is_shaped and (save_surface or save_layers):
+        raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if save_layers:
         table = rp.layers_table(config, scene, cached_centroids_path)
         table_edit = table.for_program(edit)
@@ -184,7 +270,10 @@ def main(argv=None):
     ap.add_argument("--cached_centroids_path", type=str, default=None,
                     help="--save_layers: all_centroids.pkl of inference/extract_train_centroids.py (not needed for a linear_assignment model)")
     ap.add_argument("--layers_level", type=float, default=0.5, help="the opacity above which --save_layers counts a pixel into a mask")
+    add_shape_arguments(ap)
     args = ap.parse_args(argv)
+    if args.follow_shape and (args.save_surface or args.save_layers):
+        raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if args.script is not None and (args.instance is not None or args.op is not None):
         ap.error("--script holds the edits: give it without --instance / --op")
     if args.script is None and (args.instance is None or args.op is None):
@@ -195,11 +284,28 @@ def main(argv=None):
     cfg.image_dim = list(args.image_dim)
     with open(args.bboxes, "rb") as f:
         boxes = pickle.load(f)
+    entries = None
     if args.script is not None:
         with open(args.script) as f:
-            the_edit, tag = resolve_program(boxes, json.load(f)), f"script_{Path(args.script).stem}"
+            entries, tag = json.load(f), f"script_{Path(args.script).stem}"
     else:
-        the_edit, tag = resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad), f"{args.op}_{args.instance}"
+        tag = f"{args.op}_{args.instance}"
+    shaped = args.follow_shape or script_asks_for_shapes(args.script)
+    if shaped and (args.save_surface or args.save_layers):
+        raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
+
+    def the_edit(scene, model, renderer):
+        shape_of = None
+        if shaped:
+            table = shape_table(cfg, scene, args.cached_centroids_path)
+            shape_of = field_shapes(model, renderer, table, args.shape_grid, args.shape_grow, args.shape_alpha, bool(cfg.use_delta))
+        if entries is not None:
+            return resolve_program(boxes, entries, follow_shape=args.follow_shape, shape_of=shape_of)
+        return resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad, shape=shape_of)
+    if args.follow_shape:
+        tag += "_shape"
+    if not shaped:                  # (no field is needed: resolve now, so that a bad script stops before the checkpoint is loaded)
+        the_edit = the_edit(None, None, None)
     print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
                                 save_surface=args.save_surface, surface_quantile=args.surface_quantile, save_layers=args.save_layers,
                                 cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level))

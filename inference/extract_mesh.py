@@ -41,7 +41,10 @@ gives the copy a fresh one).  The file is ``mesh_edit_<op>_<id>.ply`` or ``mesh_
 ``--split_instances`` files are ``mesh_edit_..._instance_<id>.ply``; the component flags act on the edited lattice.  At a cut face -- where
 a box face passes through matter: an extracted or moved object's sides, the hole a delete leaves -- the mesh is closed by a cap whose colour
 and labels are the field's values just inside the object.  ``--save_voxel_cloud`` is refused together with an edit: that cloud lives on the
-model grid through ``get_instance_clusters``, which knows nothing of edits.
+model grid through ``get_instance_clusters``, which knows nothing of edits.  ``--follow_shape`` (with ``--shape_grid``, ``--shape_grow``,
+``--shape_alpha``, as in inference/edit_scene.py) makes the edits follow the instance's shape, not its box: the shapes are
+read from the field once it is loaded, the slot table comes from ``--cached_centroids_path`` (a linear-assignment model needs none), and
+the file is ``mesh_edit_<tag>_shape.ply``.
 """
 import argparse
 import math
@@ -155,7 +158,8 @@ def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, 
 
 def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
                  device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None):
-    """``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``."""
+    """``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
+    ``edit`` may be a callable ``edit(config, scene, model, renderer)`` that resolves it once the field is loaded (``--follow_shape``)."""
     if edit is not None and save_voxel_cloud:
         raise SystemExit(VOXEL_CLOUD_WITH_EDIT)
     if edit is not None and not edit_tag:
@@ -172,6 +176,8 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
             centroids = pickle.load(f)
     level = default_level(renderer, alpha_level) if level is None else float(level)
     use_delta = bool(getattr(config, "use_delta", False))
+    if callable(edit):
+        edit = edit(config, scene, model, renderer)
     timer = StageTimer()
     sigma = renderer.get_dense_sigma(model, upsample) if edit is None else renderer.get_dense_sigma(model, upsample, edit=edit)
     timer.done("dense_sigma")
@@ -221,15 +227,18 @@ def mesh_stem(edit_tag=None):
 
 
 def edit_tag_of(args):
-    """``<op>_<id>`` or ``script_<file stem>`` (the tags of inference/edit_scene.py's output folders); None without an edit."""
+    """``<op>_<id>`` or ``script_<file stem>`` (the tags of inference/edit_scene.py's output folders), with ``_shape`` behind it under
+    ``--follow_shape``; None without an edit."""
+    suffix = "_shape" if getattr(args, "follow_shape", False) else ""
     if args.script is not None:
-        return f"script_{Path(args.script).stem}"
-    return None if args.op is None else f"{args.op}_{args.instance}"
+        return f"script_{Path(args.script).stem}{suffix}"
+    return None if args.op is None else f"{args.op}_{args.instance}{suffix}"
 
 
-def resolve_cli_edit(args):
+def resolve_cli_edit(args, shape_of=None):
     """(edit, tag) of the parsed command line, (None, None) without an edit: the boxes of ``--bboxes`` through inference/edit_scene.py's
-    ``resolve_edit`` / ``resolve_program``."""
+    ``resolve_edit`` / ``resolve_program``.  ``shape_of`` (``edit_scene.field_shapes`` of the loaded field) makes the shapes of
+    ``--follow_shape`` and of script entries with ``"shape": true``."""
     tag = edit_tag_of(args)
     if tag is None:
         return None, None
@@ -238,10 +247,27 @@ def resolve_cli_edit(args):
     assert tuple(es.OPS) == EDIT_OPS
     with open(args.bboxes, "rb") as f:
         boxes = pickle.load(f)
+    follow = bool(getattr(args, "follow_shape", False))
+    if follow and shape_of is None:
+        raise SystemExit("--follow_shape reads the shapes from the trained field: resolve the edit once the field is loaded (cli_edit_of)")
     if args.script is not None:
         with open(args.script) as f:
-            return es.resolve_program(boxes, json.load(f)), tag
-    return es.resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad), tag
+            return es.resolve_program(boxes, json.load(f), follow_shape=follow, shape_of=shape_of), tag
+    return es.resolve_edit(boxes, args.instance, args.op, args.translate, args.rotate_deg, args.pad, shape=shape_of if follow else None), tag
+
+
+def cli_edit_of(args):
+    """What ``extract_mesh(edit=)`` takes for the parsed command line: the resolved edit, or under ``--follow_shape`` a callable that
+    resolves it with the shapes of the loaded field (the slot table from ``render_panopli.layers_table``)."""
+    import edit_scene as es
+    if not (getattr(args, "follow_shape", False) or es.script_asks_for_shapes(args.script)):
+        return resolve_cli_edit(args)[0]
+
+    def late(config, scene, model, renderer):
+        table = es.shape_table(config, scene, args.cached_centroids_path)
+        return resolve_cli_edit(args, es.field_shapes(model, renderer, table, args.shape_grid, args.shape_grow, args.shape_alpha,
+                                                      bool(getattr(config, "use_delta", False))))[0]
+    return late
 
 
 class _Parser(argparse.ArgumentParser):
@@ -252,6 +278,8 @@ class _Parser(argparse.ArgumentParser):
         if a.script is None and (a.instance is None) != (a.op is None):
             self.error("--instance and --op come together")
         if edit_tag_of(a) is None:
+            if a.follow_shape:
+                raise SystemExit("--follow_shape shapes an edit: give --bboxes with --instance ID --op OP, or with --script FILE.json")
             if a.bboxes is not None:
                 self.error("--bboxes needs an edit: --instance ID --op OP, or --script FILE.json")
             return a
@@ -302,6 +330,8 @@ def build_parser():
     ap.add_argument("--rotate_deg", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("RX", "RY", "RZ"),
                     help="copy / move: rotation about the box centre, R = Rz Ry Rx (degrees)")
     ap.add_argument("--pad", type=float, default=0.0, help="grow the fitted box by this much on every side")
+    import edit_scene as es
+    es.add_shape_arguments(ap)
     return ap
 
 
@@ -310,7 +340,7 @@ if __name__ == "__main__":
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
     cfg.image_dim = list(args.image_dim)
-    the_edit, the_tag = resolve_cli_edit(args)
+    the_edit, the_tag = cli_edit_of(args), edit_tag_of(args)
     print(extract_mesh(cfg, upsample=args.upsample, alpha_level=args.alpha_level, level=args.level,
                        cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
                        save_voxel_cloud=args.save_voxel_cloud, min_component=args.min_component, keep_largest=args.keep_largest,

@@ -1,0 +1,376 @@
+"""Shaped edits on the GPU (csrc/edit.hip, csrc/edit_kernels_dev.h): clift_shape_pack against the host packing, the shaped
+walk over points (clift_edit_shaped_points) against its fp32 restatement bit for bit and against the fp64 walk under the face rule, the
+shaped lattice and render, ``EditShape.from_field`` / ``engine.point_slots`` against their recomposition, the refusals, and the mesh tool
+with ``--follow_shape``.  Everything runs on scene130's field or smaller.
+
+Rows (rays) within 1e-5 of a box face or of a cell face of a lattice that a stage reads are left out by the fp64 face rule
+(tests/edit_shape_cases.py); every test asserts its cap on their number from the fp64 walk alone."""
+import ctypes as C
+import math
+import pickle
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import edit_cases as ec
+import edit_mesh_cases as emc
+import edit_program_cases as epc
+import edit_shape_cases as sc
+from conftest import T, rel_close
+from test_gpu_edit_mesh import LEVEL, UP, cli, scene, stages  # noqa: F401  (cli and scene are that module's fixtures, used here as they are)
+from test_gpu_edit_program import box_C, cfg_of, chain_case
+from test_gpu_scene_edit import DEV, NAMES, build_model, build_renderer, outputs
+
+pytestmark = pytest.mark.gpu
+
+KILLED, REMAPS = 0x80, 0x0f
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.int32)
+
+
+def shaped(name, dims, p=0.5):
+    base = emc.program(name)
+    return base, sc.with_shapes(base, sc.bernoulli_shapes(len(base), dims, p))
+
+
+# ============================================================================ 1. clift_shape_pack
+@pytest.mark.parametrize("dims", [(1, 1, 1), (3, 5, 7), (8, 8, 33), (16, 16, 64)])
+def test_pack_against_the_host_backend(dims):
+    from contrastive_lift_amd import edit
+    flags = np.random.default_rng(3).random(dims) < 0.1
+    for grow in (0, 1, 2, 4):
+        host = edit.EditShape.from_flags(flags, grow=grow, backend="host")
+        dev = edit.EditShape.from_flags(flags, grow=grow, backend="device", device=DEV)
+        assert dev.dims == dims and np.array_equal(dev.words, host.words), grow
+        assert np.array_equal(dev.on(DEV).cpu().numpy().view(np.uint32), host.words)
+        again = edit.EditShape.from_flags(torch.from_numpy(flags).to(DEV), grow=grow)     # a device tensor; the second run: the same bits
+        assert np.array_equal(again.words, dev.words)
+    assert host.n_set >= int(flags.sum())
+
+
+def test_pack_errors_through_the_raw_abi():
+    from contrastive_lift_amd import _lib
+    flags = torch.ones(8 * 8 * 8, dtype=torch.uint8, device=DEV)
+    words = torch.full((16,), 0x55, dtype=torch.int32, device=DEV)
+    for g, grow, f, w, msg in (((0, 8, 8), 0, flags, words, "dimensions"), ((8, 1025, 8), 0, flags, words, "dimensions"), ((8, 8, -1), 0, flags, words, "dimensions"),
+                               ((8, 8, 8), -1, flags, words, "grow"), ((8, 8, 8), 5, flags, words, "grow"),
+                               ((8, 8, 8), 1, None, words, "NULL"), ((8, 8, 8), 1, flags, None, "NULL")):
+        with pytest.raises(_lib.CliftError, match=msg):
+            _lib.call("clift_shape_pack", _lib.ptr(f), g[0], g[1], g[2], grow, _lib.ptr(w), _lib.stream())
+    torch.cuda.synchronize()
+    assert bool((words == 0x55).all())                                     # nothing was launched
+    _lib.call("clift_shape_pack", _lib.ptr(flags), 8, 8, 8, 1, _lib.ptr(words), _lib.stream())
+    assert bool((words == -1).all())
+
+
+# ============================================================================ 2. the point walk
+@pytest.mark.parametrize("dims", [(5, 6, 7), (16, 16, 16)])
+@pytest.mark.parametrize("name", ["chain", "eight"])
+def test_point_walk(name, dims):
+    """(a) the fp32 restatement: state bytes and output bits on EVERY row; (b) the fp64 walk under the face rule -- at most 1 % of the rows
+    left out (these inputs: 3, 4, 13 and 24 rows), states equal, remapped points within 2e-6 per remap and directions within 6e-7 per
+    remap, the bounds test_gpu_edit_mesh.test_walker_against_the_fp64_walk derives (positions and translations within +-1.5: asserted);
+    (c) at least 500 rows have another state than without the shapes; (d) all-ones shapes give the unshaped bits."""
+    from contrastive_lift_amd import edit
+    base, prog = shaped(name, dims)
+    pts = sc.box_points(base)
+    dirs = sc.unit_dirs(pts.shape[0])
+    assert pts.shape[0] == 512 * len(base)
+    w = sc.ref_walk(prog, pts, dirs)
+    keep = w["keep"]
+    left = int((~keep).sum())
+    differ = int((w["state"] != sc.ref_walk(base, pts)["state"]).sum())
+    print(f"{name} {dims}: {left} of {pts.shape[0]} rows left out; {differ} rows differ from the box program; remaps {np.bincount(w['hops']).tolist()}")
+    assert left <= 0.01 * pts.shape[0] and differ >= 500                   # (both from the fp64 walk alone)
+    assert np.abs(pts).max() <= 1.5 and np.abs(w["p"]).max() <= 1.5 and max(np.abs(e.t).max() for e in prog) <= 1.5
+    dp, dd = T(pts).to(DEV), T(dirs).to(DEV)
+    op_, od_, st_ = prog.apply_to_points(dp, dd)
+    op, od, st = op_.cpu().numpy(), od_.cpu().numpy(), st_.cpu().numpy()
+    p32, d32, s32 = sc.walk32(prog, pts, dirs)                             # (a)
+    assert np.array_equal(st, s32)
+    assert np.array_equal(bits(op), bits(p32)) and np.array_equal(bits(od), bits(d32))
+    assert np.array_equal(st[keep], w["state"][keep])                      # (b)
+    moved = ((st & REMAPS) > 0) & keep
+    hops = (st & REMAPS).astype(np.float64)
+    e_p, e_d = np.linalg.norm(op - w["p"], axis=1), np.linalg.norm(od - w["d"], axis=1)
+    print(f"{name} {dims}: worst point error / remap {float((e_p[moved] / hops[moved]).max()):.3g}, direction {float((e_d[moved] / hops[moved]).max()):.3g}")
+    assert moved.sum() >= 100 and (e_p[moved] <= 2e-6 * hops[moved]).all() and (e_d[moved] <= 6e-7 * hops[moved]).all()
+    still = (st & REMAPS) == 0
+    assert np.array_equal(bits(op[still]), bits(pts[still])) and np.array_equal(bits(od[still]), bits(dirs[still]))
+    bp, bd, bs = base.apply_to_points(dp, dd)                              # (c)
+    assert int((bs != st_).sum()) >= 500
+    ones = sc.with_shapes(base, [edit.EditShape.full(dims) for _ in base])  # (d)
+    ap, ad, as_ = ones.apply_to_points(dp, dd)
+    assert torch.equal(as_, bs) and torch.equal(ap, bp) and torch.equal(ad, bd)
+    op2, od2, st2 = prog.apply_to_points(dp)                               # dirs = NULL: the same points
+    assert od2 is None and torch.equal(op2, op_) and torch.equal(st2, st_)
+
+
+def test_point_walk_with_some_shapes_and_with_none():
+    """(e) h_shapes = NULL through the raw ABI is clift_edit_list_points; (f) a program in which only some edits carry a shape; and an
+    all-zero shape on a delete kills nothing."""
+    from contrastive_lift_amd import _lib, edit
+    base = emc.program("eight")
+    shapes = sc.bernoulli_shapes(8, (5, 6, 7))
+    for i in (1, 2, 6):
+        shapes[i] = None
+    prog = sc.with_shapes(base, shapes)
+    pts = sc.box_points(base)
+    dp = T(pts).to(DEV)
+    op_, _, st_ = prog.apply_to_points(dp)
+    p32, _, s32 = sc.walk32(prog, pts)
+    assert np.array_equal(st_.cpu().numpy(), s32) and np.array_equal(bits(op_.cpu().numpy()), bits(p32))
+    bp, _, bs = base.apply_to_points(dp)
+    assert int((bs != st_).sum()) >= 200
+    out, state = torch.empty_like(dp), torch.empty(pts.shape[0], dtype=torch.uint8, device=DEV)
+    _lib.call("clift_edit_shaped_points", base.records(), None, 8, _lib.ptr(dp), 3, None, 3, pts.shape[0], _lib.ptr(out), None, _lib.ptr(state),
+              _lib.stream())
+    assert torch.equal(out, bp) and torch.equal(state, bs)
+    gone = edit.EditProgram([edit.delete(base[0].src, shape=edit.EditShape.full((3, 3, 3), False))])
+    zp, _, zs = gone.apply_to_points(dp)
+    assert int(zs.count_nonzero()) == 0 and torch.equal(zp, dp)
+    assert int((edit.EditProgram([edit.delete(base[0].src)]).apply_to_points(dp)[2] != 0).sum()) >= 200
+
+
+def _bad_shaped_programs():
+    """(what, records, shapes, n_edits, message): the program's own errors and the shape's.  A product of dimensions of 2^31 or more cannot be
+    reached with dimensions of at most 1024 (1024^3 = 2^30): the library checks it, no input here can show it."""
+    from contrastive_lift_amd import _lib
+    _, prog = shaped("chain", (5, 6, 7))
+    good, sh = prog.records(), lambda: prog.shapes(DEV)
+    mode7, nan2 = prog.records(), prog.records()
+    mode7[1].mode = 7
+    nan2[2].dst.centre[1] = float("nan")
+    nine = (_lib.EditRec * 9)(*([good[0]] * 9))
+    out = [("n_edits = 0", good, sh(), 0, "1 to 8"), ("n_edits = 9", nine, sh(), 9, "1 to 8"), ("mode 7", mode7, sh(), 3, "edit 1: unknown edit mode 7"),
+           ("NaN in record 2", nan2, sh(), 3, "edit 2")]
+    for what, i, field, k, value, msg in (("dims 0", 1, "dims", 2, 0, r"edit 1: shape dimension 2 is 0"), ("dims 1025", 2, "dims", 0, 1025, r"edit 2: shape dimension 0 is 1025"),
+                                          ("inv_cell 0", 0, "inv_cell", 1, 0.0, r"edit 0: shape inv_cell\[1\]"), ("inv_cell < 0", 1, "inv_cell", 0, -3.0, r"edit 1: shape inv_cell\[0\]"),
+                                          ("inv_cell inf", 2, "inv_cell", 2, float("inf"), r"edit 2: shape inv_cell\[2\]"),
+                                          ("inv_cell nan", 0, "inv_cell", 0, float("nan"), r"edit 0: shape inv_cell\[0\]")):
+        s = sh()
+        getattr(s[i], field)[k] = value
+        out.append((what, good, s, 3, msg))
+    return prog, out
+
+
+def test_errors_of_the_shaped_entry_points(scene):
+    """(g) every listed error, raised before anything is launched, at the point walk and at the lattice."""
+    from contrastive_lift_amd import _lib, engine
+    _, m, r = scene
+    prog, bad = _bad_shaped_programs()
+    pts = T(sc.box_points(prog)).to(DEV)[:256].contiguous()
+    out = torch.full_like(pts, -7.5)
+    state = torch.full((256,), 0x55, dtype=torch.uint8, device=DEV)
+    n = [int(x) for x in r.grid_dim.tolist()]
+    ticks = [torch.linspace(0, 1, k).to(DEV) for k in n]
+    views = m.named_views()
+    vd = engine.vm_struct(views, "density", engine.grid_res(views))
+    lo, hi = r.bbox_aabb_host
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    sig = torch.full(tuple(n), -7.5, device=DEV)
+    lstate = torch.full(tuple(n), 0x55, dtype=torch.uint8, device=DEV)
+    for what, recs, shapes, n_edits, msg in bad:
+        with pytest.raises(_lib.CliftError, match=msg):
+            _lib.call("clift_edit_shaped_points", recs, shapes, n_edits, _lib.ptr(pts), 3, None, 3, 256, _lib.ptr(out), None, _lib.ptr(state), _lib.stream())
+        with pytest.raises(_lib.CliftError, match=msg):
+            _lib.call("clift_edit_shaped_dense_sigma", C.byref(vd), recs, shapes, n_edits, f3(lo), f3(hi), f3(r.inv_box_extent_host), _lib.ptr(ticks[0]),
+                      _lib.ptr(ticks[1]), _lib.ptr(ticks[2]), n[0], n[1], n[2], float(m.splus_density_shift), _lib.ptr(sig), _lib.ptr(lstate), _lib.stream())
+        torch.cuda.synchronize()
+        assert bool((out == -7.5).all()) and bool((state == 0x55).all()) and bool((sig == -7.5).all()) and bool((lstate == 0x55).all()), what
+    with pytest.raises(_lib.CliftError, match="NULL"):
+        _lib.call("clift_edit_shaped_points", prog.records(), prog.shapes(DEV), 3, _lib.ptr(pts), 3, None, 3, 256, None, None, None, _lib.stream())
+    with pytest.raises(_lib.CliftError, match="ldp"):
+        _lib.call("clift_edit_shaped_points", prog.records(), prog.shapes(DEV), 3, _lib.ptr(pts), 2, None, 3, 256, _lib.ptr(out), None, None, _lib.stream())
+    assert bool((out == -7.5).all())
+    _lib.call("clift_edit_shaped_points", prog.records(), prog.shapes(DEV), 3, _lib.ptr(pts), 3, None, 3, 256, _lib.ptr(out), None, None, _lib.stream())
+    assert torch.equal(out, prog.apply_to_points(pts)[0])                  # and the good call does write
+
+
+# ============================================================================ 3. the lattice
+@pytest.mark.parametrize("name,upsample", [("chain", 1), ("eight", 2)])
+def test_shaped_lattice(scene, name, upsample):
+    _, m, r = scene
+    base, prog = shaped(name, (5, 6, 7))
+    lp, n = emc.lattice_points(upsample)
+    sigma, state = r.get_dense_sigma(m, upsample, edit=prog, return_state=True)
+    plain = r.get_dense_sigma(m, upsample)
+    boxed = r.get_dense_sigma(m, upsample, edit=base)
+    assert tuple(sigma.shape) == tuple(state.shape) == n and state.dtype == torch.uint8
+    walked = prog.apply_to_points(T(lp).to(DEV))[2]
+    assert torch.equal(state.reshape(-1), walked)                          # the device point walk of the same points, exactly
+    untouched = state.reshape(-1) == 0
+    assert int(untouched.sum()) > lp.shape[0] // 2
+    assert torch.equal(sigma.reshape(-1)[untouched], plain.reshape(-1)[untouched])
+    st, sg = state.reshape(-1).cpu().numpy(), sigma.reshape(-1).cpu().numpy()
+    killed = (st & KILLED) != 0
+    assert killed.sum() >= 20 and (bits(sg[killed]) == 0).all()            # exactly +0.0
+    again, state2 = r.get_dense_sigma(m, upsample, edit=prog, return_state=True)
+    assert torch.equal(again, sigma) and torch.equal(state2, state)
+    assert torch.equal(r.get_dense_sigma(m, upsample, edit=prog), sigma)    # state = NULL: the same sigma
+    print(f"{name} x{upsample}: {int((sigma != boxed).sum())} lattice points differ from the box-edited lattice, {int(killed.sum())} killed")
+    assert int((sigma != boxed).sum()) >= 100
+
+
+# ============================================================================ 4. the render
+@pytest.fixture(scope="module")
+def rays130():
+    P, rays = ec.scene130()
+    return P, rays, rays.to(DEV)
+
+
+def test_all_ones_shapes_render_the_box_program(rays130):
+    from contrastive_lift_amd import edit, engine
+    P, _, rays = rays130
+    m, r = build_model(P, "softmax"), build_renderer("softmax")
+    base = emc.program("chain")
+    ones = sc.with_shapes(base, [edit.EditShape.full((5, 6, 7)) for _ in base])
+    o0, c0 = engine.edit_forward(m, r, rays, base, False)
+    o1, c1 = engine.edit_forward(m, r, rays, ones, False)
+    assert c0.M == c1.M > 1000 and torch.equal(c0.sigma, c1.sigma)
+    for name, a, b in zip(NAMES, outputs(o0), outputs(o1)):
+        assert torch.equal(a, b), name
+    one = engine.edit_forward(m, r, rays, base[0].with_shape(ones[0].shape), False)[0]       # a single shaped Edit: the list family
+    for name, a, b in zip(NAMES, outputs(one), outputs(engine.edit_forward(m, r, rays, base[0], False)[0])):
+        assert torch.equal(a, b), name
+
+
+def test_shaped_render_against_the_oracle(rays130):
+    """edit_forward under the shaped chain program against the oracle's render of the same walk (edit_program_cases.render_program over the
+    box specs narrowed by the fp64 host rule) at 1e-3, the tolerance test_gpu_edit_program holds this pipeline to; rays with a sample in a
+    face band are left out, at most 4 of them (these boxes and lattices leave out 1), as edit_program_cases.rays_off_all_faces allows."""
+    from contrastive_lift_amd import engine, inference as inf
+    P, rays_h, rays = rays130
+    base, specs, _ = chain_case()
+    prog = sc.with_shapes(base, sc.bernoulli_shapes(3, (5, 6, 7)))
+    specs = [sc.shaped_spec(s, e) for s, e in zip(specs, prog)]
+    cfg = cfg_of("softmax")
+    keep = sc.rays_off_all_faces(rays_h, cfg, prog, cap=4)
+    print(f"shaped chain: {int((~keep).sum())} of 130 rays left out")
+    ref, ref_sigma, hops = epc.render_program(P, rays_h, cfg, specs, True)
+    m, r = build_model(P, "softmax"), build_renderer("softmax")
+    o, ctx = engine.edit_forward(m, r, rays, prog, True)
+    assert ctx.M > 1000 and int((hops > 0).sum()) > 100
+    rel_close(ctx.sigma.cpu()[keep], ref_sigma[keep], 1e-3, what="shaped chain sigma")
+    for name, x, y in zip(NAMES, outputs(o), ref):
+        rel_close(x.cpu()[keep], y[keep], 1e-3, what=f"shaped chain {name}")
+    boxed = engine.edit_forward(m, r, rays, base, True)[0]
+    assert float((boxed["depth"] - o["depth"]).abs().max()) > 0.02         # (the shapes show in this frame)
+    chunked = inf.render_rays_edit(m, r, rays, 50, True, edit=prog)
+    whole = inf.render_rays_edit(m, r, rays, 0, True, edit=prog)
+    for name, a, b in zip(NAMES, chunked, whole):
+        rel_close(a.cpu(), b.cpu(), 1e-3, what=f"chunked against whole {name}")
+
+
+# ============================================================================ 5. from_field and point_slots
+def _table(m):
+    from contrastive_lift_amd.layers import SlotTable
+    return SlotTable.from_scores([0], ec.C_CLS, int(m.render_instance_mlp.output_channels))
+
+
+def _slots_by_hand(m, r, pts, table):
+    from contrastive_lift_amd import _lib
+    xn = r.normalize_coordinates(pts).contiguous()
+    sem = m.render_semantic_mlp(None, m.compute_semantic_feature(xn)).float().contiguous()
+    feat = m.render_instance_mlp(None, m.compute_instance_feature(xn)).float().contiguous()
+    cls_slots, cent = table.on(pts.device)
+    slots = torch.empty(pts.shape[0], dtype=torch.int32, device=pts.device)
+    _lib.call("clift_sample_slots", _lib.ptr(sem), sem.shape[1], sem.shape[1], _lib.ptr(feat), feat.shape[1], table.E, None, 3, _lib.ptr(cls_slots),
+              _lib.ptr(cent), table.K_base, table.mode, pts.shape[0], _lib.ptr(slots), _lib.stream())
+    return slots
+
+
+def test_from_field(scene):
+    from contrastive_lift_amd import edit, engine
+    _, m, r = scene
+    table, box, dims, level = _table(m), box_C(), (9, 8, 10), 3.0
+    sh = edit.EditShape.from_field(m, r, box, table, dims=dims, grow=0, sigma_min=level)
+    ax = [box.lo[a] + (np.arange(dims[a]) + 0.5) * ((box.hi[a] - box.lo[a]) / dims[a]) for a in range(3)]
+    q = np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+    pts = T((q @ box.axes + box.centre).astype(np.float32)).to(DEV)
+    with torch.no_grad():
+        inside = ((pts >= r.bbox_aabb[0]) & (pts <= r.bbox_aabb[1])).all(-1)
+        occupied = inside & (m.compute_density(r.normalize_coordinates(pts)) >= level)
+        slots = engine.point_slots(m, r, pts, table)
+    slot = edit.majority_slot(slots[occupied].cpu().numpy())
+    flags = (occupied & (slots == slot)).cpu().numpy().reshape(dims)
+    assert sh.slot == slot and sh.n_occupied == int(occupied.sum()) and 20 <= sh.n_set < sh.n_cells
+    assert np.array_equal(sh.words, edit.EditShape.from_flags(flags, backend="host").words) and np.array_equal(sh.flags(), flags)
+    assert edit.EditShape.from_field(m, r, box, table, slot=slot, dims=dims, grow=0, sigma_min=level).n_set == sh.n_set
+    grown = edit.EditShape.from_field(m, r, box, table, dims=dims, grow=1, sigma_min=level)
+    assert (grown.flags() | ~sh.flags()).all() and grown.n_set > sh.n_set and grown.slot == sh.slot
+    assert np.array_equal(grown.words, edit.EditShape.from_flags(flags, grow=1, backend="host").words)
+    with pytest.raises(ValueError, match="no occupied cell"):
+        edit.EditShape.from_field(m, r, box, table, dims=dims, sigma_min=1e6)
+    far = edit.EditBox(np.eye(3), [3.0, 3.0, 3.0], [-0.1, -0.1, -0.1], [0.1, 0.1, 0.1])      # outside the aabb: nothing is occupied
+    with pytest.raises(ValueError, match="no occupied cell"):
+        edit.EditShape.from_field(m, r, far, table, dims=(4, 4, 4), sigma_min=0.0)
+
+
+def test_point_slots(scene):
+    import contrastive_lift_amd as cl
+    from contrastive_lift_amd import engine
+    _, m, r = scene
+    pts = T(emc.cloud_points(3000)[0]).to(DEV)
+    table = _table(m)
+    got = engine.point_slots(m, r, pts, table, chunk=1024)                  # three chunks
+    assert got.dtype == torch.int32 and torch.equal(got, _slots_by_hand(m, r, pts, table)) and int((got >= 0).sum()) > 1000
+    torch.manual_seed(5)
+    g = cl.TensorVMSplit(list(ec.RES), num_semantics_comps=(32, 32, 32), num_instance_comps=(32, 32, 32), num_semantic_classes=ec.C_CLS,
+                         dim_feature_instance=2 * ec.E_INST, splus_density_shift=ec.SHIFT, use_semantic_mlp=False, use_instance_mlp=False,
+                         slow_fast_mode=True, device=DEV)                  # both heads on their own VM grids
+    assert g.semantic_plane is not None and g.instance_plane is not None
+    with torch.no_grad():                                                  # (a fresh field's instance outputs are flat: one slot everywhere)
+        for key, p in g.named_parameters():
+            if "instance" in key:
+                p.copy_(torch.randn_like(p))
+    from contrastive_lift_amd.layers import SlotTable
+    tg = SlotTable.from_scores(range(ec.C_CLS), ec.C_CLS, int(g.render_instance_mlp.output_channels))
+    got = engine.point_slots(g, r, pts, tg, chunk=2048)
+    assert torch.equal(got, _slots_by_hand(g, r, pts, tg)) and len(torch.unique(got)) >= 2
+
+
+# ============================================================================ 6. the refusals
+def test_refusals_of_a_shaped_program(scene, rays130):
+    from contrastive_lift_amd import engine
+    _, m, r = scene
+    _, _, rays = rays130
+    _, prog = shaped("chain", (5, 6, 7))
+    table = _table(m)
+    pts = T(emc.cloud_points(64)[0]).to(DEV)
+    ctx = engine.edit_forward(m, r, rays, prog, False)[1]
+    for call in (lambda: engine.edit_surface_from_ctx(m, r, ctx), lambda: engine.edit_surface_forward(m, r, rays, prog),
+                 lambda: engine.edit_layers_forward(m, r, rays, prog, table), lambda: engine.edit_density_grad_points(m, r, pts, prog),
+                 lambda: engine._edit_surface_launches(m, ctx, 0.5), lambda: engine.edit_layers_forward(m, r, rays, prog[0], table)):
+        with pytest.raises(NotImplementedError, match="shaped"):
+            call()
+
+
+# ============================================================================ 7. the mesh tool
+def test_mesh_tool_follows_the_shape(cli, scene, tmp_path):
+    """inference/extract_mesh.py --op delete --follow_shape against --op delete on the blob: the shaped delete takes less away."""
+    _, m, r = scene
+    Cb = box_C()
+    path = tmp_path / "bboxes.pkl"
+    with open(path, "wb") as f:
+        pickle.dump({1: {"bbox": (Cb.lo, Cb.hi), "orientation": Cb.axes, "position": Cb.centre}}, f)
+    E = int(m.render_instance_mlp.output_channels)
+    config = types.SimpleNamespace(instance_loss_mode="linear_assignment", max_instances=E, use_delta=False)
+    data = types.SimpleNamespace(segmentation_data=types.SimpleNamespace(fg_classes=[0], bg_classes=[1, 2, 3]))
+    alpha = min(1.0 - math.exp(-LEVEL * 2.0 * r.step_size_host * float(r.distance_scale)), 0.999999)     # default_level(alpha) = LEVEL
+    common = ["--ckpt_path", "runs/x/checkpoints/y.ckpt", "--bboxes", str(path), "--instance", "1", "--op", "delete"]
+    a_box = cli.build_parser().parse_args(common)
+    a_shape = cli.build_parser().parse_args(common + ["--follow_shape", "--shape_grid", "12", "--shape_grow", "0", "--shape_alpha", repr(alpha)])
+    e_box, e_shape = cli.cli_edit_of(a_box), cli.cli_edit_of(a_shape)(config, data, m, r)
+    assert not e_box.shape and e_shape.shape is not None and e_shape.shape.dims == (12, 12, 12) and 0 < e_shape.shape.n_set < 12 ** 3
+    assert cli.mesh_stem(cli.edit_tag_of(a_shape)) == "mesh_edit_delete_1_shape"
+    mb, _, _ = stages(cli, scene, e_box)
+    ms, _, _ = stages(cli, scene, e_shape)
+    plain = r.get_dense_sigma(m, UP)
+    inside = lambda s: int((s >= LEVEL).sum())
+    print(f"inside points: unedited {inside(plain)}, box delete {inside(mb['sigma'])}, shaped delete {inside(ms['sigma'])}")
+    assert inside(ms["sigma"]) >= inside(mb["sigma"]) and not torch.equal(ms["sigma"], plain)
