@@ -13,6 +13,10 @@
 // the point, gives the gradient of the EDITED density for the surface outputs of an edited scene (clift_edit_list_density_grad_*, at the end).
 // An edit may also carry a SHAPE, a bit lattice over its source box (clift_edit_shaped_*, clift_shape_pack): the four walk
 // kernels live in edit_kernels_dev.h and are compiled twice, for the plain program (k_edit_list_*) and for the shaped one (k_edit_shaped_*).
+// Layout of the host side: the program's own checks (edit_check, edit_list_check, edit_shapes_check), then per walk kernel ONE checked
+// body that every tier of entry points calls -- the single edit, the list and the shaped program are thin wrappers that differ in how the
+// program is resolved ("the entry points over the walk kernels"); the untwinned entry points (active_origin, shape_pack, density_grad_*)
+// follow with their kernels.
 #include "clift_dev.h"
 #include "density_sweep_dev.h"
 #include "lattice_dev.h"
@@ -282,83 +286,160 @@ __device__ __forceinline__ RayG edit_active_point(const MarchP& m, const float* 
 #undef EDIT_PROG
 #undef EDIT_K
 
-// ============================================================================ density forward under an edit (the kernel: edit_kernels_dev.h)
+// ============================================================================ the entry points over the walk kernels
+// One checked host body per walk kernel (edit_density_fwd, edit_active, edit_points, edit_dense_sigma): it takes the public name (``who``:
+// every message starts with it, and clift_check_launch reports under it), the program as its own check resolved it -- an EditLS and whether
+// it is shaped -- and the rest of the arguments; it holds every check that follows the program's own, the early return and the launch:
+// k_edit_shaped_* with the whole program when it is shaped, k_edit_list_* with its edits alone (an EditL) when it is not.  The public
+// functions differ only in how they resolve the program: clift_edit_shaped_* by edit_shapes_check(h_edits, h_shapes), clift_edit_list_* by
+// the same with no shapes (clift.h: "h_shapes == NULL gives the list entry point's behaviour"), the two single-edit names by edit_check
+// and edit_list_of_one, with their own wording.  A check added to a body holds for every tier.
+static inline float3 f3_of(const float* h) { return make_float3(h[0], h[1], h[2]); }
+
+// ---- density forward under a program (the kernel: edit_kernels_dev.h)
+static int edit_density_fwd(const char* who, const EditLS& P, bool shaped, const clift_march_t* h_m, const clift_vm_t* h_dens, const float* rays,
+                            int N, float* sigma, clift_stream_t s) {
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "%s: comps must be a multiple of 4 (got %d)", who, h_dens->comps);
+    CLIFT_REQUIRE(h_m->n_samples > 0, "%s: n_samples must be positive (got %d)", who, h_m->n_samples);
+    if (N <= 0) return 0;
+    const dim3 grid(cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES)), block(64 * SWEEP_WAVES);
+    if (shaped)
+        k_edit_shaped_density_fwd<<<grid, block, 0, as_stream(s)>>>(to_dev(h_m), P, to_dev(h_dens), rays, N, sigma);
+    else
+        k_edit_list_density_fwd<<<grid, block, 0, as_stream(s)>>>(to_dev(h_m), P.L, to_dev(h_dens), rays, N, sigma);
+    return clift_check_launch(who);
+}
+
 extern "C" int clift_edit_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edit, const clift_vm_t* h_dens, const float* rays, int N,
                                       float* sigma, clift_stream_t s) {
     if (edit_check(h_edit, "clift_edit_density_fwd")) return 1;
-    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
-    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
-    if (N <= 0) return 0;
-    k_edit_list_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES), 64 * SWEEP_WAVES, 0, as_stream(s)>>>(to_dev(h_m), edit_list_of_one(h_edit),
-                                                                                                                          to_dev(h_dens), rays, N, sigma);
-    return clift_check_launch("clift_edit_density_fwd");
+    EditLS P;
+    P.L = edit_list_of_one(h_edit);
+    return edit_density_fwd("clift_edit_density_fwd", P, false, h_m, h_dens, rays, N, sigma, s);
 }
 
 extern "C" int clift_edit_list_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const clift_vm_t* h_dens,
                                            const float* rays, int N, float* sigma, clift_stream_t s) {
-    EditL L;
-    if (edit_list_check(h_edits, n_edits, "clift_edit_list_density_fwd", &L)) return 1;
-    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_list_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
-    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
-    if (N <= 0) return 0;
-    k_edit_list_density_fwd<<<cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES), 64 * SWEEP_WAVES, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens),
-                                                                                                                          rays, N, sigma);
-    return clift_check_launch("clift_edit_list_density_fwd");
+    EditLS P;
+    bool shaped;
+    if (edit_shapes_check(h_edits, nullptr, n_edits, "clift_edit_list_density_fwd", &P, &shaped)) return 1;
+    return edit_density_fwd("clift_edit_list_density_fwd", P, shaped, h_m, h_dens, rays, N, sigma, s);
 }
 
 extern "C" int clift_edit_shaped_density_fwd(const clift_march_t* h_m, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
                                              const clift_vm_t* h_dens, const float* rays, int N, float* sigma, clift_stream_t s) {
-    EditLS L;
+    EditLS P;
     bool shaped;
-    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_density_fwd", &L, &shaped)) return 1;
-    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_shaped_density_fwd: comps must be a multiple of 4 (got %d)", h_dens->comps);
-    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_shaped_density_fwd: n_samples must be positive (got %d)", h_m->n_samples);
-    if (N <= 0) return 0;
-    const dim3 grid(cdiv((long)N * cdiv(h_m->n_samples, 64), SWEEP_WAVES)), block(64 * SWEEP_WAVES);
-    if (shaped)
-        k_edit_shaped_density_fwd<<<grid, block, 0, as_stream(s)>>>(to_dev(h_m), L, to_dev(h_dens), rays, N, sigma);
-    else
-        k_edit_list_density_fwd<<<grid, block, 0, as_stream(s)>>>(to_dev(h_m), L.L, to_dev(h_dens), rays, N, sigma);
-    return clift_check_launch("clift_edit_shaped_density_fwd");
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_density_fwd", &P, &shaped)) return 1;
+    return edit_density_fwd("clift_edit_shaped_density_fwd", P, shaped, h_m, h_dens, rays, N, sigma, s);
 }
 
-// ============================================================================ positions and view directions of the active samples
+// ---- positions and view directions of the active samples
+static int edit_active(const char* who, const EditLS& P, bool shaped, const clift_march_t* h_m, const float* rays, const int* act_idx, int M,
+                       float* xa, float* dirs, clift_stream_t s) {
+    CLIFT_REQUIRE(h_m->n_samples > 0, "%s: n_samples must be positive (got %d)", who, h_m->n_samples);
+    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "%s: xa and dirs are both written", who);
+    if (M <= 0) return 0;
+    if (shaped)
+        k_edit_shaped_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), P, rays, act_idx, M, xa, dirs);
+    else
+        k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), P.L, rays, act_idx, M, xa, dirs);
+    return clift_check_launch(who);
+}
+
 extern "C" int clift_edit_active(const clift_march_t* h_m, const clift_edit_t* h_edit, const float* rays, const int* act_idx, int M, float* xa,
                                  float* dirs, clift_stream_t s) {
     if (edit_check(h_edit, "clift_edit_active")) return 1;
-    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_active: n_samples must be positive (got %d)", h_m->n_samples);
-    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_active: xa and dirs are both written");
-    if (M <= 0) return 0;
-    k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), edit_list_of_one(h_edit), rays, act_idx, M, xa, dirs);
-    return clift_check_launch("clift_edit_active");
+    EditLS P;
+    P.L = edit_list_of_one(h_edit);
+    return edit_active("clift_edit_active", P, false, h_m, rays, act_idx, M, xa, dirs, s);
 }
 
 extern "C" int clift_edit_list_active(const clift_march_t* h_m, const clift_edit_t* h_edits, int n_edits, const float* rays, const int* act_idx, int M,
                                       float* xa, float* dirs, clift_stream_t s) {
-    EditL L;
-    if (edit_list_check(h_edits, n_edits, "clift_edit_list_active", &L)) return 1;
-    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_list_active: n_samples must be positive (got %d)", h_m->n_samples);
-    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_list_active: xa and dirs are both written");
-    if (M <= 0) return 0;
-    k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
-    return clift_check_launch("clift_edit_list_active");
+    EditLS P;
+    bool shaped;
+    if (edit_shapes_check(h_edits, nullptr, n_edits, "clift_edit_list_active", &P, &shaped)) return 1;
+    return edit_active("clift_edit_list_active", P, shaped, h_m, rays, act_idx, M, xa, dirs, s);
 }
 
 extern "C" int clift_edit_shaped_active(const clift_march_t* h_m, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
                                         const float* rays, const int* act_idx, int M, float* xa, float* dirs, clift_stream_t s) {
-    EditLS L;
+    EditLS P;
     bool shaped;
-    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_active", &L, &shaped)) return 1;
-    CLIFT_REQUIRE(h_m->n_samples > 0, "clift_edit_shaped_active: n_samples must be positive (got %d)", h_m->n_samples);
-    CLIFT_REQUIRE(xa != nullptr && dirs != nullptr, "clift_edit_shaped_active: xa and dirs are both written");
-    if (M <= 0) return 0;
-    if (shaped)
-        k_edit_shaped_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, dirs);
-    else
-        k_edit_list_active<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L.L, rays, act_idx, M, xa, dirs);
-    return clift_check_launch("clift_edit_shaped_active");
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_active", &P, &shaped)) return 1;
+    return edit_active("clift_edit_shaped_active", P, shaped, h_m, rays, act_idx, M, xa, dirs, s);
 }
 
+// ---- the walk over arbitrary points
+static int edit_points(const char* who, const EditLS& P, bool shaped, const float* pts, int ldp, const float* dirs, int ldd, long n, float* out_pts,
+                       float* out_dirs, unsigned char* state, clift_stream_t s) {
+    CLIFT_REQUIRE(ldp >= 3 && (dirs == nullptr || ldd >= 3), "%s: ldp and ldd must be >= 3 (got %d, %d)", who, ldp, ldd);
+    CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "%s: %ld rows, must be in [0, 2^36)", who, n);
+    if (n == 0) return 0;
+    CLIFT_REQUIRE(pts != nullptr && out_pts != nullptr, "%s: NULL pts or out_pts", who);
+    CLIFT_REQUIRE((dirs == nullptr) == (out_dirs == nullptr), "%s: dirs and out_dirs come together (both or neither NULL)", who);
+    if (shaped)
+        k_edit_shaped_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(P, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
+    else
+        k_edit_list_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(P.L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
+    return clift_check_launch(who);
+}
+
+extern "C" int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, const float* pts, int ldp, const float* dirs, int ldd, long n,
+                                      float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
+    EditLS P;
+    bool shaped;
+    if (edit_shapes_check(h_edits, nullptr, n_edits, "clift_edit_list_points", &P, &shaped)) return 1;
+    return edit_points("clift_edit_list_points", P, shaped, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state, s);
+}
+
+extern "C" int clift_edit_shaped_points(const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits, const float* pts, int ldp,
+                                        const float* dirs, int ldd, long n, float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
+    EditLS P;
+    bool shaped;
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_points", &P, &shaped)) return 1;
+    return edit_points("clift_edit_shaped_points", P, shaped, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state, s);
+}
+
+// ---- sigma on the lattice of the edited scene
+static int edit_dense_sigma(const char* who, const EditLS& P, bool shaped, const clift_vm_t* h_dens, const float* h_lo3, const float* h_hi3,
+                            const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2, float shift, float* out,
+                            unsigned char* state, clift_stream_t s) {
+    CLIFT_REQUIRE(h_dens && h_lo3 && h_hi3 && h_inv_ext2, "%s: NULL host record", who);
+    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "%s: comps must be a multiple of 4 (got %d)", who, h_dens->comps);
+    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "%s: lattice dimensions must be positive (got %d x %d x %d)", who, n0, n1, n2);
+    const long total = (long)n0 * n1 * n2;
+    CLIFT_REQUIRE(total < (1L << 36), "%s: %ld lattice points, must be < 2^36", who, total);
+    CLIFT_REQUIRE(s0 && s1 && s2 && out, "%s: NULL device buffer", who);
+    const float3 lo = f3_of(h_lo3), hi = f3_of(h_hi3), inv = f3_of(h_inv_ext2);
+    if (shaped)
+        k_edit_shaped_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), P, lo, hi, inv, s0, s1, s2, n0, n1, n2, shift, out, state);
+    else
+        k_edit_list_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), P.L, lo, hi, inv, s0, s1, s2, n0, n1, n2, shift, out, state);
+    return clift_check_launch(who);
+}
+
+extern "C" int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, int n_edits, const float* h_lo3, const float* h_hi3,
+                                           const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2,
+                                           float shift, float* out, unsigned char* state, clift_stream_t s) {
+    EditLS P;
+    bool shaped;
+    if (edit_shapes_check(h_edits, nullptr, n_edits, "clift_edit_list_dense_sigma", &P, &shaped)) return 1;
+    return edit_dense_sigma("clift_edit_list_dense_sigma", P, shaped, h_dens, h_lo3, h_hi3, h_inv_ext2, s0, s1, s2, n0, n1, n2, shift, out, state, s);
+}
+
+extern "C" int clift_edit_shaped_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
+                                             const float* h_lo3, const float* h_hi3, const float* h_inv_ext2, const float* s0, const float* s1,
+                                             const float* s2, int n0, int n1, int n2, float shift, float* out, unsigned char* state,
+                                             clift_stream_t s) {
+    EditLS P;
+    bool shaped;
+    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_dense_sigma", &P, &shaped)) return 1;
+    return edit_dense_sigma("clift_edit_shaped_dense_sigma", P, shaped, h_dens, h_lo3, h_hi3, h_inv_ext2, s0, s1, s2, n0, n1, n2, shift, out, state, s);
+}
+
+// ============================================================================ the origin of the content at the active samples
 // k_edit_list_active with the ORIGIN of the content beside the position: the 1-based position of the first edit the backward
 // walk meets that remaps the sample and is a DUPLICATE -- the last-applied copy in whose destination the sample sits -- or 0.  A later move
 // of the copy remaps the sample first and the walk goes on to the copy: the origin stays.  A killed sample has stopped and keeps what it
@@ -389,78 +470,6 @@ extern "C" int clift_edit_list_active_origin(const clift_march_t* h_m, const cli
     if (M <= 0) return 0;
     k_edit_list_active_origin<<<cdiv(M, 256), 256, 0, as_stream(s)>>>(to_dev(h_m), L, rays, act_idx, M, xa, origin, state);
     return clift_check_launch("clift_edit_list_active_origin");
-}
-
-// ============================================================================ the walk over arbitrary points
-extern "C" int clift_edit_list_points(const clift_edit_t* h_edits, int n_edits, const float* pts, int ldp, const float* dirs, int ldd, long n,
-                                      float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
-    EditL L;
-    if (edit_list_check(h_edits, n_edits, "clift_edit_list_points", &L)) return 1;
-    CLIFT_REQUIRE(ldp >= 3 && (dirs == nullptr || ldd >= 3), "clift_edit_list_points: ldp and ldd must be >= 3 (got %d, %d)", ldp, ldd);
-    CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "clift_edit_list_points: %ld rows, must be in [0, 2^36)", n);
-    if (n == 0) return 0;
-    CLIFT_REQUIRE(pts != nullptr && out_pts != nullptr, "clift_edit_list_points: NULL pts or out_pts");
-    CLIFT_REQUIRE((dirs == nullptr) == (out_dirs == nullptr), "clift_edit_list_points: dirs and out_dirs come together (both or neither NULL)");
-    k_edit_list_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
-    return clift_check_launch("clift_edit_list_points");
-}
-
-extern "C" int clift_edit_shaped_points(const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits, const float* pts, int ldp,
-                                        const float* dirs, int ldd, long n, float* out_pts, float* out_dirs, unsigned char* state, clift_stream_t s) {
-    EditLS L;
-    bool shaped;
-    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_points", &L, &shaped)) return 1;
-    CLIFT_REQUIRE(ldp >= 3 && (dirs == nullptr || ldd >= 3), "clift_edit_shaped_points: ldp and ldd must be >= 3 (got %d, %d)", ldp, ldd);
-    CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "clift_edit_shaped_points: %ld rows, must be in [0, 2^36)", n);
-    if (n == 0) return 0;
-    CLIFT_REQUIRE(pts != nullptr && out_pts != nullptr, "clift_edit_shaped_points: NULL pts or out_pts");
-    CLIFT_REQUIRE((dirs == nullptr) == (out_dirs == nullptr), "clift_edit_shaped_points: dirs and out_dirs come together (both or neither NULL)");
-    if (shaped)
-        k_edit_shaped_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
-    else
-        k_edit_list_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(L.L, pts, ldp, dirs, ldd, n, out_pts, out_dirs, state);
-    return clift_check_launch("clift_edit_shaped_points");
-}
-
-// ============================================================================ sigma on the lattice of the edited scene
-extern "C" int clift_edit_list_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, int n_edits, const float* h_lo3, const float* h_hi3,
-                                           const float* h_inv_ext2, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2,
-                                           float shift, float* out, unsigned char* state, clift_stream_t s) {
-    EditL L;
-    if (edit_list_check(h_edits, n_edits, "clift_edit_list_dense_sigma", &L)) return 1;
-    CLIFT_REQUIRE(h_dens && h_lo3 && h_hi3 && h_inv_ext2, "clift_edit_list_dense_sigma: NULL host record");
-    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_list_dense_sigma: comps must be a multiple of 4 (got %d)", h_dens->comps);
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_edit_list_dense_sigma: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
-    const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < (1L << 36), "clift_edit_list_dense_sigma: %ld lattice points, must be < 2^36", total);
-    CLIFT_REQUIRE(s0 && s1 && s2 && out, "clift_edit_list_dense_sigma: NULL device buffer");
-    k_edit_list_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, make_float3(h_lo3[0], h_lo3[1], h_lo3[2]),
-                                                                        make_float3(h_hi3[0], h_hi3[1], h_hi3[2]),
-                                                                        make_float3(h_inv_ext2[0], h_inv_ext2[1], h_inv_ext2[2]), s0, s1, s2, n0, n1,
-                                                                        n2, shift, out, state);
-    return clift_check_launch("clift_edit_list_dense_sigma");
-}
-
-extern "C" int clift_edit_shaped_dense_sigma(const clift_vm_t* h_dens, const clift_edit_t* h_edits, const clift_edit_shape_t* h_shapes, int n_edits,
-                                             const float* h_lo3, const float* h_hi3, const float* h_inv_ext2, const float* s0, const float* s1,
-                                             const float* s2, int n0, int n1, int n2, float shift, float* out, unsigned char* state,
-                                             clift_stream_t s) {
-    EditLS L;
-    bool shaped;
-    if (edit_shapes_check(h_edits, h_shapes, n_edits, "clift_edit_shaped_dense_sigma", &L, &shaped)) return 1;
-    CLIFT_REQUIRE(h_dens && h_lo3 && h_hi3 && h_inv_ext2, "clift_edit_shaped_dense_sigma: NULL host record");
-    CLIFT_REQUIRE(h_dens->comps % 4 == 0, "clift_edit_shaped_dense_sigma: comps must be a multiple of 4 (got %d)", h_dens->comps);
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_edit_shaped_dense_sigma: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
-    const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < (1L << 36), "clift_edit_shaped_dense_sigma: %ld lattice points, must be < 2^36", total);
-    CLIFT_REQUIRE(s0 && s1 && s2 && out, "clift_edit_shaped_dense_sigma: NULL device buffer");
-    const float3 lo = make_float3(h_lo3[0], h_lo3[1], h_lo3[2]), hi = make_float3(h_hi3[0], h_hi3[1], h_hi3[2]),
-                 inv = make_float3(h_inv_ext2[0], h_inv_ext2[1], h_inv_ext2[2]);
-    if (shaped)
-        k_edit_shaped_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, lo, hi, inv, s0, s1, s2, n0, n1, n2, shift, out, state);
-    else
-        k_edit_list_dense_sigma<<<cdiv(total, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L.L, lo, hi, inv, s0, s1, s2, n0, n1, n2, shift, out, state);
-    return clift_check_launch("clift_edit_shaped_dense_sigma");
 }
 
 // ============================================================================ packing a shape
@@ -596,8 +605,7 @@ extern "C" int clift_edit_list_density_grad_points(const clift_edit_t* h_edits, 
     CLIFT_REQUIRE(n >= 0 && n < (1L << 36), "clift_edit_list_density_grad_points: %ld rows, must be in [0, 2^36)", n);
     if (n == 0) return 0;
     CLIFT_REQUIRE(pts != nullptr && out != nullptr, "clift_edit_list_density_grad_points: NULL pts or out");
-    k_edit_list_density_grad_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, pts, ldp, n, make_float3(h_lo3[0], h_lo3[1], h_lo3[2]),
-                                                                            make_float3(h_inv2[0], h_inv2[1], h_inv2[2]), shift, out, state);
+    k_edit_list_density_grad_points<<<cdiv(n, 256), 256, 0, as_stream(s)>>>(to_dev(h_dens), L, pts, ldp, n, f3_of(h_lo3), f3_of(h_inv2), shift, out, state);
     return clift_check_launch("clift_edit_list_density_grad_points");
 }
 

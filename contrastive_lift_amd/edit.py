@@ -359,8 +359,17 @@ class EditProgram:
 
     @property
     def is_shaped(self):
-        """Whether any edit follows a shape (the ``clift_edit_shaped_*`` entry points take the program then)."""
+        """Whether any edit follows a shape (``launch_family`` hands the program to the ``clift_edit_shaped_*`` entry points then)."""
         return any(e.shape is not None for e in self.edits)
+
+    def launch_family(self, device):
+        """How the program is passed to the four walk entry points (density_fwd, active, points, dense_sigma): -> (name pattern, leading
+        arguments).  ``pattern % "points"`` is the entry point; the arguments -- the records, for a shaped program the shape records with
+        their words on ``device`` right behind them, then the count -- are adjacent in every one of the four argument lists and splice in
+        with ``*``.  The one place that picks between the list and the shaped family."""
+        if self.is_shaped:
+            return "clift_edit_shaped_%s", (self.records(), self.shapes(device), len(self.edits))
+        return "clift_edit_list_%s", (self.records(), len(self.edits))
 
     def shapes(self, device):
         """Contiguous ctypes array of the n ``clift_edit_shape_t`` records, in program order, their words on ``device`` (the ``h_shapes``
@@ -447,12 +456,8 @@ class EditProgram:
         out_p = torch.empty_like(pts)
         out_d = None if dr is None else torch.empty_like(dr)
         state = torch.empty(n, dtype=torch.uint8, device=pts.device)
-        if self.is_shaped:
-            _lib.call("clift_edit_shaped_points", self.records(), self.shapes(pts.device), len(self.edits), _lib.ptr(pts), 3, _lib.ptr(dr), 3, n,
-                      _lib.ptr(out_p), _lib.ptr(out_d), _lib.ptr(state), _lib.stream())
-        else:
-            _lib.call("clift_edit_list_points", self.records(), len(self.edits), _lib.ptr(pts), 3, _lib.ptr(dr), 3, n, _lib.ptr(out_p),
-                      _lib.ptr(out_d), _lib.ptr(state), _lib.stream())
+        kernel, program = self.launch_family(pts.device)
+        _lib.call(kernel % "points", *program, _lib.ptr(pts), 3, _lib.ptr(dr), 3, n, _lib.ptr(out_p), _lib.ptr(out_d), _lib.ptr(state), _lib.stream())
         return out_p, out_d, state
 
 

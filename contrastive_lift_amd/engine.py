@@ -1112,21 +1112,18 @@ def _refuse_shaped(who, prog):
 
 
 def _edit_density_march(model, renderer, rays, edit, weight_thres):
-    """The march of an edit pass: a single ``Edit`` through clift_edit_density_fwd, anything else (``as_program``) through
-    clift_edit_list_density_fwd; a program one of whose edits follows a shape (``edit.EditShape``; a single shaped ``Edit`` included)
-    through clift_edit_shaped_density_fwd, with the shape records right behind the edits.  Returns (context, the kernel-name pattern and the leading edit arguments of that family); the context
-    keeps the resolved program (``edit_program``; a single edit as a program of one, whose list walk is that edit op for op)."""
+    """The march of an edit pass.  The program (``as_program``) says which entry points take it (``EditProgram.launch_family``): the
+    list family, or the shaped one when an edit follows a shape (``edit.EditShape``).  One exception is kept here: a single ``Edit``
+    without a shape goes through clift_edit_density_fwd / clift_edit_active, the single-edit names.
+
+    Returns (context, kernel-name pattern, leading edit arguments of that family).  The context keeps the resolved program
+    (``edit_program``; a single edit as a program of one, whose list walk is that edit op for op)."""
     N, st = rays.shape[0], stream()
     prog = _edit.as_program(edit)
-    if prog.is_shaped:          # some edit follows a shape (edit.EditShape): the shaped list family, a single Edit as a program of one
-        rec = prog.records()
-        edit_kernel, edit_args = "clift_edit_shaped_%s", (rec, prog.shapes(rays.device), len(prog))
-    elif isinstance(edit, _edit.Edit):
-        rec = edit.record()
-        edit_kernel, edit_args = "clift_edit_%s", (C.byref(rec),)
+    if isinstance(edit, _edit.Edit) and edit.shape is None:
+        edit_kernel, edit_args = "clift_edit_%s", (C.byref(edit.record()),)
     else:
-        rec = prog.records()
-        edit_kernel, edit_args = "clift_edit_list_%s", (rec, len(prog))
+        edit_kernel, edit_args = prog.launch_family(rays.device)
 
     def density_fwd(ms, vd, sigma):
         call(edit_kernel % "density_fwd", C.byref(ms), *edit_args, C.byref(vd), ptr(rays), N, ptr(sigma), st)
@@ -1140,10 +1137,14 @@ def _edit_density_march(model, renderer, rays, edit, weight_thres):
 def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     """The reference's edit renders (renderer.py:303-623: forward_delete / _extract / _duplicate / _manipulate) for one resolved edit
     (``edit.Edit``): samples the kill rule names get sigma = 0, samples inside the destination box are looked up at the remapped position
-    with the turned view direction.  ``edit`` may also be an ``edit.EditProgram`` (or a sequence of ``Edit``): its edits are applied in
-    order in this one render -- every sample walks the list backwards (``EditProgram``) in ``clift_edit_list_density_fwd`` /
-    ``clift_edit_list_active``, which take the place of the two single-edit launches; a single ``Edit`` keeps those.  No jitter (the reference samples with perturb 0, is_train False), no activations kept, no backward, no
-    distortion-loss value.  Returns (dict of outputs, context) like ``render_forward``.
+    with the turned view direction.
+
+    ``edit`` may also be an ``edit.EditProgram`` (or a sequence of ``Edit``): its edits are applied in order in this one render.  Every
+    sample walks the list backwards (``EditProgram``) in the density_fwd / active entry points of the program's family
+    (``_edit_density_march``), which take the place of the two single-edit launches; a single ``Edit`` without a shape keeps those.
+
+    No jitter (the reference samples with perturb 0, is_train False), no activations kept, no backward, no distortion-loss value.
+    Returns (dict of outputs, context) like ``render_forward``.
 
       edit_density_fwd -> march_fwd -> scan / compact at ``weight_thres`` -> edit_active (xa, dirs) ->
       vm_products_points -> basis GEMM -> app_encode_points -> appearance layers;  xyz heads on xa;  composite.

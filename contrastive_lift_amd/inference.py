@@ -10,17 +10,32 @@ from . import _lib, engine
 from .hdbscan import DeviceHDBSCAN
 
 
+def _render_chunks(rays, chunk, per_chunk):
+    """The chunk loop of every ``render_rays*``: ``per_chunk(rays[i:i + chunk])`` -> a tuple of tensors, one row per ray, that the chunk's
+    pass no longer owns (a view of its ``ray_out`` is cloned by the caller); the tuples are concatenated output by output.  ``chunk`` of 0
+    or None renders all rays at once.  Whatever the pass kept beside its outputs (the context) is dropped before the next chunk starts."""
+    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
+    outs = [per_chunk(rays[i:i + chunk]) for i in range(0, rays.shape[0], chunk)]
+    return tuple(torch.cat(x, 0) for x in zip(*outs))
+
+
+def _render_outputs(o):
+    return o["rgb"], o["semantics"], o["instances"], o["depth"].clone()
+
+
+def _surface_outputs(s):
+    return s["depth_median"], s["hit"].to(torch.float32), s["normals"].contiguous()
+
+
+def _layer_outputs(o):
+    return o["layers"], o["opacity"].clone(), o["depth"].clone()
+
+
 @torch.no_grad()
 def render_rays(model, renderer, rays, chunk, white_bg=False):
     """Chunked renderer(model, rays[i:i+chunk], perturb, white_bg, is_train=False) (RP:114-120): returns
     rgb (P,3), semantics (P,C), instances (P,D), distance (P,)."""
-    outs = [[], [], [], []]
-    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
-    for i in range(0, rays.shape[0], chunk):
-        o, ctx = engine.render_forward(model, renderer, rays[i:i + chunk], None, bool(white_bg), grad_heads=())
-        outs[0].append(o["rgb"]); outs[1].append(o["semantics"]); outs[2].append(o["instances"]); outs[3].append(o["depth"].clone())
-        del ctx
-    return tuple(torch.cat(x, 0) for x in outs)
+    return _render_chunks(rays, chunk, lambda r: _render_outputs(engine.render_forward(model, renderer, r, None, bool(white_bg), grad_heads=())[0]))
 
 
 @torch.no_grad()
@@ -31,13 +46,7 @@ def render_rays_edit(model, renderer, rays, chunk, white_bg=False, edit=None, we
     frame into row-tiles over the ranks like a plain one."""
     if edit is None:
         raise ValueError("render_rays_edit: an edit is required")
-    outs = [[], [], [], []]
-    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
-    for i in range(0, rays.shape[0], chunk):
-        o, ctx = engine.edit_forward(model, renderer, rays[i:i + chunk], edit, bool(white_bg), weight_thres=weight_thres)
-        outs[0].append(o["rgb"]); outs[1].append(o["semantics"]); outs[2].append(o["instances"]); outs[3].append(o["depth"].clone())
-        del ctx
-    return tuple(torch.cat(x, 0) for x in outs)
+    return _render_chunks(rays, chunk, lambda r: _render_outputs(engine.edit_forward(model, renderer, r, edit, bool(white_bg), weight_thres=weight_thres)[0]))
 
 
 @torch.no_grad()
@@ -46,16 +55,11 @@ def render_rays_surface(model, renderer, rays, chunk, white_bg=False, q=0.5):
     rgb (P,3), semantics (P,C), instances (P,D), distance (P,), distance_median (P,), hit (P,) as float 0 / 1, normals (P,3) --
     the un-normalised sums of w n.  The first four are ``render_rays``' own.  It has the ``render_fn`` signature of ``render_rays_sharded``
     (bind ``q`` with functools.partial), which carries all seven over the ranks."""
-    outs = [[] for _ in range(7)]
-    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
-    for i in range(0, rays.shape[0], chunk):
-        o, ctx = engine.render_forward(model, renderer, rays[i:i + chunk], None, bool(white_bg), grad_heads=())
-        s = engine.surface_from_ctx(model, renderer, ctx, q)
-        for dst, x in zip(outs, (o["rgb"], o["semantics"], o["instances"], o["depth"].clone(), s["depth_median"], s["hit"].to(torch.float32),
-                                 s["normals"].contiguous())):
-            dst.append(x)
-        del ctx
-    return tuple(torch.cat(x, 0) for x in outs)
+    def per_chunk(r):
+        o, ctx = engine.render_forward(model, renderer, r, None, bool(white_bg), grad_heads=())
+        return _render_outputs(o) + _surface_outputs(engine.surface_from_ctx(model, renderer, ctx, q))
+
+    return _render_chunks(rays, chunk, per_chunk)
 
 
 @torch.no_grad()
@@ -66,16 +70,12 @@ def render_rays_edit_surface(model, renderer, rays, chunk, white_bg=False, edit=
     (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``."""
     if edit is None:
         raise ValueError("render_rays_edit_surface: an edit is required")
-    outs = [[] for _ in range(7)]
-    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
-    for i in range(0, rays.shape[0], chunk):
-        o, ctx = engine.edit_forward(model, renderer, rays[i:i + chunk], edit, bool(white_bg), weight_thres=weight_thres)
-        s = engine.edit_surface_from_ctx(model, renderer, ctx, q)
-        for dst, x in zip(outs, (o["rgb"], o["semantics"], o["instances"], o["depth"].clone(), s["depth_median"], s["hit"].to(torch.float32),
-                                 s["normals"].contiguous())):
-            dst.append(x)
-        del ctx
-    return tuple(torch.cat(x, 0) for x in outs)
+
+    def per_chunk(r):
+        o, ctx = engine.edit_forward(model, renderer, r, edit, bool(white_bg), weight_thres=weight_thres)
+        return _render_outputs(o) + _surface_outputs(engine.edit_surface_from_ctx(model, renderer, ctx, q))
+
+    return _render_chunks(rays, chunk, per_chunk)
 
 
 @torch.no_grad()
@@ -87,13 +87,7 @@ def render_rays_layers(model, renderer, rays, chunk, white_bg=False, table=None,
     ``render_rays_sharded``."""
     if table is None:
         raise ValueError("render_rays_layers: a slot table is required (layers.SlotTable)")
-    outs = [[], [], []]
-    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
-    for i in range(0, rays.shape[0], chunk):
-        o, ctx = engine.layers_forward(model, renderer, rays[i:i + chunk], table, alpha_thres=alpha_thres, use_delta=use_delta)
-        outs[0].append(o["layers"]); outs[1].append(o["opacity"].clone()); outs[2].append(o["depth"].clone())
-        del ctx
-    return tuple(torch.cat(x, 0) for x in outs)
+    return _render_chunks(rays, chunk, lambda r: _layer_outputs(engine.layers_forward(model, renderer, r, table, alpha_thres=alpha_thres, use_delta=use_delta)[0]))
 
 
 @torch.no_grad()
@@ -106,13 +100,8 @@ def render_rays_edit_layers(model, renderer, rays, chunk, white_bg=False, table=
         raise ValueError("render_rays_edit_layers: a slot table is required (layers.SlotTable)")
     if edit is None:
         raise ValueError("render_rays_edit_layers: an edit is required")
-    outs = [[], [], []]
-    chunk = int(chunk) if chunk and int(chunk) > 0 else rays.shape[0]
-    for i in range(0, rays.shape[0], chunk):
-        o, ctx = engine.edit_layers_forward(model, renderer, rays[i:i + chunk], edit, table, alpha_thres=alpha_thres, use_delta=use_delta)
-        outs[0].append(o["layers"]); outs[1].append(o["opacity"].clone()); outs[2].append(o["depth"].clone())
-        del ctx
-    return tuple(torch.cat(x, 0) for x in outs)
+    return _render_chunks(rays, chunk,
+                          lambda r: _layer_outputs(engine.edit_layers_forward(model, renderer, r, edit, table, alpha_thres=alpha_thres, use_delta=use_delta)[0]))
 
 
 def tile_bounds(n, world):

@@ -286,9 +286,8 @@ class TensoRFRenderer(nn.Module):
             return (sigma, torch.zeros(sigma.shape, dtype=torch.uint8, device=dev)) if return_state else sigma
         prog = ed.as_program(edit)
         state = torch.empty(sigma.shape, dtype=torch.uint8, device=dev) if return_state else None
-        # (a program one of whose edits follows a shape, edit.EditShape, goes through the shaped entry point: the same launch, the walk reading the lattices)
-        name, edits = ("clift_edit_shaped_dense_sigma", (prog.records(), prog.shapes(dev))) if prog.is_shaped else ("clift_edit_list_dense_sigma", (prog.records(),))
-        _lib.call(name, C.byref(vd), *edits, len(prog), f3(lo), f3(hi), f3(self.inv_box_extent_host),
+        kernel, program = prog.launch_family(dev)        # (a shaped program: the same launch, the walk reading the lattices)
+        _lib.call(kernel % "dense_sigma", C.byref(vd), *program, f3(lo), f3(hi), f3(self.inv_box_extent_host),
                   _lib.ptr(ticks[0]), _lib.ptr(ticks[1]), _lib.ptr(ticks[2]), n[0], n[1], n[2], float(tensorf.splus_density_shift),
                   _lib.ptr(sigma), _lib.ptr(state), _lib.stream())
         return (sigma, state) if return_state else sigma

@@ -136,6 +136,51 @@ def test_point_walk_with_some_shapes_and_with_none():
     assert int((edit.EditProgram([edit.delete(base[0].src)]).apply_to_points(dp)[2] != 0).sum()) >= 200
 
 
+@pytest.mark.parametrize("name", ["chain", "one move"])
+def test_shaped_names_without_shapes_are_the_list_names(scene, rays130, name):
+    """h_shapes = NULL through the raw ABI at the other three walk kernels: clift_edit_shaped_density_fwd, _active (on the act_idx of that
+    march) and _dense_sigma (the scene's lattice, upsample 1) write the bits of clift_edit_list_*; for the program of one move the two ray
+    kernels also those of the single-edit names clift_edit_density_fwd / clift_edit_active."""
+    from contrastive_lift_amd import _lib, edit, engine
+    _, m, r = scene
+    _, _, rays = rays130
+    prog = emc.program("chain")
+    assert len(prog) == 3 and prog[0].mode == edit.MANIPULATE
+    if name == "one move":
+        prog = edit.EditProgram([prog[0]])
+    recs, n_edits, st = prog.records(), len(prog), _lib.stream()
+    families = {"list": ("clift_edit_list_%s", (recs, n_edits)), "shaped": ("clift_edit_shaped_%s", (recs, None, n_edits))}
+    if n_edits == 1:
+        families["single"] = ("clift_edit_%s", (C.byref(recs[0]),))
+    ctx = engine.edit_forward(m, r, rays, prog, False)[1]
+    ms, N, M, act = ctx.ms, rays.shape[0], ctx.M, ctx.act_idx
+    assert M > 1000
+    views = m.named_views()
+    vd = engine.vm_struct(views, "density", engine.grid_res(views))
+    sigma, xa, dirs = {}, {}, {}
+    for fam, (kernel, program) in families.items():
+        sigma[fam] = torch.full_like(ctx.sigma, -7.5)
+        xa[fam], dirs[fam] = torch.full((M, 4), -7.5, device=DEV), torch.full((M, 4), -7.5, device=DEV)
+        _lib.call(kernel % "density_fwd", C.byref(ms), *program, C.byref(vd), _lib.ptr(rays), N, _lib.ptr(sigma[fam]), st)
+        _lib.call(kernel % "active", C.byref(ms), *program, _lib.ptr(rays), _lib.ptr(act), M, _lib.ptr(xa[fam]), _lib.ptr(dirs[fam]), st)
+    assert torch.equal(sigma["list"], ctx.sigma) and bool((xa["list"][:, :3] != -7.5).all())     # (the list names did run)
+    for fam in families:
+        assert torch.equal(sigma[fam], sigma["list"]) and torch.equal(xa[fam], xa["list"]) and torch.equal(dirs[fam], dirs["list"]), fam
+    n = [int(x) for x in r.grid_dim.tolist()]
+    ticks = [torch.linspace(0, 1, k).to(DEV) for k in n]
+    lo, hi = r.bbox_aabb_host
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    lat, lstate = {}, {}
+    for fam in ("list", "shaped"):
+        kernel, program = families[fam]
+        lat[fam], lstate[fam] = torch.full(tuple(n), -7.5, device=DEV), torch.full(tuple(n), 0x55, dtype=torch.uint8, device=DEV)
+        _lib.call(kernel % "dense_sigma", C.byref(vd), *program, f3(lo), f3(hi), f3(r.inv_box_extent_host), _lib.ptr(ticks[0]), _lib.ptr(ticks[1]),
+                  _lib.ptr(ticks[2]), n[0], n[1], n[2], float(m.splus_density_shift), _lib.ptr(lat[fam]), _lib.ptr(lstate[fam]), st)
+    want, want_state = r.get_dense_sigma(m, 1, edit=prog, return_state=True)
+    assert torch.equal(lat["list"], want) and torch.equal(lstate["list"], want_state) and int((want_state != 0).sum()) >= 20
+    assert torch.equal(lat["shaped"], lat["list"]) and torch.equal(lstate["shaped"], lstate["list"])
+
+
 def _bad_shaped_programs():
     """(what, records, shapes, n_edits, message): the program's own errors and the shape's.  A product of dimensions of 2^31 or more cannot be
     reached with dimensions of at most 1024 (1024^3 = 2^30): the library checks it, no input here can show it."""
