@@ -164,6 +164,7 @@ _SIGNATURES = {
     "clift_ray_surface": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P, _P], C.c_int),
     "clift_sample_slots": ([_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _L, _P, _P], C.c_int),
     "clift_ray_layers": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P], C.c_int),
+    "clift_ray_layer_colour": ([_P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _L, _P, _P, _P], C.c_int),
     "clift_edit_list_density_grad_points": ([_P, _I, _P, _P, _I, _L, _P, _P, _F, _P, _P, _P], C.c_int),
     "clift_edit_list_density_grad_active": ([_P, _P, _I, _P, _P, _P, _I, _P, _P], C.c_int),
     "clift_edit_shaped_density_fwd": ([_P, _P, _P, _I, _P, _P, _I, _P, _P], C.c_int),

@@ -4,6 +4,7 @@
 //                    nearest centroid (mode 0) or the first maximum of the row's slot scores (mode 1)
 //   k_ray_layers     one wave per ray: the ray's range of an alpha-list walked in order; per column (K instance slots and the rest column) a
 //                    transmittance of its own, the scene's weight, the expected distance and the distance of the first entry
+//   k_ray_layer_colour  the same walk with a colour per list row: per column its premultiplied colour and opacity when alone
 // Every operation is rounded on its own (no fmaf), so that an fp32 numpy loop restates both kernels to the bit.  No atomics, no LDS: every
 // output element is written once by one lane, the walks run in list order -- two runs give the same bits.
 #include "clift_dev.h"
@@ -161,4 +162,99 @@ extern "C" int clift_ray_layers(const clift_march_t* h_m, const float* rays, con
     default: k_ray_layers<4><<<grid, block, 0, st>>>(m, rays, jitter, N, alpha, w, ray_start, act_idx, M, slot, K, out); break;
     }
     return clift_check_launch("clift_ray_layers");
+}
+
+// ============================================================================ the colour of every layer of a ray
+// The walk of k_ray_layers -- the same columns, the same skipped entries, the same order -- with the colour of a list row in place of its
+// distance and weight: per column R, G, B += (Tc a) c and Tc *= 1 - a, every operation rounded on its own.  An entry without a colour (its
+// row of rgb_row outside [0, n_rgb)) still takes its share of the column's transmittance; its colour is never read.  The march record gives S
+// alone: no ray is loaded and no distance is formed.
+struct ColourAcc {
+    float Tc, R, G, B;
+};
+
+template <int Q>
+__global__ __launch_bounds__(256) void k_ray_layer_colour(int S, int N, const float* __restrict__ alpha, const int* __restrict__ ray_start,
+                                                           const int* __restrict__ act, int M, const int* __restrict__ slot, int K,
+                                                           const float* __restrict__ rgb, int ldc, long n_rgb,
+                                                           const int* __restrict__ rgb_row, float* __restrict__ out) {
+    const int r = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (r >= N) return;
+    const int l = lane_id();
+    ColourAcc acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = ColourAcc{1.f, 0.f, 0.f, 0.f};
+    const int j0 = min(max(ray_start[r], 0), M), j1 = min(max(ray_start[r + 1], 0), M);
+    const long first = (long)r * S;
+    for (int base = j0; base < j1; base += 64) {
+        const int j = base + l;
+        const bool in = j < j1;
+        const long sid = in ? (long)act[j] : -1L;
+        const long kl = sid - first;
+        const bool ok = in && sid >= 0 && kl >= 0 && kl < S;          // an entry of another ray or out of range: skipped, never followed
+        const int sl = ok ? slot[j] : -1;
+        const int col = (sl >= 0 && sl < K) ? sl : K;
+        const float a = ok ? alpha[sid] : 0.f;
+        const long row = ok ? (rgb_row ? (long)rgb_row[j] : (long)j) : -1L;
+        const bool has = row >= 0 && row < n_rgb;                     // no colour: rgb is not read
+        const float* cr = rgb + (size_t)(has ? row : 0) * (size_t)ldc;
+        const float cR = has ? cr[0] : 0.f, cG = has ? cr[1] : 0.f, cB = has ? cr[2] : 0.f;
+        unsigned long long todo = __ballot(ok);
+        const unsigned long long coloured = __ballot(has);
+        while (todo != 0ull) {                                       // scalar: the entries of this trip, in list order
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1ull;
+            const int c = __builtin_amdgcn_readlane(col, i);
+            const float ai = read_lane(a, i), ri = read_lane(cR, i), gi = read_lane(cG, i), bi = read_lane(cB, i);
+            const bool ci = (coloured >> i) & 1ull;
+            const int set = c >> 6;
+            if (l == (c & 63)) {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    if (set == q) {
+                        ColourAcc& A = acc[q];
+                        const float u = __fmul_rn(A.Tc, ai);
+                        if (ci) {
+                            A.R = __fadd_rn(A.R, __fmul_rn(u, ri));
+                            A.G = __fadd_rn(A.G, __fmul_rn(u, gi));
+                            A.B = __fadd_rn(A.B, __fmul_rn(u, bi));
+                        }
+                        A.Tc = __fmul_rn(A.Tc, __fsub_rn(1.f, ai));
+                    }
+                }
+            }
+        }
+    }
+    float* orow = out + (size_t)r * (size_t)(K + 1) * 4;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int c = l + 64 * q;
+        if (c <= K) *reinterpret_cast<float4*>(orow + (size_t)c * 4) = make_float4(acc[q].R, acc[q].G, acc[q].B, __fsub_rn(1.f, acc[q].Tc));
+    }
+}
+
+extern "C" int clift_ray_layer_colour(const clift_march_t* h_m, int N, const float* alpha, const int* ray_start, const int* act_idx, int M,
+                                      const int* slot, int K, const float* rgb, int ldc, long n_rgb, const int* rgb_row, float* out,
+                                      clift_stream_t s) {
+    CLIFT_REQUIRE(h_m != nullptr, "clift_ray_layer_colour: NULL march record");
+    CLIFT_REQUIRE(K >= 0 && K <= 255, "clift_ray_layer_colour: K must lie in [0, 255] (got %d)", K);
+    CLIFT_REQUIRE(h_m->n_samples >= 1, "clift_ray_layer_colour: the march has no samples");
+    CLIFT_REQUIRE(M >= 0, "clift_ray_layer_colour: negative M");
+    CLIFT_REQUIRE(ldc >= 3, "clift_ray_layer_colour: ldc must be >= 3 (got %d)", ldc);
+    CLIFT_REQUIRE(n_rgb >= 0, "clift_ray_layer_colour: negative n_rgb");
+    if (N <= 0) return 0;
+    CLIFT_REQUIRE((long)N * h_m->n_samples < 2147483647L, "clift_ray_layer_colour: N*S overflows int32 sample ids");
+    CLIFT_REQUIRE(alpha && ray_start && out, "clift_ray_layer_colour: NULL buffer");
+    CLIFT_REQUIRE(M == 0 || (act_idx && slot), "clift_ray_layer_colour: NULL act_idx / slot with M = %d", M);
+    CLIFT_REQUIRE(n_rgb == 0 || rgb != nullptr, "clift_ray_layer_colour: NULL rgb with n_rgb = %ld", n_rgb);
+    const int S = h_m->n_samples;
+    const dim3 grid(cdiv(N, 4)), block(256);
+    hipStream_t st = as_stream(s);
+    switch (K / 64) {          // sets of 64 columns that K + 1 columns need, less one
+    case 0: k_ray_layer_colour<1><<<grid, block, 0, st>>>(S, N, alpha, ray_start, act_idx, M, slot, K, rgb, ldc, n_rgb, rgb_row, out); break;
+    case 1: k_ray_layer_colour<2><<<grid, block, 0, st>>>(S, N, alpha, ray_start, act_idx, M, slot, K, rgb, ldc, n_rgb, rgb_row, out); break;
+    case 2: k_ray_layer_colour<3><<<grid, block, 0, st>>>(S, N, alpha, ray_start, act_idx, M, slot, K, rgb, ldc, n_rgb, rgb_row, out); break;
+    default: k_ray_layer_colour<4><<<grid, block, 0, st>>>(S, N, alpha, ray_start, act_idx, M, slot, K, rgb, ldc, n_rgb, rgb_row, out); break;
+    }
+    return clift_check_launch("clift_ray_layer_colour");
 }

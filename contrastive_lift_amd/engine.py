@@ -715,6 +715,8 @@ class RenderCtx:
         self.slots = self.layer_add = None   # layers_forward: the slot of every list row; with use_delta the world positions added to the features
         self.M_render = 0                    # layers_forward: the length of the march's own list (w > threshold), which its alpha-list replaced
         self.base_slots = self.origin = self.state = None  # edit_layers_forward: the slots under the base table, and which copy a row's content came through
+        self.layer_rgb = self.layer_rgb_row = self.layer_dirs = None       # colour layers: the colours (Mc, 3) of the coloured list rows, the row of each list row (M; -1: none), their view directions
+        self.layer_xa = None                 # edit_layers_forward with colour: the xa that clift_edit_list_active wrote beside the directions
 
 
 INT_MAX = 2 ** 31 - 1
@@ -1133,6 +1135,26 @@ def _edit_density_march(model, renderer, rays, edit, weight_thres):
     return ctx, edit_kernel, edit_args
 
 
+def _app_points_chain(model, views, params, F, dirs, ldd, M, keep):
+    """The point-wise appearance chain behind clift_vm_products_points: from the products ``F`` (M, 3 comps) and one view direction per row
+    (``dirs``, row pitch ``ldd`` >= 3) the un-fused front end (the fused one recomputes positions from the rays) -- the basis Linear in exact
+    fp32, clift_app_encode_points --, then render_forward's appearance layers with fp32-stored activations.  -> rgb_s (M, 3).  ``keep``
+    receives every temporary (the caller may be on a side stream)."""
+    dev = F.device
+    with _app_precision():
+        Wb = views["appearance_basis_mat.weight"]
+        nf, nc = Wb.shape[0], F.shape[1]
+        ldx, ldf = _pitch(params["app"][0][0]), (nf + 3) // 4 * 4
+        feat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
+        with exact_fp32():
+            gemm(M, nf, nc, F, nc, Wb, _pitch(Wb), feat, ldf)
+        X = torch.empty((M, ldx), dtype=torch.float32, device=dev)
+        call("clift_app_encode_points", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(dirs), ldd, M, ptr(X), ldx, stream())
+        H1, H2, rgb_s = _app_layers(M, X, params["app"], torch.float32, False, keep)
+        keep.extend([feat, X, H1, H2, F, dirs])
+    return rgb_s
+
+
 @torch.no_grad()
 def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
     """The reference's edit renders (renderer.py:303-623: forward_delete / _extract / _duplicate / _manipulate) for one resolved edit
@@ -1175,19 +1197,7 @@ def edit_forward(model, renderer, rays, edit, white_bg, weight_thres=0.0):
         call("clift_vm_products_points", C.byref(va), ptr(ctx.xa), 4, M, ptr(F), st)
 
         def app_chain(keep):
-            # the un-fused front end (the fused one recomputes positions from the rays), then render_forward's appearance layers with
-            # fp32-stored activations
-            with _app_precision():
-                Wb = views["appearance_basis_mat.weight"]
-                nf = Wb.shape[0]
-                ldx, ldf = _pitch(params["app"][0][0]), (nf + 3) // 4 * 4
-                feat = torch.empty((M, ldf), dtype=torch.float32, device=dev)
-                with exact_fp32():
-                    gemm(M, nf, nc, F, nc, Wb, _pitch(Wb), feat, ldf)
-                X = torch.empty((M, ldx), dtype=torch.float32, device=dev)
-                call("clift_app_encode_points", ptr(feat), ldf, nf, model.pe_feat, model.pe_view, ptr(dirs), 4, M, ptr(X), ldx, stream())
-                H1, H2, ctx.rgb_s = _app_layers(M, X, params["app"], torch.float32, False, keep)
-                keep.extend([feat, X, H1, H2, F, dirs])
+            ctx.rgb_s = _app_points_chain(model, views, params, F, dirs, 4, M, keep)
 
         br = Branches(model=model)
         br.run(0, app_chain)
@@ -1579,6 +1589,38 @@ def _sample_slots(ctx, renderer, table, E, use_delta):
     return slots
 
 
+def _layer_colour_check(who, colour, colour_rest):
+    if colour_rest and not colour:
+        raise ValueError(f"{who}: colour_rest needs colour=True (it says which rows are coloured, not whether)")
+
+
+def _layer_colour(model, views, ctx, K, colour_rest, dirs_of):
+    """The colour layers of a layer pass whose slots are known -> (N, K + 1, 4) rows [R, G, B, A], premultiplied.  Coloured
+    are the list rows whose column is below ``K`` -- with ``colour_rest`` every row: most listed samples of a real scene belong to stuff
+    classes, and the appearance chain is the expensive part.  ``dirs_of(rows)``: the view directions (Mc, 3) of the list rows ``rows`` (int64).
+    The count Mc reaches the host.  The context keeps layer_rgb (Mc, 3), layer_rgb_row (M; -1: not coloured) and layer_dirs (Mc, 3)."""
+    N, M, dev, st = ctx.N, ctx.M, ctx.rays.device, stream()
+    Mc = 0
+    if M > 0:
+        keep = torch.ones((M,), dtype=torch.bool, device=dev) if colour_rest else (ctx.slots >= 0) & (ctx.slots < K)
+        rows = torch.nonzero(keep).reshape(-1)
+        Mc = int(rows.shape[0])
+        ctx.layer_rgb_row = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        ctx.layer_rgb_row[rows] = torch.arange(Mc, dtype=torch.int32, device=dev)
+    ctx.layer_rgb = ctx.layer_dirs = None
+    if Mc > 0:
+        xc = ctx.xa[rows].contiguous()
+        ctx.layer_dirs = dirs_of(rows).contiguous()
+        va = vm_struct(views, "appearance", ctx.res)
+        F = torch.empty((Mc, 3 * va.comps), dtype=torch.float32, device=dev)
+        call("clift_vm_products_points", C.byref(va), ptr(xc), 4, Mc, ptr(F), st)
+        ctx.layer_rgb = _app_points_chain(model, views, _head_params(views), F, ctx.layer_dirs, 3, Mc, [])
+    out = torch.empty((N, K + 1, 4), dtype=torch.float32, device=dev)
+    call("clift_ray_layer_colour", C.byref(ctx.ms), N, ptr(ctx.alpha), ptr(ctx.ray_start), ptr(ctx.act_idx) if M > 0 else None, M,
+         ptr(ctx.slots) if M > 0 else None, K, ptr(ctx.layer_rgb), 3, Mc, ptr(ctx.layer_rgb_row) if M > 0 else None, ptr(out), st)
+    return out
+
+
 @torch.no_grad()
 def point_slots(model, renderer, points, table, use_delta=False, chunk=2 ** 20):
     """The slot under ``table`` (a ``layers.SlotTable``) of arbitrary WORLD points (n, 3) on the device -> (n,) int32, -1 where the point's
@@ -1603,7 +1645,7 @@ def point_slots(model, renderer, points, table, use_delta=False, chunk=2 ** 20):
 
 
 @torch.no_grad()
-def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, use_delta=False, cap=None):
+def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, use_delta=False, cap=None, colour=False, colour_rest=False):
     """Per ray and per instance slot of ``table`` (a ``layers.SlotTable``) what that instance covers ALONE, also behind what hides it: the march,
     its samples listed again by alpha > ``alpha_thres`` (default: renderer.raymarch_weight_thres) -- a sample behind an occluder has w ~ 0 and is
     in no render's list --, the semantic head and the fast instance net over that list (no appearance chain, no slow net, no compositing), one
@@ -1611,7 +1653,13 @@ def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, 
     Returns (dict(layers (N, K + 1, 4) rows [A, V, Z, zf], column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed), context).
     The context holds the alpha-list (ray_start, act_idx, M), xa, sem_s, inst_s (the fast half), slots and, with ``use_delta`` (the feature is
     output + world position; needs 3 feature columns), layer_add.  Refused: a sync-free pass (``cap``), a field without an instance head, a table
-    that does not fit the field.  This pass takes no edit: the layers of an edited scene are ``edit_layers_forward``'s."""
+    that does not fit the field.  This pass takes no edit: the layers of an edited scene are ``edit_layers_forward``'s.
+
+    ``colour``: the dict also holds colour (N, K + 1, 4), rows [R, G, B, A]: the premultiplied colour of every column rendered
+    alone, without a background, A with the bits of layers[..., 0].  The listed rows with a slot -- with ``colour_rest`` all of them -- go
+    through the point-wise appearance chain at xa with the ray's direction, and clift_ray_layer_colour composites them per column; the
+    context keeps layer_rgb, layer_rgb_row and layer_dirs.  Without ``colour`` nothing of this is launched."""
+    _layer_colour_check("layers_forward", colour, colour_rest)
     if cap is not None:
         raise _lib.CliftError("layers_forward: a sync-free (capped) pass is not supported: the length of the alpha-list has to reach the host")
     E = _layers_check("layers_forward", model, table, use_delta)
@@ -1632,12 +1680,17 @@ def layers_forward(model, renderer, rays, table, jitter=None, alpha_thres=None, 
     out = torch.empty((N, K + 1, 4), dtype=torch.float32, device=dev)
     call("clift_ray_layers", C.byref(ctx.ms), ptr(rays), ptr(jitter), N, ptr(ctx.alpha), ptr(ctx.w), ptr(ray_start), ptr(act_idx) if M > 0 else None,
          M, ptr(ctx.slots), K, ptr(out), st)
-    return dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M), ctx
+    res = dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M)
+    if colour:
+        # the direction the render's own appearance encoding reads for a sample: its ray's
+        res["colour"] = _layer_colour(model, views, ctx, K, colour_rest,
+                                      lambda rows: rays[torch.div(act_idx[rows].long(), ctx.S, rounding_mode="floor"), 3:6])
+    return res, ctx
 
 
 # ----------------------------------------------------------------------------- amodal instance layers of an edited scene
 @torch.no_grad()
-def edit_layers_forward(model, renderer, rays, edit, table, alpha_thres=None, use_delta=False):
+def edit_layers_forward(model, renderer, rays, edit, table, alpha_thres=None, use_delta=False, colour=False, colour_rest=False):
     """``layers_forward`` of the scene ``edit`` describes (whatever ``edit.as_program`` takes), with a column of its own for every copy:
     ``table`` (the scene's ``layers.SlotTable``) is extended by ``table.for_program`` to K + c slots, c the DUPLICATE edits of the program.
 
@@ -1652,7 +1705,12 @@ def edit_layers_forward(model, renderer, rays, edit, table, alpha_thres=None, us
     context); the context holds the alpha-list, xa, sem_s, inst_s, slots (retargeted), base_slots, origin, state, edit_program and edited =
     True.  The march always goes through the list kernel: a single ``Edit`` is walked as a program of one (clift_edit_list_density_fwd, whose
     walk is that edit op for op), where ``edit_forward`` keeps the single-edit launches for it.  Refused: a head on its own VM grid (as
-    ``edit_forward``), and what ``layers_forward`` refuses."""
+    ``edit_forward``), and what ``layers_forward`` refuses.
+
+    ``colour`` / ``colour_rest``: as in ``layers_forward``, with K + c + 1 columns -- a copy has a colour layer of its own.  One more launch
+    of clift_edit_list_active over the alpha-list gives the turned view directions (its xa, kept as layer_xa, has the bits of the origin
+    kernel's); the rows whose retargeted column is below K + c are coloured at xa with those directions."""
+    _layer_colour_check("edit_layers_forward", colour, colour_rest)
     if model.semantic_plane is not None or model.instance_plane is not None:
         raise NotImplementedError("edit_layers_forward: a semantic / instance head on its own VM grid is not supported (xyz MLP heads only)")
     E = _layers_check("edit_layers_forward", model, table, use_delta)
@@ -1680,7 +1738,15 @@ def edit_layers_forward(model, renderer, rays, edit, table, alpha_thres=None, us
     out = torch.empty((N, ext.K + 1, 4), dtype=torch.float32, device=dev)
     call("clift_ray_layers", C.byref(ctx.ms), ptr(rays), None, N, ptr(ctx.alpha), ptr(ctx.w), ptr(ctx.ray_start), ptr(ctx.act_idx) if M > 0 else None,
          M, ptr(ctx.slots), ext.K, ptr(out), st)
-    return dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M, table=ext), ctx
+    res = dict(layers=out, opacity=ctx.ray_out[:, 0], depth=ctx.ray_out[:, 1], n_listed=M, table=ext)
+    if colour:
+        dirs = None
+        if M > 0:
+            ctx.layer_xa = torch.empty((M, 4), dtype=torch.float32, device=dev)
+            dirs = torch.empty((M, 4), dtype=torch.float32, device=dev)
+            call("clift_edit_list_active", C.byref(ctx.ms), prog.records(), len(prog), ptr(rays), ptr(ctx.act_idx), M, ptr(ctx.layer_xa), ptr(dirs), st)
+        res["colour"] = _layer_colour(model, views, ctx, ext.K, colour_rest, lambda rows: dirs[rows, :3])
+    return res, ctx
 
 
 # ----------------------------------------------------------------------------- surface outputs of an edited scene

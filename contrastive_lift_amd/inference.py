@@ -28,7 +28,8 @@ def _surface_outputs(s):
 
 
 def _layer_outputs(o):
-    return o["layers"], o["opacity"].clone(), o["depth"].clone()
+    """layers, opacity, depth -- and the colour layers behind them where the pass formed them."""
+    return (o["layers"], o["opacity"].clone(), o["depth"].clone()) + ((o["colour"],) if "colour" in o else ())
 
 
 @torch.no_grad()
@@ -79,29 +80,34 @@ def render_rays_edit_surface(model, renderer, rays, chunk, white_bg=False, edit=
 
 
 @torch.no_grad()
-def render_rays_layers(model, renderer, rays, chunk, white_bg=False, table=None, alpha_thres=None, use_delta=False):
+def render_rays_layers(model, renderer, rays, chunk, white_bg=False, table=None, alpha_thres=None, use_delta=False, colour=False, colour_rest=False):
     """Chunked ``engine.layers_forward``: the amodal instance layers of the rays under the slot table ``table``
     (``layers.SlotTable``).  Returns layers (P, K + 1, 4) rows [A, V, Z, zf], opacity (P,), distance (P,) -- the last two of the whole scene, as
     ``render_rays`` gives them.  A ray's layers depend on that ray alone, so the chunking changes no bit.  ``white_bg`` is accepted and unused
     (no colour is formed): with ``table``, ``alpha_thres`` and ``use_delta`` bound (functools.partial) it has the ``render_fn`` signature of
-    ``render_rays_sharded``."""
+    ``render_rays_sharded``.  With ``colour`` a fourth output follows: colour (P, K + 1, 4) rows [R, G, B, A], premultiplied, without a
+    background (``colour_rest``: the rest column is coloured too)."""
     if table is None:
         raise ValueError("render_rays_layers: a slot table is required (layers.SlotTable)")
-    return _render_chunks(rays, chunk, lambda r: _layer_outputs(engine.layers_forward(model, renderer, r, table, alpha_thres=alpha_thres, use_delta=use_delta)[0]))
+    return _render_chunks(rays, chunk, lambda r: _layer_outputs(engine.layers_forward(model, renderer, r, table, alpha_thres=alpha_thres, use_delta=use_delta,
+                                                                                      colour=colour, colour_rest=colour_rest)[0]))
 
 
 @torch.no_grad()
-def render_rays_edit_layers(model, renderer, rays, chunk, white_bg=False, table=None, edit=None, alpha_thres=None, use_delta=False):
+def render_rays_edit_layers(model, renderer, rays, chunk, white_bg=False, table=None, edit=None, alpha_thres=None, use_delta=False, colour=False,
+                            colour_rest=False):
     """Chunked ``engine.edit_layers_forward``: the amodal instance layers of the scene ``edit`` describes, under the slot table
     ``table`` extended by one column per copy (``table.for_program(edit)`` names them).  Returns layers (P, K + c + 1, 4), opacity (P,),
     distance (P,) like ``render_rays_layers``; a ray's layers depend on that ray alone, so the chunking changes no bit.  With ``table``,
-    ``edit``, ``alpha_thres`` and ``use_delta`` bound (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``."""
+    ``edit``, ``alpha_thres`` and ``use_delta`` bound (functools.partial) it has the ``render_fn`` signature of ``render_rays_sharded``.
+    With ``colour`` a fourth output follows, colour (P, K + c + 1, 4), as in ``render_rays_layers``."""
     if table is None:
         raise ValueError("render_rays_edit_layers: a slot table is required (layers.SlotTable)")
     if edit is None:
         raise ValueError("render_rays_edit_layers: an edit is required")
     return _render_chunks(rays, chunk,
-                          lambda r: _layer_outputs(engine.edit_layers_forward(model, renderer, r, edit, table, alpha_thres=alpha_thres, use_delta=use_delta)[0]))
+                          lambda r: _layer_outputs(engine.edit_layers_forward(model, renderer, r, edit, table, alpha_thres=alpha_thres, use_delta=use_delta,
+                                                                              colour=colour, colour_rest=colour_rest)[0]))
 
 
 def tile_bounds(n, world):

@@ -9,6 +9,9 @@ when alone, the distance of its first listed sample.  Columns ``0 .. K - 1`` are
 Layers of an EDITED scene (``engine.edit_layers_forward``) have ``c`` more instance columns, one per copy of the edit program:
 ``SlotTable.for_program`` numbers them ``K .. K + c - 1`` behind the table's own slots, ``retarget`` sends a listed sample that a copy
 brought to that copy's column, and ``compare`` says per slot what an edit hid, revealed or removed.
+
+COLOUR layers (``colour=True`` on either pass) are ``(N, K + 1, 4)`` fp32 rows ``[R, G, B, A]`` over the same columns: the
+premultiplied colour of every column rendered alone, without a background; ``unpremultiply`` and ``over`` turn them into what an image wants.
 """
 import numpy as np
 import torch
@@ -154,6 +157,33 @@ def front_order(layers, level=0.5):
     idx = torch.sort(key, dim=1, stable=True)[1]
     order = torch.where(torch.gather(on, 1, idx), idx, torch.full_like(idx, -1))
     return order, on.sum(1)
+
+
+def _check_colour(colour):
+    if colour.shape[-1] != 4:
+        raise ValueError(f"a colour layer array ends in [R, G, B, A], got {tuple(colour.shape)}")
+
+
+@torch.no_grad()
+def unpremultiply(colour, eps=1e-6):
+    """Colour layers (..., 4) rows [R, G, B, A] with premultiplied colours (``engine.layers_forward(colour=True)``) -> the same
+    shape with RGB / A where A > ``eps`` and 0 elsewhere; A is kept.  What an RGBA image file wants."""
+    colour = torch.as_tensor(colour)
+    _check_colour(colour)
+    A = colour[..., 3:4]
+    on = A > eps
+    rgb = torch.where(on, colour[..., :3] / torch.where(on, A, torch.ones_like(A)), torch.zeros_like(colour[..., :3]))
+    return torch.cat([rgb, A], -1)
+
+
+@torch.no_grad()
+def over(colour, background):
+    """Premultiplied colour layers (..., 4) over ``background`` (a scalar, (3,) or anything that broadcasts against (..., 3)) -> (..., 3):
+    RGB + (1 - A) background."""
+    colour = torch.as_tensor(colour)
+    _check_colour(colour)
+    background = torch.as_tensor(background, dtype=colour.dtype, device=colour.device)
+    return colour[..., :3] + (1.0 - colour[..., 3:4]) * background
 
 
 @torch.no_grad()

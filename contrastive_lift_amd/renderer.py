@@ -184,17 +184,19 @@ class TensoRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------ amodal instance layers
     @torch.no_grad()
-    def forward_layers(self, tensorf, rays, table, alpha_thres=None, use_delta=False):
+    def forward_layers(self, tensorf, rays, table, alpha_thres=None, use_delta=False, colour=False, colour_rest=False):
         """What every instance slot of ``table`` (``layers.SlotTable``) covers along the rays, also behind what hides it:
         dict(layers (N, K + 1, 4) rows [A amodal opacity, V visible weight, Z amodal expected distance (un-normalised), zf first listed distance],
-        column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed).  No jitter (is_train False), no gradient."""
-        return engine.layers_forward(tensorf, self, rays, table, None, alpha_thres, use_delta)[0]
+        column K the rest; opacity (N,), depth (N,) of the whole scene; n_listed).  With ``colour`` also colour (N, K + 1, 4) rows [R, G, B, A]:
+        every column's premultiplied colour when rendered alone (``colour_rest``: the rest column too).  No jitter (is_train
+        False), no gradient."""
+        return engine.layers_forward(tensorf, self, rays, table, None, alpha_thres, use_delta, colour=colour, colour_rest=colour_rest)[0]
 
-    def forward_edit_layers(self, tensorf, rays, edit, table, alpha_thres=None, use_delta=False):
+    def forward_edit_layers(self, tensorf, rays, edit, table, alpha_thres=None, use_delta=False, colour=False, colour_rest=False):
         """``forward_layers`` of the scene ``edit`` describes (an ``edit.Edit``, an ``edit.EditProgram`` or a sequence of edits): the same dict
         with ``layers`` (N, K + c + 1, 4), one more instance column per copy of the program, and ``table``, the slot table extended by
-        those columns (engine.edit_layers_forward).  No jitter, no gradient."""
-        return engine.edit_layers_forward(tensorf, self, rays, edit, table, alpha_thres, use_delta)[0]
+        those columns (engine.edit_layers_forward), and with ``colour`` the colour layers of all of them.  No jitter, no gradient."""
+        return engine.edit_layers_forward(tensorf, self, rays, edit, table, alpha_thres, use_delta, colour=colour, colour_rest=colour_rest)[0]
 
     # ------------------------------------------------------------------ scene edits (renderer.py:303-623)
     def _forward_edit(self, tensorf, rays, white_bg, resolved):

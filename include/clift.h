@@ -931,6 +931,28 @@ int clift_sample_slots(const float* sem, int lds, int C, const float* feat, int 
 int clift_ray_layers(const clift_march_t* h_m, const float* rays, const float* jitter, int N, const float* alpha, const float* w,
                      const int* ray_start, const int* act_idx, int M, const int* slot, int K, float* out /* (N, K+1, 4) */, clift_stream_t s);
 
+/* ---- amodal colour layers (a further ABI 27 addition; csrc/layers.hip): the colour of every column of clift_ray_layers when
+ * rendered alone, from one colour per list row.
+ *
+ * clift_ray_layer_colour: out (N, K + 1, 4) fp32 rows [R, G, B, A], column K the rest.  alpha (N, S) as the march wrote it (S = h_m->n_samples,
+ *   the only field of the record that is read); ray_start, act_idx, M, slot, K exactly what clift_ray_layers takes, with its column rule (a
+ *   slot in [0, K) is that column, anything else column K) and its skip rule (an entry with k = act_idx[j] - r S outside [0, S) is skipped,
+ *   never followed; ray_start is clamped to [0, M]).  rgb (n_rgb, ldc >= 3) fp32 holds one row of colours per coloured list row; rgb_row (M)
+ *   int32 names the row of rgb that belongs to list row j, NULL means j itself.  An entry whose rgb_row lies outside [0, n_rgb) takes part in
+ *   the transmittance of its column but adds no colour, and rgb is not read for it.  Per entry of column c in list order, from Tc = 1,
+ *   R = G = B = 0, each operation ONE separately rounded fp32 operation (no fma):
+ *       u  = Tc * a
+ *       R  = R + (u * r);  G = G + (u * g);  B = B + (u * b)        (a coloured entry only)
+ *       Tc = Tc * (1 - a)
+ *   and A = 1 - Tc: the colour is premultiplied and knows no background; A has the bits of column 0 of clift_ray_layers on the same inputs.
+ *   One wave per ray, every (ray, column) written once as one float4, no atomics, no LDS: two runs give the same bits.  M = 0 (act_idx, slot,
+ *   rgb_row and rgb may be NULL) writes zeros.
+ *   Errors: a NULL record, K < 0, K > 255, S < 1, M < 0, ldc < 3, n_rgb < 0, N S >= 2^31 - 1, NULL alpha / ray_start / out, NULL act_idx / slot
+ *   with M > 0, NULL rgb with n_rgb > 0.  N <= 0 returns 0 without a launch. */
+int clift_ray_layer_colour(const clift_march_t* h_m, int N, const float* alpha, const int* ray_start, const int* act_idx, int M,
+                           const int* slot, int K, const float* rgb, int ldc, long n_rgb, const int* rgb_row, float* out /* (N, K+1, 4) */,
+                           clift_stream_t s);
+
 /* ---- surface outputs of an EDITED scene (a further ABI 27 addition; csrc/edit.hip): the gradient of the raw density of the
  * scene an edit program describes.  The walk of clift_edit_list_points remaps a world point p h times, by the edits i_1 .. i_h in walk order,
  * and ends at p' = J p + b with J = M_{i_h} ... M_{i_1} (the identity for h = 0; formed in fp32, every multiply and add rounded separately).

@@ -4,7 +4,7 @@
     python inference/edit_scene.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt --bboxes bboxes.pkl --instance ID
                                    --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz] [--pad 0.0]
                                    [--render_trajectory] [--image_dim H W] [--weight_thres 0] [--save_surface [--surface_quantile 0.5]]
-                                   [--save_layers --cached_centroids_path C [--layers_level 0.5]]
+                                   [--save_layers --cached_centroids_path C [--layers_level 0.5] [--layers_colour [--layers_colour_rest]]]
                                    [--follow_shape --cached_centroids_path C [--shape_grid 32] [--shape_grow 1] [--shape_alpha 0.5]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
@@ -22,6 +22,8 @@ rendered as row-tiles over the ranks.  Writes ``rgb/*.png``, ``pred_semantics/*.
 one more slot per copy of the program (slot_class -1, slot_index = the copy's 0-based position in the program), and
 ``layers/<frame>_change.json``: per slot what the edit hid, revealed or removed (``layers.compare`` of the unedited and the edited frame,
 one more plain layer pass per frame).  The slots come from ``--cached_centroids_path`` (a linear-assignment model needs none).
+``--layers_colour [--layers_colour_rest]`` adds the colour layers of the edited scene as ``render_panopli.py`` does for a
+plain one: ``colour`` in the npz and ``vis_amodal_rgb/<frame>/slot_<k>.png``, the copy's slot included.
 
 ``--script FILE.json`` applies up to 8 edits in ONE render (``edit.EditProgram``), in file order.  The file holds a list of
 ``{"instance": id, "op": "delete|extract|copy|move", "translate": [x, y, z], "rotate_deg": [rx, ry, rz], "pad": p, "at": "moved"}``;
@@ -178,7 +180,10 @@ SHAPE_WITH_SURFACE_OR_LAYERS = ("--follow_shape (or a script entry with \"shape\
 
 
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
-                          save_surface=False, surface_quantile=0.5, save_layers=False, cached_centroids_path=None, layers_level=0.5):
+                          save_surface=False, surface_quantile=0.5, save_layers=False, cached_centroids_path=None, layers_level=0.5,
+                          layers_colour=False, layers_colour_rest=False):
+    if (layers_colour or layers_colour_rest) and not save_layers:
+        raise ValueError("layers_colour needs save_layers")
     out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}")
     device, rank = rp.distributed_device(device)
     scene, model, renderer = rp.load_for_inference(config, device)
@@ -191,7 +196,8 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
         table = rp.layers_table(config, scene, cached_centroids_path)
         table_edit = table.for_program(edit)
         layers_fn = functools.partial(inf.render_rays_layers, table=table, use_delta=bool(config.use_delta))
-        edit_layers_fn = functools.partial(inf.render_rays_edit_layers, table=table, edit=edit, use_delta=bool(config.use_delta))
+        edit_layers_fn = functools.partial(inf.render_rays_edit_layers, table=table, edit=edit, use_delta=bool(config.use_delta),
+                                           colour=bool(layers_colour), colour_rest=bool(layers_colour_rest))
     if save_surface:
         render_fn = functools.partial(inf.render_rays_edit_surface, edit=edit, weight_thres=float(weight_thres), q=float(surface_quantile))
     else:
@@ -204,7 +210,7 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
             p_rgb, p_sem, _, p_dist, *p_surface = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg,
                                                                           render_fn=render_fn)
             if save_layers:         # every rank renders its tiles of the two layer passes (each ends in a collective); rank 0 writes
-                lay_after = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=edit_layers_fn)[0]
+                lay_after, _, _, *lay_colour = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=edit_layers_fn)
                 lay_before = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=layers_fn)[0]
             if rank != 0:
                 continue
@@ -217,8 +223,8 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
                 rp.write_surface_frame(out, name, inf.distance_to_depth(K_frame, p_dmed.view(H, W)).reshape(H, W), (p_hit > 0.5).reshape(H, W),
                                        p_nrm.reshape(H, W, 3))
             if save_layers:
-                write_layers(out, name, lay_before, lay_after, table, table_edit, H, W, p_rgb, layers_level)
-                del lay_before, lay_after
+                write_layers(out, name, lay_before, lay_after, table, table_edit, H, W, p_rgb, layers_level, colour=lay_colour[0] if lay_colour else None)
+                del lay_before, lay_after, lay_colour
     return out
 
 
@@ -235,15 +241,16 @@ def change_summary(frame_name, before, after, table, table_edit, level):
                             **{k: int(col[k][i]) for k in keys}) for i in present])
 
 
-def write_layers(out, name, before, after, table, table_edit, H, W, p_rgb, level):
+def write_layers(out, name, before, after, table, table_edit, H, W, p_rgb, level, colour=None):
     """The files of ``--save_layers`` for one frame, from the layers of the unedited (``before``) and the edited (``after``) frame: the
-    edited scene's written like ``render_panopli.py --save_layers`` writes a plain one, and ``layers/<frame>_change.json``."""
-    rp.write_layers_frame(out, name, after, table_edit, H, W, p_rgb, level)
+    edited scene's written like ``render_panopli.py --save_layers`` writes a plain one (with ``colour``, the edited scene's colour layers,
+    like ``--layers_colour``: a copy has a slot and so an image of its own), and ``layers/<frame>_change.json``."""
+    rp.write_layers_frame(out, name, after, table_edit, H, W, p_rgb, level, **({} if colour is None else {"colour": colour}))
     with open(out / "layers" / f"{name}_change.json", "w") as f:
         json.dump(change_summary(name, before, after, table, table_edit, level), f, indent=1)
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--ckpt_path", type=str, required=True)
     ap.add_argument("--bboxes", type=str, required=True, help="bboxes.pkl of inference/fit_bboxes.py")
@@ -270,14 +277,26 @@ def main(argv=None):
     ap.add_argument("--cached_centroids_path", type=str, default=None,
                     help="--save_layers: all_centroids.pkl of inference/extract_train_centroids.py (not needed for a linear_assignment model)")
     ap.add_argument("--layers_level", type=float, default=0.5, help="the opacity above which --save_layers counts a pixel into a mask")
+    rp.add_layers_colour_arguments(ap)
     add_shape_arguments(ap)
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    rp.check_layers_colour_arguments(ap, args)
     if args.follow_shape and (args.save_surface or args.save_layers):
         raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if args.script is not None and (args.instance is not None or args.op is not None):
         ap.error("--script holds the edits: give it without --instance / --op")
     if args.script is None and (args.instance is None or args.op is None):
         ap.error("--instance and --op are required without --script")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
     cfg.subsample_frames = 1
@@ -308,7 +327,8 @@ def main(argv=None):
         the_edit = the_edit(None, None, None)
     print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
                                 save_surface=args.save_surface, surface_quantile=args.surface_quantile, save_layers=args.save_layers,
-                                cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level))
+                                cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level,
+                                layers_colour=args.layers_colour, layers_colour_rest=args.layers_colour_rest))
 
 
 if __name__ == "__main__":

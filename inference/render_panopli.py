@@ -19,7 +19,8 @@ normals to ``pointcloud.pkl``.
 
 Amodal instance layers (a pass of its own per frame, only when asked for): ``--save_layers [--layers_level 0.5]`` writes per
 frame ``layers/<frame>.npz`` and ``.json`` -- what every instance covers also behind the things in front of it, what of it is visible and
-where its first sample lies -- and ``vis_amodal/<frame>.png``.  It needs ``--cached_centroids_path`` (the centroids are numbered once for the
+where its first sample lies -- and ``vis_amodal/<frame>.png``; with ``--layers_colour [--layers_colour_rest]`` also the colour of every
+instance behind its occluders: ``colour`` in the npz and ``vis_amodal_rgb/<frame>/slot_<k>.png``, one RGBA image per slot.  It needs ``--cached_centroids_path`` (the centroids are numbered once for the
 scene) or a linear_assignment model.
 """
 import argparse
@@ -150,12 +151,15 @@ def layers_table(config, scene, cached_centroids_path):
     raise ValueError("--save_layers needs --cached_centroids_path (or a linear_assignment model): the layers are kept per centroid")
 
 
-def write_layers_frame(out, frame_name, layers, table, H, W, rgb, level=0.5):
+def write_layers_frame(out, frame_name, layers, table, H, W, rgb, level=0.5, colour=None):
     """The files of ``--save_layers`` for one frame, from its layers (H W, K + 1, 4) and rendered colours (H W, 3), tensors on any device.
     ``layers/<frame>.npz``: slots (n,) the slots with an amodal pixel (A > level) in this frame, slot_class (n,), and amodal = A, visible = V,
     front = zf, the distance at which the slot's first sample lies, each (n, H, W) float16.  ``layers/<frame>.json``: level and per such slot
     its class, centroid index, amodal and visible pixel counts, occlusion rate and mean amodal distance (layers.summarise).
-    ``vis_amodal/<frame>.png``: the outline of every amodal mask, in the slot's colour, over the rendered colours."""
+    ``vis_amodal/<frame>.png``: the outline of every amodal mask, in the slot's colour, over the rendered colours.
+    With ``colour`` (H W, K + 1, 4), the premultiplied colour layers of ``--layers_colour``: the npz also holds colour
+    (n, H, W, 4) uint8, un-premultiplied RGB plus A, and ``vis_amodal_rgb/<frame>/slot_<k>.png`` is that RGBA image of slot k -- the
+    instance with nothing in front of it."""
     import json
     from contrastive_lift_amd import layers as ly
     for d in ("layers", "vis_amodal"):
@@ -164,9 +168,16 @@ def write_layers_frame(out, frame_name, layers, table, H, W, rgb, level=0.5):
     present = torch.nonzero(s["amodal_pixels"] > 0).reshape(-1)
     sel = layers[:, present].permute(1, 0, 2).reshape(present.shape[0], H, W, 4).cpu()
     slots = present.cpu().numpy().astype(np.int32)
+    extra = {}
+    if colour is not None:
+        rgba = ly.unpremultiply(colour[:, present].permute(1, 0, 2).reshape(present.shape[0], H, W, 4)).clamp(0, 1)
+        extra["colour"] = (rgba * 255).round().to(torch.uint8).cpu().numpy()
+        (out / "vis_amodal_rgb" / str(frame_name)).mkdir(exist_ok=True, parents=True)
+        for i, img in zip(slots, extra["colour"]):
+            Image.fromarray(np.ascontiguousarray(img)).save(out / "vis_amodal_rgb" / str(frame_name) / f"slot_{int(i)}.png")
     np.savez(out / "layers" / f"{frame_name}.npz", slots=slots, slot_class=table.slot_class[slots].astype(np.int32),
              amodal=sel[..., 0].numpy().astype(np.float16), visible=sel[..., 1].numpy().astype(np.float16),
-             front=sel[..., 3].numpy().astype(np.float16))
+             front=sel[..., 3].numpy().astype(np.float16), **extra)
     col = {k: v.cpu().numpy() for k, v in s.items()}
     summary = dict(frame=str(frame_name), level=float(level), n_slots=int(table.K),
                    slots=[dict(slot=int(i), slot_class=int(col["slot_class"][i]), slot_index=int(col["slot_index"][i]),
@@ -187,7 +198,9 @@ def write_layers_frame(out, frame_name, layers, table, H, W, rgb, level=0.5):
 def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth=0.15, use_dbscan=False, segmentwise=False,
                               cached_centroids_path=None, device="cuda:0", use_silverman=False, cluster_size=500,
                               meanshift="sklearn", save_pointcloud=False, hdbscan="sklearn", save_surface=False, pointcloud_depth="expected",
-                              save_layers=False, layers_level=0.5):
+                              save_layers=False, layers_level=0.5, layers_colour=False, layers_colour_rest=False):
+    if (layers_colour or layers_colour_rest) and not save_layers:
+        raise ValueError("layers_colour needs save_layers")
     if pointcloud_depth not in ("expected", "median"):
         raise ValueError(f"pointcloud_depth must be 'expected' or 'median', got {pointcloud_depth!r}")
     median_cloud = bool(save_pointcloud) and pointcloud_depth == "median"
@@ -215,11 +228,12 @@ def render_panopli_checkpoint(config, trajectory_name, test_only=True, bandwidth
                 p_rgb, p_sem, p_inst, p_dist = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg)
             depths.append(inf.distance_to_depth(K_frame, p_dist.view(H, W)))
             if save_layers:         # a pass of its own over the frame; written at once: a frame's layers are large
-                fn = functools.partial(inf.render_rays_layers, table=table, use_delta=bool(config.use_delta))
-                lay = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=fn)[0]
+                fn = functools.partial(inf.render_rays_layers, table=table, use_delta=bool(config.use_delta), colour=bool(layers_colour),
+                                       colour_rest=bool(layers_colour_rest))
+                lay, _, _, *lay_colour = inf.render_rays_sharded(model, renderer, rays, int(config.chunk), scene.white_bg, render_fn=fn)
                 if rank == 0:
-                    write_layers_frame(out, name, lay, table, H, W, p_rgb, layers_level)
-                del lay
+                    write_layers_frame(out, name, lay, table, H, W, p_rgb, layers_level, colour=lay_colour[0] if lay_colour else None)
+                del lay, lay_colour
             if save_pointcloud:
                 # (use_delta below keeps the expected distance for the instance features: only the saved points change)
                 points.append(points3d.backproject(rays, p_dmed if median_cloud else p_dist).float().cpu())
@@ -312,11 +326,36 @@ def build_parser():
                     help="also write layers/<frame>.npz and .json (amodal opacity, visible weight and front distance of every instance slot, and "
                          "their summary) and vis_amodal/<frame>.png; needs --cached_centroids_path or a linear_assignment model")
     ap.add_argument("--layers_level", type=float, default=0.5, help="the opacity above which --save_layers counts a pixel into a mask")
+    add_layers_colour_arguments(ap)
     return ap
 
 
+def add_layers_colour_arguments(ap):
+    """The colour-layer flags of ``--save_layers`` (inference/edit_scene.py has them too)."""
+    ap.add_argument("--layers_colour", action="store_true",
+                    help="--save_layers: also the colour of every instance behind its occluders (one more appearance pass over the listed samples "
+                         "that have a slot): layers/<frame>.npz gains colour (n, H, W, 4) uint8 and vis_amodal_rgb/<frame>/slot_<k>.png is written, "
+                         "an RGBA image per slot")
+    ap.add_argument("--layers_colour_rest", action="store_true",
+                    help="--layers_colour: colour every listed sample, the rest column's (stuff, unassigned) too -- much more appearance work")
+
+
+def check_layers_colour_arguments(ap, args):
+    if args.layers_colour and not args.save_layers:
+        ap.error("--layers_colour needs --save_layers")
+    if args.layers_colour_rest and not args.layers_colour:
+        ap.error("--layers_colour_rest needs --layers_colour")
+
+
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    check_layers_colour_arguments(ap, args)
+    return args
+
+
 if __name__ == "__main__":
-    args = build_parser().parse_args()
+    args = parse_args()
     cfg = load_run_config(Path(args.ckpt_path).parents[1] / "config.yaml")
     cfg.resume = args.ckpt_path
     cfg.subsample_frames = args.subsample
@@ -327,4 +366,5 @@ if __name__ == "__main__":
                                     cluster_size=args.cluster_size, meanshift=args.meanshift, hdbscan=args.hdbscan,
                                     save_pointcloud=args.save_pointcloud, save_surface=args.save_surface,
                                     pointcloud_depth=args.pointcloud_depth, save_layers=args.save_layers,
-                                    layers_level=args.layers_level))
+                                    layers_level=args.layers_level, layers_colour=args.layers_colour,
+                                    layers_colour_rest=args.layers_colour_rest))
