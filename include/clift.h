@@ -863,6 +863,32 @@ int clift_iso_faces(const float* vol, int n0, int n1, int n2, float level, const
  * other than 6 / 14 / 26, a NULL buffer. */
 int clift_cc_label(const int* key, int n0, int n1, int n2, int connectivity, int* root, clift_stream_t s);
 
+/* ---- relations of a keyed lattice (a further ABI 27 addition; csrc/relations.hip): per key its extent, per ordered pair of keys
+ * the faces between them and their contacts across a thin empty gap -- the counts under a scene graph (contrastive_lift_amd/relations.py).
+ *
+ * key (n0, n1, n2) int32, x-major as above; key 0 is background, valid keys are 0 .. n_keys - 1.  All results are integers and each is defined
+ * without reference to execution order: two runs give the same bits.
+ *   count (n_keys) int64: the points with key k, background included.  isum (n_keys, 3) int64: the sum of the index i_a over them.
+ *   ibox (n_keys, 6) int32: min_0 min_1 min_2 max_0 max_1 max_2 of the indices; min_a = n_a and max_a = -1 for a key that no point carries.
+ *   faces (n_keys, n_keys, 3) int32: every pair of lattice points (p, p + e_a) that both exist, with u = key[p], v = key[p + e_a], u != v, adds 1
+ *     to faces[u][v][a] -- u is the lower point along axis a.  Background counts: faces[u][0][a] are u's free faces towards +a, faces[0][v][a]
+ *     are v's free faces towards -a.  The diagonal stays 0.
+ *   near, same shape, NULL exactly when gap == 0 (gap 0 .. CLIFT_REL_MAX_GAP): for every p with u = key[p] != 0 and key[p + e_a] == 0, look on
+ *     along +a at d = 2 .. gap + 1 while p + d e_a is a lattice point and stop at the first non-background key v; if v != u, add 1 to
+ *     near[u][v][a] (a hole in one object, u 0 u, adds nothing).  A near contact is counted from its lower side only, once.
+ *   rejected (1) int32: a point whose key is outside [0, n_keys) adds 1 here and nothing else: no pair contains it, a look-through stops at it.
+ * The call clears its tables on the stream itself; it neither allocates nor synchronises.  One pass over 8 x 8 x 32 tiles held in LDS with the
+ * gap + 1 slabs beyond each positive face; equal keys and equal (u, v, a) are folded inside the wave before any atomic, and with
+ * n_keys <= CLIFT_REL_LDS_KEYS the pair counts go to a block-private LDS table first (2 x 3 x 32 x 32 ints = 24 KiB beside the 12.2 KiB tile:
+ * four 256-thread blocks per CU out of the CU's 160 KiB, which is what the fixed grid asks for); above it the folded adds go straight to memory.
+ * Errors, all checked before the device is touched: a dimension < 1, N >= CLIFT_ISO_LIMIT = 2^31 (the message names the limit), n_keys outside
+ * 1 .. CLIFT_REL_MAX_KEYS, gap outside 0 .. CLIFT_REL_MAX_GAP, near without gap or gap without near, a NULL required buffer. */
+#define CLIFT_REL_LDS_KEYS 32
+#define CLIFT_REL_MAX_KEYS 1024
+#define CLIFT_REL_MAX_GAP 4
+int clift_lattice_relations(const int* key, int n0, int n1, int n2, int n_keys, int gap, long* count, long* isum, int* ibox, int* faces,
+                            int* near, int* rejected, clift_stream_t s);
+
 /* ---- surface outputs of the ray route (a further ABI 27 addition; csrc/surface.hip).
  *
  * clift_density_grad_points: out (n, 4) fp32, row = [gx, gy, gz, sigma_raw] at the normalised points xn (n, ldx >= 3), where

@@ -4,6 +4,7 @@
     python inference/extract_mesh.py --ckpt_path runs/<experiment>/checkpoints/<x>.ckpt [--upsample 2] [--alpha_level 0.5 | --level SIGMA]
                                      [--cached_centroids_path all_centroids.pkl] [--split_instances] [--save_voxel_cloud]
                                      [--min_component VOXELS] [--keep_largest K] [--connectivity {6,kuhn,26}] [--split_disconnected [MIN_VOXELS]]
+                                     [--relations [--relations_gap 1] [--up_axis +z] [--relations_min_faces 4]]
                                      [--bboxes bboxes.pkl (--instance ID --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz]
                                                            [--pad 0.0] | --script edits.json)]
 
@@ -45,6 +46,17 @@ model grid through ``get_instance_clusters``, which knows nothing of edits.  ``-
 ``--shape_alpha``, as in inference/edit_scene.py) makes the edits follow the instance's shape, not its box: the shapes are
 read from the field once it is loaded, the slot table comes from ``--cached_centroids_path`` (a linear-assignment model needs none), and
 the file is ``mesh_edit_<tag>_shape.ply``.
+
+``--relations`` says how the instances stand to one another on the lattice that is meshed (after ``--min_component`` / ``--keep_largest``):
+every inside lattice point gets its class and id in one call (``lattice_nodes``, by the vertices' rule with zero normals; with
+``--split_disconnected`` the split ids, so a copy and its original are two nodes), every (class, id) pair becomes a node
+(``relations.node_keys``), and one kernel counts per node its extent and free faces and per pair of nodes the lattice faces between them
+and the contacts across at most ``--relations_gap`` empty lattice points (``relations.lattice_relations``, clift_lattice_relations).
+``relations.npz`` (``relations_edit_<tag>.npz`` under an edit) holds the raw tables and the node list, ``relations.json`` (``relations_edit_
+<tag>.json``) the scene graph (``relations.SceneGraph``): per node voxels, volume, centroid, box and free area, and "on" (along ``--up_axis``,
+with its support ratio) and "beside" between nodes with at least ``--relations_min_faces`` contacts.  Under an edit the lattice and the
+labels are the edited scene's, labelled where the content came from: the graph of a move shows what the moved object touches at its
+destination.  Without the flag nothing changes.
 """
 import argparse
 import math
@@ -64,6 +76,7 @@ sys.path.insert(0, HERE)
 import render_panopli as rp                                           # noqa: E402
 from contrastive_lift_amd import components as cc                     # noqa: E402
 from contrastive_lift_amd import mesh as cm                           # noqa: E402
+from contrastive_lift_amd import relations as rel                     # noqa: E402
 from contrastive_lift_amd.config import load_run_config               # noqa: E402
 
 
@@ -124,23 +137,66 @@ def lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, chu
     return ids.view(sigma.shape)
 
 
-def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity):
+def lattice_nodes(model, renderer, sigma, level, things, centroids, use_delta, chunk=2 ** 20, edit=None):
+    """The sibling of ``lattice_ids`` that keeps the class -> (sem, ids), both (n0, n1, n2) int32: class and instance id of every inside
+    lattice point by the same ONE call of ``surrogate_ids`` with zero normals (``ids`` is what ``lattice_ids`` returns: 0 on stuff), and
+    sem = -1, ids = 0 outside."""
+    inside = (sigma >= torch.tensor(float(level), dtype=torch.float32, device=sigma.device)).reshape(-1).nonzero().reshape(-1)
+    sem = torch.full((sigma.numel(),), -1, dtype=torch.int32, device=sigma.device)
+    ids = torch.zeros(sigma.numel(), dtype=torch.int32, device=sigma.device)
+    ticks = renderer.lattice_ticks(sigma.shape)
+    n1, n2 = int(sigma.shape[1]), int(sigma.shape[2])
+    xyz = torch.stack([ticks[0][inside // (n1 * n2)], ticks[1][(inside // n2) % n1], ticks[2][inside % n2]], 1).contiguous()
+    if inside.numel():
+        p_sem, p_ids, _ = surrogate_ids(model, renderer, xyz, torch.zeros_like(xyz), things, centroids, use_delta, chunk=chunk, edit=edit)
+        sem[inside], ids[inside] = p_sem.int(), p_ids.int()
+    return sem.view(sigma.shape), ids.view(sigma.shape)
+
+
+def scene_relations(renderer, sem, ids, gap=1, up="+z", min_faces=4):
+    """The relations of a labelled lattice (``lattice_nodes``; ``ids`` may be the split ids) -> dict(tables, nodes, key, graph)."""
+    key, nodes = rel.node_keys(sem, ids)
+    if len(nodes) + 1 > rel.MAX_KEYS:
+        raise SystemExit(f"--relations: {len(nodes)} (class, instance) nodes, at most {rel.MAX_KEYS - 1} can be related -- raise --min_component "
+                         f"or the MIN_VOXELS of --split_disconnected on a frothy scene")
+    tables = rel.lattice_relations(key, n_keys=len(nodes) + 1, gap=int(gap))
+    graph = rel.SceneGraph.from_counts(tables, nodes, renderer.lattice_ticks(key.shape), up=up, min_faces=min_faces)
+    return dict(tables=tables, nodes=nodes, key=key, graph=graph)
+
+
+def relations_stem(edit_tag=None):
+    """File stem of the relations: ``relations``, or ``relations_edit_<tag>`` for an edited scene; ``<stem>.npz`` and ``<stem>.json``."""
+    return "relations" if edit_tag is None else f"relations_edit_{edit_tag}"
+
+
+def write_relations(out, stem, r, gap):
+    """``<stem>.npz``: the raw tables (near absent at gap 0), the node list (K, 2) = (class, instance) of keys 1..K, and the gap;
+    ``<stem>.json``: the graph."""
+    arrays = {k: v.cpu().numpy() for k, v in r["tables"].items() if v is not None}
+    np.savez(Path(out) / f"{stem}.npz", nodes=np.asarray(r["nodes"], np.int64).reshape(-1, 2), gap=np.asarray(int(gap)), **arrays)
+    with open(Path(out) / f"{stem}.json", "w") as f:
+        f.write(r["graph"].to_json(indent=1))
+
+
+def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity, return_lattice=False):
     """-> (vertex ids after the split, table {fresh id: parent}).  A vertex takes the new id of the inside endpoint of its edge when its own
     id equals that point's original id; otherwise it keeps its id.  Fresh ids start above every id in use, the vertices' included (a vertex
-    on a class boundary can carry an id that no lattice point has)."""
+    on a class boundary can carry an id that no lattice point has).  ``return_lattice``: the id lattice after the split as a third result."""
     above = int(inst.max()) + 1 if inst.numel() else 1
     new_ids, table = cc.split_disconnected(ids, connectivity=connectivity, min_voxels=min_voxels, first_fresh=above)
     at = cc.vertex_owner_inside(keys, sigma, level)
     old, new = ids.reshape(-1)[at].long(), new_ids.reshape(-1)[at].long()
-    return torch.where(inst == old, new, inst), table
+    out = torch.where(inst == old, new, inst)
+    return (out, table, new_ids) if return_lattice else (out, table)
 
 
 def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=0, keep_largest=None, connectivity="kuhn",
-                   split_disconnected=None, edit=None):
+                   split_disconnected=None, edit=None, relations=None):
     """Everything between the density lattice and the files: (components) - isosurface - label_vertices - (split), each closed by a mark
     of ``timer``.  ``edit``: sigma is the lattice of the edited scene (``get_dense_sigma(edit=)``); vertices and lattice points are then
     labelled where their content came from.  -> dict(verts, faces, normals, sem, inst, rgb, sigma (as meshed), info (of filter_components, or None), table (of
-    split_disconnected, or None))."""
+    split_disconnected, or None)).  ``relations``: dict(gap, up, min_faces) adds the stage "relations" and the key ``relations``
+    (``scene_relations`` of the lattice as meshed; with ``split_disconnected`` on the split ids)."""
     info = table = None
     if int(min_component or 0) > 0 or keep_largest is not None:
         sigma, info = cc.filter_components(sigma, level, min_voxels=min_component, keep_largest=keep_largest, connectivity=connectivity)
@@ -149,16 +205,24 @@ def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, 
     timer.done("isosurface")
     sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta, edit=edit)
     timer.done("label_vertices")
+    if relations is not None:                                         # class and id of the inside points, once: the split below works on these ids
+        p_sem, p_ids = lattice_nodes(model, renderer, sigma, level, things, centroids, use_delta, edit=edit)
+        if split_disconnected is None:
+            timer.done("lattice_nodes")
     if split_disconnected is not None:
-        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, edit=edit)
-        inst, table = split_vertex_ids(inst, keys[0], sigma, level, ids, int(split_disconnected), connectivity)
+        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, edit=edit) if relations is None else p_ids
+        inst, table, *split = split_vertex_ids(inst, keys[0], sigma, level, ids, int(split_disconnected), connectivity, return_lattice=relations is not None)
         timer.done("split")
-    return dict(verts=verts, faces=faces, normals=normals, sem=sem, inst=inst, rgb=rgb, sigma=sigma, info=info, table=table)
+    out = dict(verts=verts, faces=faces, normals=normals, sem=sem, inst=inst, rgb=rgb, sigma=sigma, info=info, table=table)
+    if relations is not None:
+        out["relations"] = scene_relations(renderer, p_sem, split[0] if split_disconnected is not None else p_ids, **relations)
+        timer.done("relations")
+    return out
 
 
 def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
-                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None):
-    """``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
+                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None, relations=None):
+    """``relations``: dict(gap, up, min_faces) of ``--relations``.  ``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
     ``edit`` may be a callable ``edit(config, scene, model, renderer)`` that resolves it once the field is loaded (``--follow_shape``)."""
     if edit is not None and save_voxel_cloud:
         raise SystemExit(VOXEL_CLOUD_WITH_EDIT)
@@ -182,7 +246,7 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     sigma = renderer.get_dense_sigma(model, upsample) if edit is None else renderer.get_dense_sigma(model, upsample, edit=edit)
     timer.done("dense_sigma")
     m = surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=min_component, keep_largest=keep_largest,
-                       connectivity=connectivity, split_disconnected=split_disconnected, edit=edit)
+                       connectivity=connectivity, split_disconnected=split_disconnected, edit=edit, **({} if relations is None else {"relations": relations}))
     verts, faces, normals, sem, inst, rgb = (m[k] for k in ("verts", "faces", "normals", "sem", "inst", "rgb"))
     times = timer.report()
     print(f"sigma lattice {tuple(sigma.shape)}, level {level:.6g}: {verts.shape[0]} vertices, {faces.shape[0]} faces, "
@@ -193,6 +257,11 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     if m["table"] is not None:
         print(f"split_disconnected ({connectivity}, pieces of at least {int(split_disconnected)} points): {len(m['table'])} fresh ids")
     cm.write_ply(out / f"{stem}.ply", verts, faces, normals, rgb, sem, inst)
+    if relations is not None:
+        write_relations(out, relations_stem(edit_tag if edit is not None else None), m["relations"], relations["gap"])
+        g = m["relations"]["graph"]
+        print(f"relations (gap {relations['gap']}, up {relations['up']}): {len(g.nodes)} nodes, {len(g.pairs)} pairs in contact, "
+              f"{sum(r['relation'] == 'on' for r in g.relations)} on, {sum(r['relation'] == 'beside' for r in g.relations)} beside")
     if split_instances:
         f_inst = inst[faces.long()]                                   # (F, 3)
         for i in torch.unique(inst).tolist():
@@ -270,11 +339,22 @@ def cli_edit_of(args):
     return late
 
 
+def relations_options(args):
+    """What ``extract_mesh(relations=)`` takes for the parsed command line; None without ``--relations``."""
+    if not args.relations:
+        return None
+    return dict(gap=args.relations_gap, up=args.up_axis, min_faces=args.relations_min_faces)
+
+
 class _Parser(argparse.ArgumentParser):
     """The cross-argument rules of the edit flags, checked where the arguments are parsed."""
 
     def parse_args(self, args=None, namespace=None):
-        a = super().parse_args(args, namespace)
+        args = list(sys.argv[1:] if args is None else args)
+        for i in range(len(args) - 1):                                # "--up_axis -z": argparse would read the value as an option
+            if args[i] == "--up_axis" and args[i + 1] in rel.UP_AXES:
+                args[i:i + 2] = [f"--up_axis={args[i + 1]}", None]
+        a = super().parse_args([x for x in args if x is not None], namespace)
         if a.script is None and (a.instance is None) != (a.op is None):
             self.error("--instance and --op come together")
         if edit_tag_of(a) is None:
@@ -319,6 +399,14 @@ def build_parser():
                     help="give the separated pieces of one instance id ids of their own: the largest keeps the id, every other piece of at least "
                          "MIN_VOXELS lattice points (default 1) gets a fresh one; mesh_instance_<id>.ply follows the new ids (the PLY holds ids up "
                          "to 65535: raise MIN_VOXELS or --min_component on a frothy scene)")
+    ap.add_argument("--relations", action="store_true",
+                    help="also write relations.npz (raw tables) and relations.json (the scene graph) next to the mesh: per (class, instance) node "
+                         "its extent and free area, per pair of nodes their contacts, and what stands on or beside what")
+    ap.add_argument("--relations_gap", type=int, default=1, choices=list(range(rel.MAX_GAP + 1)), metavar="G",
+                    help="--relations: a contact may look through up to G empty lattice points (0 .. %d; objects of a density field are "
+                         "usually separated by a thin gap at the level set)" % rel.MAX_GAP)
+    ap.add_argument("--up_axis", type=str, default="+z", choices=list(rel.UP_AXES), help="--relations: the scene's up direction")
+    ap.add_argument("--relations_min_faces", type=int, default=4, metavar="N", help="--relations: contacts below this count name no relation")
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="as render_panopli.py (the scene loader wants it)")
     ap.add_argument("--bboxes", type=str, default=None, help="bboxes.pkl of inference/fit_bboxes.py: mesh the scene under an edit (with --instance / --op or --script)")
     ap.add_argument("--instance", type=int, default=None, help="instance id (a key of bboxes.pkl) the edit acts on")
@@ -344,4 +432,5 @@ if __name__ == "__main__":
     print(extract_mesh(cfg, upsample=args.upsample, alpha_level=args.alpha_level, level=args.level,
                        cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
                        save_voxel_cloud=args.save_voxel_cloud, min_component=args.min_component, keep_largest=args.keep_largest,
-                       connectivity=args.connectivity, split_disconnected=args.split_disconnected, edit=the_edit, edit_tag=the_tag)[0])
+                       connectivity=args.connectivity, split_disconnected=args.split_disconnected, edit=the_edit, edit_tag=the_tag,
+                       relations=relations_options(args))[0])
