@@ -889,6 +889,37 @@ int clift_cc_label(const int* key, int n0, int n1, int n2, int connectivity, int
 int clift_lattice_relations(const int* key, int n0, int n1, int n2, int n_keys, int gap, long* count, long* isum, int* ibox, int* faces,
                             int* near, int* rejected, clift_stream_t s);
 
+/* ---- clearance of a keyed lattice (a further ABI 27 addition; csrc/clearance.hip): how far every key can travel along the six
+ * lattice directions before it meets another key, and on how many faces it then rests -- a look of UNBOUNDED length, where `near` above stops
+ * after CLIFT_REL_MAX_GAP points (contrastive_lift_amd/clearance.py; inference/edit_scene.py --settle).
+ *
+ * key (n0, n1, n2) int32 as above: key 0 is background, valid keys are 0 .. n_keys - 1 (1 <= n_keys <= CLIFT_REL_MAX_KEYS), N = n0 n1 n2 < 2^31.
+ * Directions: d = 2a for +a, d = 2a + 1 for -a, a = 0, 1, 2.
+ * Events.  In one column of the lattice along axis a take two points at indices i < j with keys u (at i) and v (at j), both valid and non-zero,
+ *   u != v, and every point strictly between them of key 0: then g = j - i - 1 >= 0 is an event (u, v, 2a, g) and an event (v, u, 2a + 1, g).
+ *   Two such points with u == v are no event (a rigid object does not stop on its own handle).  A point whose key lies outside [0, n_keys) is
+ *   counted in `rejected` and ends the look from both sides: no event crosses it.  The lattice border is no obstacle and gives no event (the
+ *   distance to it follows from ibox above).
+ * Outputs, all int32, all filled by the call itself, each defined without reference to execution order (two runs give the same bits):
+ *   pair (n_keys, n_keys, 6): the minimum g over the events (u, v, d, .), CLIFT_CLR_NONE where there is none; rows and columns of key 0 and the
+ *     diagonal stay NONE.
+ *   travel (n_keys, 6): min_v pair[u][v][d] -- the lattice steps key u can be shifted along d before its first point meets another key.
+ *   landing (n_keys, n_keys, 6): the number of events (u, v, d, g) with g <= travel[u][d] + slack, slack 0 .. CLIFT_CLR_MAX_SLACK: the faces on
+ *     which u rests on v once it has travelled; 0 where travel is NONE.
+ *   rejected (1): as above.
+ * With `faces` and `near` of clift_lattice_relations, for u, v >= 1: pair[u][v][2a] == 0 exactly where faces[u][v][a] > 0, and for gap = G >= 1
+ * pair[u][v][2a] <= G exactly where faces[u][v][a] + near[u][v][a] > 0.
+ * Two launches of one kernel body in stream order -- the minima by atomic-min, then the same events again for the counts --; every axis is read
+ * coalesced (axes 0, 1: a lane per column; axis 2: a wave per row, the predecessor of a point from the ballot of the non-zero lanes) and a
+ * column is walked whole, whatever its length.  Equal codes are folded inside the wave before any atomic; with n_keys <= CLIFT_REL_LDS_KEYS the
+ * block works into a private LDS table (at most 6 x 32 x 33 ints = 24.75 KiB) first.  The call neither allocates nor synchronises.
+ * Errors, all checked before the device is touched: a dimension < 1, N >= CLIFT_ISO_LIMIT = 2^31 (the message names the limit), n_keys outside
+ * 1 .. CLIFT_REL_MAX_KEYS, slack outside 0 .. CLIFT_CLR_MAX_SLACK, a NULL buffer. */
+#define CLIFT_CLR_MAX_SLACK 4
+#define CLIFT_CLR_NONE 0x7fffffff
+int clift_lattice_clearance(const int* key, int n0, int n1, int n2, int n_keys, int slack, int* pair, int* travel, int* landing, int* rejected,
+                            clift_stream_t s);
+
 /* ---- surface outputs of the ray route (a further ABI 27 addition; csrc/surface.hip).
  *
  * clift_density_grad_points: out (n, 4) fp32, row = [gx, gy, gz, sigma_raw] at the normalised points xn (n, ldx >= 3), where

@@ -6,6 +6,7 @@
                                    [--render_trajectory] [--image_dim H W] [--weight_thres 0] [--save_surface [--surface_quantile 0.5]]
                                    [--save_layers --cached_centroids_path C [--layers_level 0.5] [--layers_colour [--layers_colour_rest]]]
                                    [--follow_shape --cached_centroids_path C [--shape_grid 32] [--shape_grow 1] [--shape_alpha 0.5]]
+                                   [--settle [AXIS] [--settle_upsample 1] [--settle_slack 0]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
@@ -41,6 +42,16 @@ and a moved chair takes no floor along and covers nothing but itself at the dest
 the cells set, occupied and in all.  A script entry may say ``"shape": true|false`` (default: the flag); an ``"at": "moved"`` entry
 reuses the shape of the move it refers to and must not pad the box again.  Output names get ``_shape`` behind them.
 ``--follow_shape`` cannot be combined with ``--save_surface`` or ``--save_layers``: those passes walk the boxes alone.
+
+``--settle [AXIS]`` (with ``--op move|copy``, or a ``--script`` whose last entry is a move or a copy) drops the object that the last edit
+places along AXIS (one of +x -x +y -y +z -z, default -z) until it touches the rest of the edited scene (DESIGN.md 6n;
+``clearance.settle_offset``): the density lattice of the edited scene at ``--settle_upsample`` times the grid is keyed -- the moved content,
+everything else, empty --, one kernel finds the free travel of the moved content along AXIS in lattice steps
+(clift_lattice_clearance), and the last edit is rebuilt with that translation added (a shape is reused as it is).  One line reports
+``settled by N steps = D along AXIS onto F faces`` (``--settle_slack S`` counts the faces up to S steps further away); the output folder
+gets ``_settled`` behind its name.  When nothing stands in the way the tool says so and renders the edit as given.  A BOX move carries a
+slab of its surroundings along -- the floor under a chair --, which is in contact already, so its travel is usually 0: ``--follow_shape``
+is the intended companion.
 """
 import argparse
 import functools
@@ -62,6 +73,7 @@ import render_panopli as rp                                           # noqa: E4
 from contrastive_lift_amd import edit as ed                           # noqa: E402
 from contrastive_lift_amd import inference as inf                     # noqa: E402
 from contrastive_lift_amd.config import load_run_config               # noqa: E402
+from contrastive_lift_amd.relations import UP_AXES                    # noqa: E402
 
 OPS = ("delete", "extract", "copy", "move")
 
@@ -179,12 +191,45 @@ SHAPE_WITH_SURFACE_OR_LAYERS = ("--follow_shape (or a script entry with \"shape\
                                 "those passes walk the boxes alone and would drop the shapes (shaped surfaces and layers are not built yet)")
 
 
+SETTLE_WANTS_A_MOTION = "--settle drops the object that a move or a copy places: give it with --op move|copy, or with a --script whose last entry is one"
+
+
+def check_settle(edit):
+    """``SystemExit`` unless the last edit of ``edit`` is a copy or a move."""
+    if ed.as_program(edit)[-1].mode not in (ed.DUPLICATE, ed.MANIPULATE):
+        raise SystemExit(SETTLE_WANTS_A_MOTION)
+
+
+def settled_edit(edit, offset):
+    """``edit`` (an ``Edit`` or an ``EditProgram``) with the world translation ``offset`` added to its LAST edit, a copy or a move: that
+    edit goes through the same constructor again with translate + offset.  Its rotation is read back from the map (M = R^-1), its
+    translation from the two box centres; a shape is reused as it is -- a rigid move keeps lo, hi and the frame."""
+    program = ed.as_program(edit)
+    last = program[-1]
+    make = ed.copy if last.mode == ed.DUPLICATE else ed.move
+    moved = make(last.src, (last.dst.centre - last.src.centre) + np.asarray(offset, np.float64), np.linalg.inv(last.M), shape=last.shape)
+    return moved if isinstance(edit, ed.Edit) else ed.EditProgram(list(program.edits[:-1]) + [moved])
+
+
+def settle(model, renderer, edit, direction="-z", upsample=1, slack=0):
+    """``--settle``: (the edit to render, the dict of ``clearance.settle_offset``); prints the one line."""
+    from contrastive_lift_amd import clearance as clr
+    check_settle(edit)
+    found = clr.settle_offset(model, renderer, edit, direction=direction, upsample=int(upsample), slack=int(slack))
+    if not found["found"]:
+        print(f"not settled: nothing stands in the way along {direction} ({found['n_moved']} lattice points moved); the edit is rendered as given")
+        return edit, found
+    print(f"settled by {found['steps']} steps = {found['steps'] * found['spacing']:.4f} along {direction} onto {found['faces']} faces")
+    return settled_edit(edit, found["offset"]), found
+
+
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
                           save_surface=False, surface_quantile=0.5, save_layers=False, cached_centroids_path=None, layers_level=0.5,
-                          layers_colour=False, layers_colour_rest=False):
+                          layers_colour=False, layers_colour_rest=False, settle_options=None):
+    """``settle_options``: dict(direction, upsample, slack) of ``--settle``; the folder gets ``_settled`` behind its name."""
     if (layers_colour or layers_colour_rest) and not save_layers:
         raise ValueError("layers_colour needs save_layers")
-    out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}")
+    out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}{'_settled' if settle_options else ''}")
     device, rank = rp.distributed_device(device)
     scene, model, renderer = rp.load_for_inference(config, device)
     H, W = scene.image_dim
@@ -192,6 +237,8 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
         edit = edit(scene, model, renderer)
     if ed.as_program(edit).is_shaped and (save_surface or save_layers):
         raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
+    if settle_options:              # (every rank computes the same offset: integer tables of the same lattice)
+        edit = settle(model, renderer, edit, **settle_options)[0]
     if save_layers:
         table = rp.layers_table(config, scene, cached_centroids_path)
         table_edit = table.for_program(edit)
@@ -279,13 +326,40 @@ def build_parser():
     ap.add_argument("--layers_level", type=float, default=0.5, help="the opacity above which --save_layers counts a pixel into a mask")
     rp.add_layers_colour_arguments(ap)
     add_shape_arguments(ap)
+    ap.add_argument("--settle", type=str, nargs="?", const="-z", default=None, metavar="AXIS",
+                    help="with --op move|copy, or a --script that ends in one: drop the object that the last edit places along AXIS (one of "
+                         "+x -x +y -y +z -z, default -z) until it touches the rest of the edited scene, report the lattice steps and the faces "
+                         "in contact, and render into ..._settled.  A BOX move carries a slab of its surroundings along, so its travel is "
+                         "usually 0: --follow_shape is the intended companion")
+    ap.add_argument("--settle_upsample", type=int, default=None, metavar="U", help="--settle: the lattice is the grid times this factor per axis (default 1)")
+    ap.add_argument("--settle_slack", type=int, default=None, metavar="S",
+                    help="--settle: count the faces up to S lattice steps further away than the first contact (0 .. 4, default 0)")
     return ap
 
 
 def parse_args(argv=None):
     ap = build_parser()
-    args = ap.parse_args(argv)
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):                                    # "--settle -z": argparse would read the value as an option
+        if argv[i] == "--settle" and argv[i + 1] in UP_AXES:
+            argv[i:i + 2] = [f"--settle={argv[i + 1]}", None]
+    args = ap.parse_args([x for x in argv if x is not None])
     rp.check_layers_colour_arguments(ap, args)
+    if args.settle is None:
+        for flag in ("settle_upsample", "settle_slack"):
+            if getattr(args, flag) is not None:
+                ap.error(f"--{flag} needs --settle")
+    else:
+        if args.settle not in UP_AXES:
+            ap.error(f"--settle: AXIS is one of {' '.join(UP_AXES)} (got {args.settle!r})")
+        if args.script is None and args.op not in ("move", "copy"):
+            ap.error(SETTLE_WANTS_A_MOTION)
+        args.settle_upsample = 1 if args.settle_upsample is None else args.settle_upsample
+        args.settle_slack = 0 if args.settle_slack is None else args.settle_slack
+        if args.settle_upsample < 1:
+            ap.error(f"--settle_upsample must be >= 1 (got {args.settle_upsample})")
+        if not 0 <= args.settle_slack <= 4:
+            ap.error(f"--settle_slack must be 0 .. 4 (got {args.settle_slack})")
     if args.follow_shape and (args.save_surface or args.save_layers):
         raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if args.script is not None and (args.instance is not None or args.op is not None):
@@ -325,10 +399,14 @@ def main(argv=None):
         tag += "_shape"
     if not shaped:                  # (no field is needed: resolve now, so that a bad script stops before the checkpoint is loaded)
         the_edit = the_edit(None, None, None)
+        if args.settle is not None:
+            check_settle(the_edit)
+    settle_options = None if args.settle is None else dict(direction=args.settle, upsample=args.settle_upsample, slack=args.settle_slack)
     print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
                                 save_surface=args.save_surface, surface_quantile=args.surface_quantile, save_layers=args.save_layers,
                                 cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level,
-                                layers_colour=args.layers_colour, layers_colour_rest=args.layers_colour_rest))
+                                layers_colour=args.layers_colour, layers_colour_rest=args.layers_colour_rest,
+                                **({} if settle_options is None else {"settle_options": settle_options})))
 
 
 if __name__ == "__main__":

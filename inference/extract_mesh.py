@@ -5,6 +5,7 @@
                                      [--cached_centroids_path all_centroids.pkl] [--split_instances] [--save_voxel_cloud]
                                      [--min_component VOXELS] [--keep_largest K] [--connectivity {6,kuhn,26}] [--split_disconnected [MIN_VOXELS]]
                                      [--relations [--relations_gap 1] [--up_axis +z] [--relations_min_faces 4]]
+                                     [--clearance [--clearance_slack 0]]
                                      [--bboxes bboxes.pkl (--instance ID --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz]
                                                            [--pad 0.0] | --script edits.json)]
 
@@ -57,9 +58,15 @@ and the contacts across at most ``--relations_gap`` empty lattice points (``rela
 with its support ratio) and "beside" between nodes with at least ``--relations_min_faces`` contacts.  Under an edit the lattice and the
 labels are the edited scene's, labelled where the content came from: the graph of a move shows what the moved object touches at its
 destination.  Without the flag nothing changes.
+
+``--clearance`` says how far every node of that labelled lattice -- the nodes of ``--relations``; with both flags the labelling is done once --
+can travel along the six lattice directions before it meets another node (``clearance.lattice_clearance``, clift_lattice_clearance: a look
+of unbounded length, where ``--relations_gap`` stops after 4 points).  ``clearance.npz`` (``clearance_edit_<tag>.npz`` under an edit) holds
+the raw tables pair, travel and landing and the node list, ``clearance.json`` (``clearance_edit_<tag>.json``) per node and direction the
+steps, the distance, the nodes it would then rest on with their face counts (``--clearance_slack S``: up to S steps further away) and the
+steps to the lattice border (``clearance.Clearance``).  ``relations.json`` and ``relations.npz`` do not change.
 """
 import argparse
-import math
 import os
 import pickle
 import random
@@ -74,6 +81,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 import render_panopli as rp                                           # noqa: E402
+from contrastive_lift_amd import clearance as clr                     # noqa: E402
 from contrastive_lift_amd import components as cc                     # noqa: E402
 from contrastive_lift_amd import mesh as cm                           # noqa: E402
 from contrastive_lift_amd import relations as rel                     # noqa: E402
@@ -82,11 +90,12 @@ from contrastive_lift_amd.config import load_run_config               # noqa: E4
 
 def default_level(renderer, alpha_level):
     """The sigma at which ONE sample of a training step would have opacity ``alpha_level``: alpha = 1 - exp(-sigma step distance_scale).
-    ``renderer`` comes from ``load_for_inference``, which halves the step ratio (RP:104): the training step is twice its step."""
-    if not 0.0 < alpha_level < 1.0:
-        raise SystemExit(f"--alpha_level must lie in (0, 1) (got {alpha_level})")
-    train_step = 2.0 * renderer.step_size_host
-    return -math.log(1.0 - alpha_level) / (train_step * float(renderer.distance_scale))
+    ``renderer`` comes from ``load_for_inference``, which halves the step ratio (RP:104): the training step is twice its step.
+    (``clearance.default_level``, which ``clearance.settle_offset`` shares; a bad ``alpha_level`` ends the tool.)"""
+    try:
+        return clr.default_level(renderer, alpha_level)
+    except ValueError as err:
+        raise SystemExit(str(err))
 
 
 class StageTimer:
@@ -178,6 +187,32 @@ def write_relations(out, stem, r, gap):
         f.write(r["graph"].to_json(indent=1))
 
 
+def scene_clearance(renderer, sem, ids, slack=0, related=None):
+    """The clearance of a labelled lattice (``lattice_nodes``; ``ids`` may be the split ids) -> dict(tables, nodes, key, summary, slack).
+    ``related``: the result of ``scene_relations`` on the same labels -- its keys, nodes and index boxes are used as they are."""
+    key, nodes = (related["key"], related["nodes"]) if related is not None else rel.node_keys(sem, ids)
+    if len(nodes) + 1 > rel.MAX_KEYS:
+        raise SystemExit(f"--clearance: {len(nodes)} (class, instance) nodes, at most {rel.MAX_KEYS - 1} can be swept -- raise --min_component "
+                         f"or the MIN_VOXELS of --split_disconnected on a frothy scene")
+    tables = clr.lattice_clearance(key, n_keys=len(nodes) + 1, slack=int(slack))
+    box = dict(relations=related["tables"]) if related is not None else dict(key=key)
+    summary = clr.Clearance.from_tables(tables, nodes, renderer.lattice_ticks(key.shape), slack=int(slack), **box)
+    return dict(tables=tables, nodes=nodes, key=key, summary=summary, slack=int(slack))
+
+
+def clearance_stem(edit_tag=None):
+    """File stem of the clearance: ``clearance``, or ``clearance_edit_<tag>`` for an edited scene; ``<stem>.npz`` and ``<stem>.json``."""
+    return "clearance" if edit_tag is None else f"clearance_edit_{edit_tag}"
+
+
+def write_clearance(out, stem, c):
+    """``<stem>.npz``: the raw tables, the node list (K, 2) = (class, instance) of keys 1..K, and the slack; ``<stem>.json``: the summary."""
+    arrays = {k: v.cpu().numpy() for k, v in c["tables"].items()}
+    np.savez(Path(out) / f"{stem}.npz", nodes=np.asarray(c["nodes"], np.int64).reshape(-1, 2), slack=np.asarray(int(c["slack"])), **arrays)
+    with open(Path(out) / f"{stem}.json", "w") as f:
+        f.write(c["summary"].to_json(indent=1))
+
+
 def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity, return_lattice=False):
     """-> (vertex ids after the split, table {fresh id: parent}).  A vertex takes the new id of the inside endpoint of its edge when its own
     id equals that point's original id; otherwise it keeps its id.  Fresh ids start above every id in use, the vertices' included (a vertex
@@ -191,13 +226,15 @@ def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity, re
 
 
 def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=0, keep_largest=None, connectivity="kuhn",
-                   split_disconnected=None, edit=None, relations=None):
+                   split_disconnected=None, edit=None, relations=None, clearance=None):
     """Everything between the density lattice and the files: (components) - isosurface - label_vertices - (split), each closed by a mark
     of ``timer``.  ``edit``: sigma is the lattice of the edited scene (``get_dense_sigma(edit=)``); vertices and lattice points are then
     labelled where their content came from.  -> dict(verts, faces, normals, sem, inst, rgb, sigma (as meshed), info (of filter_components, or None), table (of
     split_disconnected, or None)).  ``relations``: dict(gap, up, min_faces) adds the stage "relations" and the key ``relations``
-    (``scene_relations`` of the lattice as meshed; with ``split_disconnected`` on the split ids)."""
+    (``scene_relations`` of the lattice as meshed; with ``split_disconnected`` on the split ids).  ``clearance``: dict(slack) adds the stage
+    "clearance" and the key ``clearance`` (``scene_clearance`` of the same labels; with ``relations`` the labelling is shared)."""
     info = table = None
+    labelled = relations is not None or clearance is not None
     if int(min_component or 0) > 0 or keep_largest is not None:
         sigma, info = cc.filter_components(sigma, level, min_voxels=min_component, keep_largest=keep_largest, connectivity=connectivity)
         timer.done("components")
@@ -205,24 +242,28 @@ def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, 
     timer.done("isosurface")
     sem, inst, rgb = surrogate_ids(model, renderer, verts, normals, things, centroids, use_delta, edit=edit)
     timer.done("label_vertices")
-    if relations is not None:                                         # class and id of the inside points, once: the split below works on these ids
+    if labelled:                                                      # class and id of the inside points, once: the split below works on these ids
         p_sem, p_ids = lattice_nodes(model, renderer, sigma, level, things, centroids, use_delta, edit=edit)
         if split_disconnected is None:
             timer.done("lattice_nodes")
     if split_disconnected is not None:
-        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, edit=edit) if relations is None else p_ids
-        inst, table, *split = split_vertex_ids(inst, keys[0], sigma, level, ids, int(split_disconnected), connectivity, return_lattice=relations is not None)
+        ids = lattice_ids(model, renderer, sigma, level, things, centroids, use_delta, edit=edit) if not labelled else p_ids
+        inst, table, *split = split_vertex_ids(inst, keys[0], sigma, level, ids, int(split_disconnected), connectivity, return_lattice=labelled)
         timer.done("split")
     out = dict(verts=verts, faces=faces, normals=normals, sem=sem, inst=inst, rgb=rgb, sigma=sigma, info=info, table=table)
     if relations is not None:
         out["relations"] = scene_relations(renderer, p_sem, split[0] if split_disconnected is not None else p_ids, **relations)
         timer.done("relations")
+    if clearance is not None:
+        out["clearance"] = scene_clearance(renderer, p_sem, split[0] if split_disconnected is not None else p_ids, related=out.get("relations"), **clearance)
+        timer.done("clearance")
     return out
 
 
 def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
-                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None, relations=None):
-    """``relations``: dict(gap, up, min_faces) of ``--relations``.  ``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
+                 device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None, relations=None,
+                 clearance=None):
+    """``relations``: dict(gap, up, min_faces) of ``--relations``; ``clearance``: dict(slack) of ``--clearance``.  ``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
     ``edit`` may be a callable ``edit(config, scene, model, renderer)`` that resolves it once the field is loaded (``--follow_shape``)."""
     if edit is not None and save_voxel_cloud:
         raise SystemExit(VOXEL_CLOUD_WITH_EDIT)
@@ -246,7 +287,8 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     sigma = renderer.get_dense_sigma(model, upsample) if edit is None else renderer.get_dense_sigma(model, upsample, edit=edit)
     timer.done("dense_sigma")
     m = surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=min_component, keep_largest=keep_largest,
-                       connectivity=connectivity, split_disconnected=split_disconnected, edit=edit, **({} if relations is None else {"relations": relations}))
+                       connectivity=connectivity, split_disconnected=split_disconnected, edit=edit, **({} if relations is None else {"relations": relations}),
+                       **({} if clearance is None else {"clearance": clearance}))
     verts, faces, normals, sem, inst, rgb = (m[k] for k in ("verts", "faces", "normals", "sem", "inst", "rgb"))
     times = timer.report()
     print(f"sigma lattice {tuple(sigma.shape)}, level {level:.6g}: {verts.shape[0]} vertices, {faces.shape[0]} faces, "
@@ -262,6 +304,11 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
         g = m["relations"]["graph"]
         print(f"relations (gap {relations['gap']}, up {relations['up']}): {len(g.nodes)} nodes, {len(g.pairs)} pairs in contact, "
               f"{sum(r['relation'] == 'on' for r in g.relations)} on, {sum(r['relation'] == 'beside' for r in g.relations)} beside")
+    if clearance is not None:
+        write_clearance(out, clearance_stem(edit_tag if edit is not None else None), m["clearance"])
+        c = m["clearance"]["summary"]
+        print(f"clearance (slack {clearance['slack']}): {len(c.nodes)} nodes, "
+              f"{sum(d['steps'] is not None for n in c.nodes for d in n['directions'].values())} of {6 * len(c.nodes)} looks end at another node")
     if split_instances:
         f_inst = inst[faces.long()]                                   # (F, 3)
         for i in torch.unique(inst).tolist():
@@ -346,6 +393,13 @@ def relations_options(args):
     return dict(gap=args.relations_gap, up=args.up_axis, min_faces=args.relations_min_faces)
 
 
+def clearance_options(args):
+    """What ``extract_mesh(clearance=)`` takes for the parsed command line; None without ``--clearance``."""
+    if not args.clearance:
+        return None
+    return dict(slack=0 if args.clearance_slack is None else args.clearance_slack)
+
+
 class _Parser(argparse.ArgumentParser):
     """The cross-argument rules of the edit flags, checked where the arguments are parsed."""
 
@@ -355,6 +409,10 @@ class _Parser(argparse.ArgumentParser):
             if args[i] == "--up_axis" and args[i + 1] in rel.UP_AXES:
                 args[i:i + 2] = [f"--up_axis={args[i + 1]}", None]
         a = super().parse_args([x for x in args if x is not None], namespace)
+        if a.clearance_slack is not None and not a.clearance:
+            self.error("--clearance_slack needs --clearance")
+        if a.clearance:
+            a.clearance_slack = 0 if a.clearance_slack is None else a.clearance_slack
         if a.script is None and (a.instance is None) != (a.op is None):
             self.error("--instance and --op come together")
         if edit_tag_of(a) is None:
@@ -407,6 +465,12 @@ def build_parser():
                          "usually separated by a thin gap at the level set)" % rel.MAX_GAP)
     ap.add_argument("--up_axis", type=str, default="+z", choices=list(rel.UP_AXES), help="--relations: the scene's up direction")
     ap.add_argument("--relations_min_faces", type=int, default=4, metavar="N", help="--relations: contacts below this count name no relation")
+    ap.add_argument("--clearance", action="store_true",
+                    help="also write clearance.npz (raw tables) and clearance.json next to the mesh: per (class, instance) node and lattice "
+                         "direction the free travel to the next node in lattice steps and as a distance, the nodes it would rest on with their "
+                         "face counts, and the steps to the lattice border (DESIGN.md 6n); the nodes are those of --relations")
+    ap.add_argument("--clearance_slack", type=int, default=None, choices=list(range(clr.MAX_SLACK + 1)), metavar="S",
+                    help="--clearance: count the faces up to S lattice steps further away than the first contact (0 .. %d, default 0)" % clr.MAX_SLACK)
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="as render_panopli.py (the scene loader wants it)")
     ap.add_argument("--bboxes", type=str, default=None, help="bboxes.pkl of inference/fit_bboxes.py: mesh the scene under an edit (with --instance / --op or --script)")
     ap.add_argument("--instance", type=int, default=None, help="instance id (a key of bboxes.pkl) the edit acts on")
@@ -433,4 +497,4 @@ if __name__ == "__main__":
                        cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
                        save_voxel_cloud=args.save_voxel_cloud, min_component=args.min_component, keep_largest=args.keep_largest,
                        connectivity=args.connectivity, split_disconnected=args.split_disconnected, edit=the_edit, edit_tag=the_tag,
-                       relations=relations_options(args))[0])
+                       relations=relations_options(args), **({} if clearance_options(args) is None else {"clearance": clearance_options(args)}))[0])
