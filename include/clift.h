@@ -920,6 +920,36 @@ int clift_lattice_relations(const int* key, int n0, int n1, int n2, int n_keys, 
 int clift_lattice_clearance(const int* key, int n0, int n1, int n2, int n_keys, int slack, int* pair, int* travel, int* landing, int* rejected,
                             clift_stream_t s);
 
+/* ---- distance transform of a keyed lattice (a further ABI 27 addition; csrc/distance.hip): the exact Euclidean distance of
+ * every lattice point to the nearest site, with that site carried along (a feature transform) -- where the clearance above looks along the six
+ * lattice directions only (contrastive_lift_amd/distance.py; inference/extract_mesh.py --separation, inference/edit_scene.py --check_placement).
+ *
+ * Lattice and keys.  key (n0, n1, n2) int32, x-major: lin = (i0 n1 + i1) n2 + i2; N = n0 n1 n2 < 2^31 and every dimension is
+ *   1 .. CLIFT_DT_MAX_DIM = 16384, so that dist2 <= 3 * 16383^2 < 2^31.  Valid keys are 0 .. n_keys - 1, 1 <= n_keys <= CLIFT_REL_MAX_KEYS.  A
+ *   point whose key lies outside that range is counted in `rejected` (1) int32; it is no site and contributes to nothing.
+ * Sites.  site: n_keys bytes on the device.  A point is a site when its key is valid and site[key] != 0.  Key 0 (background) may be a site:
+ *   that gives the transform of the complement, the distance to the nearest empty point.
+ * Result.  out (N) int64: out[p] = (dist2 << 31) | nearest with dist2 = min over the sites s of |p - s|^2 in index units (an integer) and
+ *   nearest = the lin of a site at that distance; of several sites at that distance the one with the smallest lin.  That is: out[p] is the
+ *   minimum of the packed word over all sites.  out[p] = CLIFT_DT_NONE where there is no site at all.  A site has dist2 = 0 and itself as
+ *   nearest.  The rule is separable: in a pass along one axis take the packed word with its dist2 field increased by (i - j)^2 and the minimum
+ *   over j; the passes z, y, x compose to the minimum over all sites.
+ * Per-key minimum.  key_min (n_keys) int64, may be NULL: key_min[u] = min over the points p with key u of (dist2(p) << 31) | lin(p) for the
+ *   valid keys u >= 1 -- the point of u nearest to a site, the smaller lin on a tie.  key_min[0] and the keys that no point carries stay
+ *   CLIFT_DT_NONE, and so does everything when there is no site.  One 64-bit unsigned minimum per entry: the order of the atomics cannot
+ *   change the result.
+ * Metric.  Distances are in index units: the nearest site in index space, not in world space, is taken (the voxels of the density lattice are
+ *   nearly but not exactly cubic).  World distances are formed afterwards in fp64 from the lattice ticks of p and of nearest and are exact for
+ *   the pair that was chosen.  There are no per-axis weights.
+ * work (N) int64 is scratch for the passes; its contents after the call are unspecified.  out and work must not overlap.  The call fills out,
+ * key_min and rejected itself, on its stream; it neither allocates nor synchronises.  Two runs give the same bits.
+ * Errors, all checked before the device is touched: a dimension outside 1 .. CLIFT_DT_MAX_DIM, N >= CLIFT_ISO_LIMIT = 2^31 (the message names
+ * the limit), n_keys outside 1 .. CLIFT_REL_MAX_KEYS, a NULL buffer (key_min excepted), out and work overlapping. */
+#define CLIFT_DT_MAX_DIM 16384
+#define CLIFT_DT_NONE 0x7fffffffffffffffL
+int clift_lattice_distance(const int* key, int n0, int n1, int n2, int n_keys, const unsigned char* site, long* out, long* work, long* key_min,
+                           int* rejected, clift_stream_t s);
+
 /* ---- surface outputs of the ray route (a further ABI 27 addition; csrc/surface.hip).
  *
  * clift_density_grad_points: out (n, 4) fp32, row = [gx, gy, gz, sigma_raw] at the normalised points xn (n, ldx >= 3), where

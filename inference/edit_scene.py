@@ -7,6 +7,7 @@
                                    [--save_layers --cached_centroids_path C [--layers_level 0.5] [--layers_colour [--layers_colour_rest]]]
                                    [--follow_shape --cached_centroids_path C [--shape_grid 32] [--shape_grow 1] [--shape_alpha 0.5]]
                                    [--settle [AXIS] [--settle_upsample 1] [--settle_slack 0]]
+                                   [--check_placement [--placement_upsample 1]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
@@ -52,10 +53,19 @@ everything else, empty --, one kernel finds the free travel of the moved content
 gets ``_settled`` behind its name.  When nothing stands in the way the tool says so and renders the edit as given.  A BOX move carries a
 slab of its surroundings along -- the floor under a chair --, which is in contact already, so its travel is usually 0: ``--follow_shape``
 is the intended companion.
+
+``--check_placement`` (with ``--op move|copy``, or a ``--script`` whose last entry is one) says whether the object that the last edit places
+collides with what stood at its destination (``distance.placement``, clift_lattice_distance): on the lattice at
+``--placement_upsample`` times the grid, the moved content against the density of the scene before the paste.  One line reports
+``placement: collides on N cells, depth D`` (D: how many lattice steps the deepest overlapping point lies inside what was there) or
+``placement: touches|clear, gap G cells = W`` (the true distance to the rest of the scene, in lattice steps and in world units), and
+``placement.json`` in the output folder holds the numbers and the two world points.  With ``--settle`` the settled edit is checked.  The
+render itself does not change.
 """
 import argparse
 import functools
 import json
+import math
 import os
 import pickle
 import sys
@@ -223,10 +233,45 @@ def settle(model, renderer, edit, direction="-z", upsample=1, slack=0):
     return settled_edit(edit, found["offset"]), found
 
 
+PLACEMENT_WANTS_A_MOTION = ("--check_placement checks the object that a move or a copy places: give it with --op move|copy, or with a --script "
+                            "whose last entry is one")
+
+
+def check_placement_edit(edit):
+    """``SystemExit`` unless the last edit of ``edit`` is a copy or a move."""
+    if ed.as_program(edit)[-1].mode not in (ed.DUPLICATE, ed.MANIPULATE):
+        raise SystemExit(PLACEMENT_WANTS_A_MOTION)
+
+
+def placement_line(found):
+    """The one line of ``--check_placement`` for the dict of ``distance.placement``."""
+    if found["verdict"] == "collides":
+        return f"placement: collides on {found['overlap']} cells, depth {math.sqrt(found['depth2']):.2f}"
+    if found["gap2"] is None:
+        return f"placement: {found['verdict']}, nothing else in the scene"
+    world = math.sqrt(sum((a - b) ** 2 for a, b in zip(found["moved_point"], found["rest_point"])))
+    return f"placement: {found['verdict']}, gap {math.sqrt(found['gap2']):.2f} cells = {world:.4f}"
+
+
+def check_placement(model, renderer, edit, out, upsample=1, write=True):
+    """``--check_placement``: the dict of ``distance.placement`` for ``edit``; prints the one line and writes ``out``/placement.json."""
+    from contrastive_lift_amd import distance as dt
+    check_placement_edit(edit)
+    found = dt.placement(model, renderer, edit, upsample=int(upsample))
+    print(placement_line(found))
+    if write:
+        Path(out).mkdir(exist_ok=True, parents=True)
+        with open(Path(out) / "placement.json", "w") as f:
+            json.dump(found, f, indent=1)
+    return found
+
+
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
                           save_surface=False, surface_quantile=0.5, save_layers=False, cached_centroids_path=None, layers_level=0.5,
-                          layers_colour=False, layers_colour_rest=False, settle_options=None):
-    """``settle_options``: dict(direction, upsample, slack) of ``--settle``; the folder gets ``_settled`` behind its name."""
+                          layers_colour=False, layers_colour_rest=False, settle_options=None, placement_options=None):
+    """``settle_options``: dict(direction, upsample, slack) of ``--settle``; the folder gets ``_settled`` behind its name.
+    ``placement_options``: dict(upsample) of ``--check_placement``; the edit that is rendered (the settled one under ``--settle``) is
+    checked and ``placement.json`` written beside the frames; the render itself does not change."""
     if (layers_colour or layers_colour_rest) and not save_layers:
         raise ValueError("layers_colour needs save_layers")
     out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}{'_settled' if settle_options else ''}")
@@ -239,6 +284,8 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
         raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if settle_options:              # (every rank computes the same offset: integer tables of the same lattice)
         edit = settle(model, renderer, edit, **settle_options)[0]
+    if placement_options:           # (every rank computes the same integers; rank 0 writes)
+        check_placement(model, renderer, edit, out, write=rank == 0, **placement_options)
     if save_layers:
         table = rp.layers_table(config, scene, cached_centroids_path)
         table_edit = table.for_program(edit)
@@ -334,6 +381,12 @@ def build_parser():
     ap.add_argument("--settle_upsample", type=int, default=None, metavar="U", help="--settle: the lattice is the grid times this factor per axis (default 1)")
     ap.add_argument("--settle_slack", type=int, default=None, metavar="S",
                     help="--settle: count the faces up to S lattice steps further away than the first contact (0 .. 4, default 0)")
+    ap.add_argument("--check_placement", action="store_true",
+                    help="with --op move|copy, or a --script that ends in one: say whether the object that the last edit places collides with "
+                         "what stood there -- on how many lattice cells and how deep -- or how far it is from the rest of the scene (the true "
+                         "distance, not along an axis), and write placement.json beside the frames.  With --settle the settled edit is checked")
+    ap.add_argument("--placement_upsample", type=int, default=None, metavar="U",
+                    help="--check_placement: the lattice is the grid times this factor per axis (default 1)")
     return ap
 
 
@@ -360,6 +413,15 @@ def parse_args(argv=None):
             ap.error(f"--settle_upsample must be >= 1 (got {args.settle_upsample})")
         if not 0 <= args.settle_slack <= 4:
             ap.error(f"--settle_slack must be 0 .. 4 (got {args.settle_slack})")
+    if not args.check_placement:
+        if args.placement_upsample is not None:
+            ap.error("--placement_upsample needs --check_placement")
+    else:
+        if args.script is None and args.op not in ("move", "copy"):
+            ap.error(PLACEMENT_WANTS_A_MOTION)
+        args.placement_upsample = 1 if args.placement_upsample is None else args.placement_upsample
+        if args.placement_upsample < 1:
+            ap.error(f"--placement_upsample must be >= 1 (got {args.placement_upsample})")
     if args.follow_shape and (args.save_surface or args.save_layers):
         raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if args.script is not None and (args.instance is not None or args.op is not None):
@@ -401,12 +463,15 @@ def main(argv=None):
         the_edit = the_edit(None, None, None)
         if args.settle is not None:
             check_settle(the_edit)
+        if args.check_placement:
+            check_placement_edit(the_edit)
     settle_options = None if args.settle is None else dict(direction=args.settle, upsample=args.settle_upsample, slack=args.settle_slack)
     print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
                                 save_surface=args.save_surface, surface_quantile=args.surface_quantile, save_layers=args.save_layers,
                                 cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level,
                                 layers_colour=args.layers_colour, layers_colour_rest=args.layers_colour_rest,
-                                **({} if settle_options is None else {"settle_options": settle_options})))
+                                **({} if settle_options is None else {"settle_options": settle_options}),
+                                **({"placement_options": dict(upsample=args.placement_upsample)} if args.check_placement else {})))
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@
                                      [--cached_centroids_path all_centroids.pkl] [--split_instances] [--save_voxel_cloud]
                                      [--min_component VOXELS] [--keep_largest K] [--connectivity {6,kuhn,26}] [--split_disconnected [MIN_VOXELS]]
                                      [--relations [--relations_gap 1] [--up_axis +z] [--relations_min_faces 4]]
-                                     [--clearance [--clearance_slack 0]]
+                                     [--clearance [--clearance_slack 0]] [--separation [--separation_max_cells N]]
                                      [--bboxes bboxes.pkl (--instance ID --op delete|extract|copy|move [--translate x y z] [--rotate_deg rx ry rz]
                                                            [--pad 0.0] | --script edits.json)]
 
@@ -65,6 +65,14 @@ of unbounded length, where ``--relations_gap`` stops after 4 points).  ``clearan
 the raw tables pair, travel and landing and the node list, ``clearance.json`` (``clearance_edit_<tag>.json``) per node and direction the
 steps, the distance, the nodes it would then rest on with their face counts (``--clearance_slack S``: up to S steps further away) and the
 steps to the lattice border (``clearance.Clearance``).  ``relations.json`` and ``relations.npz`` do not change.
+
+``--separation`` gives the true distance between every two nodes of that labelled lattice (the labelling is shared with ``--relations`` and
+``--clearance``), diagonal neighbours included, which the axis looks of the two other stages cannot see (``distance.separation``,
+clift_lattice_distance: one exact Euclidean distance transform per node, at most 255 nodes).  ``separation.npz``
+(``separation_edit_<tag>.npz`` under an edit) holds the raw tables gap2, at and to and the node list, ``separation.json``
+(``separation_edit_<tag>.json``) per node its nearest other node and per pair of nodes the distance in lattice steps and in world units
+with the two points (``distance.Separation``; ``--separation_max_cells N``: only the pairs at most N steps apart).  The other files do not
+change.
 """
 import argparse
 import os
@@ -82,6 +90,7 @@ sys.path.insert(0, HERE)
 
 import render_panopli as rp                                           # noqa: E402
 from contrastive_lift_amd import clearance as clr                     # noqa: E402
+from contrastive_lift_amd import distance as dt                       # noqa: E402
 from contrastive_lift_amd import components as cc                     # noqa: E402
 from contrastive_lift_amd import mesh as cm                           # noqa: E402
 from contrastive_lift_amd import relations as rel                     # noqa: E402
@@ -213,6 +222,31 @@ def write_clearance(out, stem, c):
         f.write(c["summary"].to_json(indent=1))
 
 
+def scene_separation(renderer, sem, ids, max_cells=None, related=None):
+    """The true gaps between the nodes of a labelled lattice (``lattice_nodes``; ``ids`` may be the split ids) -> dict(tables, nodes, key,
+    summary).  ``related``: a result of ``scene_relations`` or ``scene_clearance`` on the same labels -- its keys and nodes are used."""
+    key, nodes = (related["key"], related["nodes"]) if related is not None else rel.node_keys(sem, ids)
+    if len(nodes) + 1 > dt.MAX_SEPARATION_KEYS:
+        raise SystemExit(f"--separation: {len(nodes)} (class, instance) nodes, at most {dt.MAX_SEPARATION_KEYS - 1} get a transform each -- raise "
+                         f"--min_component or the MIN_VOXELS of --split_disconnected on a frothy scene")
+    tables = dt.separation(key, n_keys=len(nodes) + 1)
+    summary = dt.Separation.from_tables(tables, nodes, renderer.lattice_ticks(key.shape), max_cells=max_cells)
+    return dict(tables=tables, nodes=nodes, key=key, summary=summary)
+
+
+def separation_stem(edit_tag=None):
+    """File stem of the separation: ``separation``, or ``separation_edit_<tag>`` for an edited scene; ``<stem>.npz`` and ``<stem>.json``."""
+    return "separation" if edit_tag is None else f"separation_edit_{edit_tag}"
+
+
+def write_separation(out, stem, s):
+    """``<stem>.npz``: the raw tables gap2, at, to and the node list (K, 2) = (class, instance) of keys 1..K; ``<stem>.json``: the summary."""
+    arrays = {k: s["tables"][k].cpu().numpy() for k in ("gap2", "at", "to")}
+    np.savez(Path(out) / f"{stem}.npz", nodes=np.asarray(s["nodes"], np.int64).reshape(-1, 2), **arrays)
+    with open(Path(out) / f"{stem}.json", "w") as f:
+        f.write(s["summary"].to_json(indent=1))
+
+
 def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity, return_lattice=False):
     """-> (vertex ids after the split, table {fresh id: parent}).  A vertex takes the new id of the inside endpoint of its edge when its own
     id equals that point's original id; otherwise it keeps its id.  Fresh ids start above every id in use, the vertices' included (a vertex
@@ -226,15 +260,16 @@ def split_vertex_ids(inst, keys, sigma, level, ids, min_voxels, connectivity, re
 
 
 def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=0, keep_largest=None, connectivity="kuhn",
-                   split_disconnected=None, edit=None, relations=None, clearance=None):
+                   split_disconnected=None, edit=None, relations=None, clearance=None, separation=None):
     """Everything between the density lattice and the files: (components) - isosurface - label_vertices - (split), each closed by a mark
     of ``timer``.  ``edit``: sigma is the lattice of the edited scene (``get_dense_sigma(edit=)``); vertices and lattice points are then
     labelled where their content came from.  -> dict(verts, faces, normals, sem, inst, rgb, sigma (as meshed), info (of filter_components, or None), table (of
     split_disconnected, or None)).  ``relations``: dict(gap, up, min_faces) adds the stage "relations" and the key ``relations``
     (``scene_relations`` of the lattice as meshed; with ``split_disconnected`` on the split ids).  ``clearance``: dict(slack) adds the stage
-    "clearance" and the key ``clearance`` (``scene_clearance`` of the same labels; with ``relations`` the labelling is shared)."""
+    "clearance" and the key ``clearance`` (``scene_clearance`` of the same labels; with ``relations`` the labelling is shared).
+    ``separation``: dict(max_cells) adds the stage "separation" and the key ``separation`` (``scene_separation``, the labelling shared)."""
     info = table = None
-    labelled = relations is not None or clearance is not None
+    labelled = relations is not None or clearance is not None or separation is not None
     if int(min_component or 0) > 0 or keep_largest is not None:
         sigma, info = cc.filter_components(sigma, level, min_voxels=min_component, keep_largest=keep_largest, connectivity=connectivity)
         timer.done("components")
@@ -257,13 +292,17 @@ def surface_stages(model, renderer, sigma, level, things, centroids, use_delta, 
     if clearance is not None:
         out["clearance"] = scene_clearance(renderer, p_sem, split[0] if split_disconnected is not None else p_ids, related=out.get("relations"), **clearance)
         timer.done("clearance")
+    if separation is not None:
+        out["separation"] = scene_separation(renderer, p_sem, split[0] if split_disconnected is not None else p_ids,
+                                             related=out.get("relations") or out.get("clearance"), **separation)
+        timer.done("separation")
     return out
 
 
 def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroids_path=None, split_instances=False, save_voxel_cloud=False,
                  device="cuda:0", min_component=0, keep_largest=None, connectivity="kuhn", split_disconnected=None, edit=None, edit_tag=None, relations=None,
-                 clearance=None):
-    """``relations``: dict(gap, up, min_faces) of ``--relations``; ``clearance``: dict(slack) of ``--clearance``.  ``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
+                 clearance=None, separation=None):
+    """``relations``: dict(gap, up, min_faces) of ``--relations``; ``clearance``: dict(slack) of ``--clearance``; ``separation``: dict(max_cells) of ``--separation``.``edit`` (an ``edit.Edit`` / ``EditProgram``) with its ``edit_tag`` (``edit_tag_of``): mesh the edited scene into ``mesh_edit_<tag>.ply``.
     ``edit`` may be a callable ``edit(config, scene, model, renderer)`` that resolves it once the field is loaded (``--follow_shape``)."""
     if edit is not None and save_voxel_cloud:
         raise SystemExit(VOXEL_CLOUD_WITH_EDIT)
@@ -288,7 +327,7 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
     timer.done("dense_sigma")
     m = surface_stages(model, renderer, sigma, level, things, centroids, use_delta, timer, min_component=min_component, keep_largest=keep_largest,
                        connectivity=connectivity, split_disconnected=split_disconnected, edit=edit, **({} if relations is None else {"relations": relations}),
-                       **({} if clearance is None else {"clearance": clearance}))
+                       **({} if clearance is None else {"clearance": clearance}), **({} if separation is None else {"separation": separation}))
     verts, faces, normals, sem, inst, rgb = (m[k] for k in ("verts", "faces", "normals", "sem", "inst", "rgb"))
     times = timer.report()
     print(f"sigma lattice {tuple(sigma.shape)}, level {level:.6g}: {verts.shape[0]} vertices, {faces.shape[0]} faces, "
@@ -309,6 +348,12 @@ def extract_mesh(config, upsample=2, alpha_level=0.5, level=None, cached_centroi
         c = m["clearance"]["summary"]
         print(f"clearance (slack {clearance['slack']}): {len(c.nodes)} nodes, "
               f"{sum(d['steps'] is not None for n in c.nodes for d in n['directions'].values())} of {6 * len(c.nodes)} looks end at another node")
+    if separation is not None:
+        write_separation(out, separation_stem(edit_tag if edit is not None else None), m["separation"])
+        s = m["separation"]["summary"]
+        closest = min(s.pairs, key=lambda p: p["gap2"], default=None)
+        print(f"separation: {len(s.nodes)} nodes, {len(s.pairs)} pairs" + (f" within {s.max_cells:g} cells" if s.max_cells is not None else "")
+              + (f", the closest {closest['a']} - {closest['b']} at {closest['cells']:.2f} cells = {closest['distance']:.4f}" if closest else ""))
     if split_instances:
         f_inst = inst[faces.long()]                                   # (F, 3)
         for i in torch.unique(inst).tolist():
@@ -400,6 +445,13 @@ def clearance_options(args):
     return dict(slack=0 if args.clearance_slack is None else args.clearance_slack)
 
 
+def separation_options(args):
+    """What ``extract_mesh(separation=)`` takes for the parsed command line; None without ``--separation``."""
+    if not args.separation:
+        return None
+    return dict(max_cells=args.separation_max_cells)
+
+
 class _Parser(argparse.ArgumentParser):
     """The cross-argument rules of the edit flags, checked where the arguments are parsed."""
 
@@ -413,6 +465,10 @@ class _Parser(argparse.ArgumentParser):
             self.error("--clearance_slack needs --clearance")
         if a.clearance:
             a.clearance_slack = 0 if a.clearance_slack is None else a.clearance_slack
+        if a.separation_max_cells is not None and not a.separation:
+            self.error("--separation_max_cells needs --separation")
+        if a.separation_max_cells is not None and not a.separation_max_cells >= 0.0:
+            self.error(f"--separation_max_cells must be >= 0 (got {a.separation_max_cells:g})")
         if a.script is None and (a.instance is None) != (a.op is None):
             self.error("--instance and --op come together")
         if edit_tag_of(a) is None:
@@ -471,6 +527,12 @@ def build_parser():
                          "face counts, and the steps to the lattice border (DESIGN.md 6n); the nodes are those of --relations")
     ap.add_argument("--clearance_slack", type=int, default=None, choices=list(range(clr.MAX_SLACK + 1)), metavar="S",
                     help="--clearance: count the faces up to S lattice steps further away than the first contact (0 .. %d, default 0)" % clr.MAX_SLACK)
+    ap.add_argument("--separation", action="store_true",
+                    help="also write separation.npz (raw tables) and separation.json next to the mesh: the true distance between every two "
+                         "(class, instance) nodes -- diagonal neighbours included, which the axis looks of --relations and --clearance do not "
+                         "see --, in lattice steps and as a world distance with the two points (DESIGN.md 6o); the nodes are those of --relations")
+    ap.add_argument("--separation_max_cells", type=float, default=None, metavar="N",
+                    help="--separation: list only the pairs at most N lattice steps apart in separation.json (default: every pair)")
     ap.add_argument("--image_dim", type=int, nargs=2, default=[256, 384], help="as render_panopli.py (the scene loader wants it)")
     ap.add_argument("--bboxes", type=str, default=None, help="bboxes.pkl of inference/fit_bboxes.py: mesh the scene under an edit (with --instance / --op or --script)")
     ap.add_argument("--instance", type=int, default=None, help="instance id (a key of bboxes.pkl) the edit acts on")
@@ -497,4 +559,5 @@ if __name__ == "__main__":
                        cached_centroids_path=args.cached_centroids_path, split_instances=args.split_instances,
                        save_voxel_cloud=args.save_voxel_cloud, min_component=args.min_component, keep_largest=args.keep_largest,
                        connectivity=args.connectivity, split_disconnected=args.split_disconnected, edit=the_edit, edit_tag=the_tag,
-                       relations=relations_options(args), **({} if clearance_options(args) is None else {"clearance": clearance_options(args)}))[0])
+                       relations=relations_options(args), **({} if clearance_options(args) is None else {"clearance": clearance_options(args)}),
+                       **({} if separation_options(args) is None else {"separation": separation_options(args)}))[0])
