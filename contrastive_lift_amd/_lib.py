@@ -163,6 +163,7 @@ _SIGNATURES = {
     "clift_lattice_relations": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "clift_lattice_clearance": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P], C.c_int),
     "clift_lattice_distance": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], C.c_int),
+    "clift_lattice_placement": ([_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "clift_density_grad_points": ([_P, _P, _I, _L, _F, _P, _P, _P], C.c_int),
     "clift_ray_surface": ([_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _F, _P, _P, _P, _P], C.c_int),
     "clift_sample_slots": ([_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _L, _P, _P], C.c_int),

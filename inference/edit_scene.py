@@ -8,6 +8,7 @@
                                    [--follow_shape --cached_centroids_path C [--shape_grid 32] [--shape_grow 1] [--shape_alpha 0.5]]
                                    [--settle [AXIS] [--settle_upsample 1] [--settle_slack 0]]
                                    [--check_placement [--placement_upsample 1]]
+                                   [--snap_placement [AXIS] [--snap_upsample 1] [--snap_min_support 1]]
     python inference/edit_scene.py --ckpt_path ... --bboxes bboxes.pkl --script edits.json [--render_trajectory] ...
 
 ``bboxes.pkl`` comes from ``inference/fit_bboxes.py`` (one oriented box per instance id).  ``copy`` and ``move`` are rigid: the box content
@@ -61,6 +62,15 @@ collides with what stood at its destination (``distance.placement`
 ``placement: touches|clear, gap G cells = W`` (the true distance to the rest of the scene, in lattice steps and in world units), and
 ``placement.json`` in the output folder holds the numbers and the two world points.  With ``--settle`` the settled edit is checked.  The
 render itself does not change.
+
+``--snap_placement [AXIS]`` (with ``--op move|copy``, or a ``--script`` whose last entry is one; not together with ``--settle``) moves the
+object that the last edit places to the NEAREST translation at which it collides with nothing and stands (DESIGN.md 6p;
+``placement.snap_offset``, clift_lattice_placement): on the lattice at ``--snap_upsample`` times the grid one kernel counts, for every
+translation of the moved content, the cells that collide with what stood there before the paste and the faces that look along AXIS (default
+-z) onto it; the nearest translation without a collision and with at least ``--snap_min_support`` such faces is added to the last edit as
+``--settle`` adds its drop.  One line reports ``snapped by (dx, dy, dz) steps = W onto F faces (was: collides on N cells)`` (W: the length
+of the world translation) or ``not snapped: no free supported position`` (the edit is then rendered as given); the output folder gets
+``_snapped`` behind its name and ``snap.json`` holds the numbers.  With ``--check_placement`` the snapped edit is checked.
 """
 import argparse
 import functools
@@ -233,6 +243,39 @@ def settle(model, renderer, edit, direction="-z", upsample=1, slack=0):
     return settled_edit(edit, found["offset"]), found
 
 
+SNAP_WANTS_A_MOTION = ("--snap_placement moves the object that a move or a copy places: give it with --op move|copy, or with a --script whose last "
+                       "entry is one")
+SNAP_WITH_SETTLE = "--snap_placement cannot be combined with --settle: the snap chooses the whole translation, the drop along an axis included"
+
+
+def check_snap(edit):
+    """``SystemExit`` unless the last edit of ``edit`` is a copy or a move."""
+    if ed.as_program(edit)[-1].mode not in (ed.DUPLICATE, ed.MANIPULATE):
+        raise SystemExit(SNAP_WANTS_A_MOTION)
+
+
+def snap_line(found):
+    """The one line of ``--snap_placement`` for the dict of ``placement.snap_offset``."""
+    if not found["found"]:
+        return "not snapped: no free supported position"
+    was = f"collides on {found['overlap_before']} cells" if found["overlap_before"] > 0 else f"free on {found['support_before']} faces"
+    dx, dy, dz = (int(x) for x in found["steps"])
+    return f"snapped by ({dx}, {dy}, {dz}) steps = {math.sqrt(sum(float(x) ** 2 for x in found['offset'])):.4f} onto {found['support']} faces (was: {was})"
+
+
+def snap(model, renderer, edit, out, direction="-z", upsample=1, min_support=1, write=True):
+    """``--snap_placement``: (the edit to render, the dict of ``placement.snap_offset``); prints the one line and writes ``out``/snap.json."""
+    from contrastive_lift_amd import placement as pm
+    check_snap(edit)
+    found = pm.snap_offset(model, renderer, edit, direction=direction, upsample=int(upsample), min_support=int(min_support))
+    print(snap_line(found))
+    if write:
+        Path(out).mkdir(exist_ok=True, parents=True)
+        with open(Path(out) / "snap.json", "w") as f:
+            json.dump({k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in found.items()}, f, indent=1)
+    return (settled_edit(edit, found["offset"]) if found["found"] else edit), found
+
+
 PLACEMENT_WANTS_A_MOTION = ("--check_placement checks the object that a move or a copy places: give it with --op move|copy, or with a --script "
                             "whose last entry is one")
 
@@ -268,13 +311,14 @@ def check_placement(model, renderer, edit, out, upsample=1, write=True):
 
 def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender", test_only=True, device="cuda:0", weight_thres=0.0,
                           save_surface=False, surface_quantile=0.5, save_layers=False, cached_centroids_path=None, layers_level=0.5,
-                          layers_colour=False, layers_colour_rest=False, settle_options=None, placement_options=None):
+                          layers_colour=False, layers_colour_rest=False, settle_options=None, placement_options=None, snap_options=None):
     """``settle_options``: dict(direction, upsample, slack) of ``--settle``; the folder gets ``_settled`` behind its name.
     ``placement_options``: dict(upsample) of ``--check_placement``; the edit that is rendered (the settled one under ``--settle``) is
-    checked and ``placement.json`` written beside the frames; the render itself does not change."""
+    checked and ``placement.json`` written beside the frames; the render itself does not change.
+    ``snap_options``: dict(direction, upsample, min_support) of ``--snap_placement``; the folder gets ``_snapped`` behind its name."""
     if (layers_colour or layers_colour_rest) and not save_layers:
         raise ValueError("layers_colour needs save_layers")
-    out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}{'_settled' if settle_options else ''}")
+    out = Path(f"{rp.output_dirname(config, trajectory_name, test_only, False, False)}_edit_{tag}{'_settled' if settle_options else ''}{'_snapped' if snap_options else ''}")
     device, rank = rp.distributed_device(device)
     scene, model, renderer = rp.load_for_inference(config, device)
     H, W = scene.image_dim
@@ -284,6 +328,8 @@ def edit_scene_checkpoint(config, edit, tag, trajectory_name="trajectory_blender
         raise SystemExit(SHAPE_WITH_SURFACE_OR_LAYERS)
     if settle_options:              # (every rank computes the same offset: integer tables of the same lattice)
         edit = settle(model, renderer, edit, **settle_options)[0]
+    if snap_options:                # (every rank computes the same integers; rank 0 writes)
+        edit = snap(model, renderer, edit, out, write=rank == 0, **snap_options)[0]
     if placement_options:           # (every rank computes the same integers; rank 0 writes)
         check_placement(model, renderer, edit, out, write=rank == 0, **placement_options)
     if save_layers:
@@ -387,6 +433,13 @@ def build_parser():
                          "distance, not along an axis), and write placement.json beside the frames.  With --settle the settled edit is checked")
     ap.add_argument("--placement_upsample", type=int, default=None, metavar="U",
                     help="--check_placement: the lattice is the grid times this factor per axis (default 1)")
+    ap.add_argument("--snap_placement", type=str, nargs="?", const="-z", default=None, metavar="AXIS",
+                    help="with --op move|copy, or a --script that ends in one: move the object that the last edit places to the nearest "
+                         "translation at which it collides with nothing and rests on faces that look along AXIS (one of +x -x +y -y +z -z, "
+                         "default -z), report the steps and the faces, write snap.json and render into ..._snapped.  Not together with --settle")
+    ap.add_argument("--snap_upsample", type=int, default=None, metavar="U", help="--snap_placement: the lattice is the grid times this factor per axis (default 1)")
+    ap.add_argument("--snap_min_support", type=int, default=None, metavar="F",
+                    help="--snap_placement: the faces along AXIS that a position needs to count as supported (>= 1, default 1)")
     return ap
 
 
@@ -394,8 +447,8 @@ def parse_args(argv=None):
     ap = build_parser()
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                                    # "--settle -z": argparse would read the value as an option
-        if argv[i] == "--settle" and argv[i + 1] in UP_AXES:
-            argv[i:i + 2] = [f"--settle={argv[i + 1]}", None]
+        if argv[i] in ("--settle", "--snap_placement") and argv[i + 1] in UP_AXES:
+            argv[i:i + 2] = [f"{argv[i]}={argv[i + 1]}", None]
     args = ap.parse_args([x for x in argv if x is not None])
     rp.check_layers_colour_arguments(ap, args)
     if args.settle is None:
@@ -413,6 +466,23 @@ def parse_args(argv=None):
             ap.error(f"--settle_upsample must be >= 1 (got {args.settle_upsample})")
         if not 0 <= args.settle_slack <= 4:
             ap.error(f"--settle_slack must be 0 .. 4 (got {args.settle_slack})")
+    if args.snap_placement is None:
+        for flag in ("snap_upsample", "snap_min_support"):
+            if getattr(args, flag) is not None:
+                ap.error(f"--{flag} needs --snap_placement")
+    else:
+        if args.snap_placement not in UP_AXES:
+            ap.error(f"--snap_placement: AXIS is one of {' '.join(UP_AXES)} (got {args.snap_placement!r})")
+        if args.settle is not None:
+            ap.error(SNAP_WITH_SETTLE)
+        if args.script is None and args.op not in ("move", "copy"):
+            ap.error(SNAP_WANTS_A_MOTION)
+        args.snap_upsample = 1 if args.snap_upsample is None else args.snap_upsample
+        args.snap_min_support = 1 if args.snap_min_support is None else args.snap_min_support
+        if args.snap_upsample < 1:
+            ap.error(f"--snap_upsample must be >= 1 (got {args.snap_upsample})")
+        if args.snap_min_support < 1:
+            ap.error(f"--snap_min_support must be >= 1 (got {args.snap_min_support})")
     if not args.check_placement:
         if args.placement_upsample is not None:
             ap.error("--placement_upsample needs --check_placement")
@@ -465,13 +535,17 @@ def main(argv=None):
             check_settle(the_edit)
         if args.check_placement:
             check_placement_edit(the_edit)
+        if args.snap_placement is not None:
+            check_snap(the_edit)
     settle_options = None if args.settle is None else dict(direction=args.settle, upsample=args.settle_upsample, slack=args.settle_slack)
     print(edit_scene_checkpoint(cfg, the_edit, tag, test_only=not args.render_trajectory, weight_thres=args.weight_thres,
                                 save_surface=args.save_surface, surface_quantile=args.surface_quantile, save_layers=args.save_layers,
                                 cached_centroids_path=args.cached_centroids_path, layers_level=args.layers_level,
                                 layers_colour=args.layers_colour, layers_colour_rest=args.layers_colour_rest,
                                 **({} if settle_options is None else {"settle_options": settle_options}),
-                                **({"placement_options": dict(upsample=args.placement_upsample)} if args.check_placement else {})))
+                                **({"placement_options": dict(upsample=args.placement_upsample)} if args.check_placement else {}),
+                                **({} if args.snap_placement is None else
+                                   {"snap_options": dict(direction=args.snap_placement, upsample=args.snap_upsample, min_support=args.snap_min_support)})))
 
 
 if __name__ == "__main__":
