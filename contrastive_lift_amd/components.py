@@ -11,17 +11,15 @@ tetrahedron are Kuhn edges, so with "kuhn" a face of the mesh belongs to one com
 a component removes whole closed pieces of the surface and touches nothing else.
 
 ``backend="device"`` is the kernel plus torch on the device; ``backend="host"`` gives the same integers through scipy.ndimage.label (one
-call per distinct key) for machines and tests without a GPU.
+call per distinct key) for machines and tests without a GPU.  What the lattice modules share is in ``lattice``.
 """
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, lattice
 
-CC_LIMIT = 2 ** 31
 KUHN_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))       # the mesher's edge classes, in its order
 _CONNECTIVITY = {6: 6, 14: 14, 26: 26, "6": 6, "14": 14, "26": 26, "kuhn": 14}
-BACKENDS = ("device", "host")
 
 
 def connectivity_code(connectivity):
@@ -45,23 +43,6 @@ def structure(connectivity):
     return s
 
 
-def _check_backend(backend):
-    if backend not in BACKENDS:
-        raise ValueError(f"backend must be 'device' or 'host' (got {backend!r})")
-    return backend
-
-
-def _as_key(key):
-    """-> (int32 contiguous tensor (n0, n1, n2), on the caller's device)."""
-    if not torch.is_tensor(key):
-        key = torch.from_numpy(np.ascontiguousarray(key))
-    if key.dim() != 3:
-        raise ValueError(f"key must be (n0, n1, n2), got {tuple(key.shape)}")
-    if key.dtype.is_floating_point or key.dtype.is_complex:
-        raise ValueError(f"key must be bool or integer, got {key.dtype}")
-    return key.to(torch.int32).contiguous()
-
-
 def _roots_host(key, code):
     from scipy import ndimage
     k = key.cpu().numpy()
@@ -81,18 +62,14 @@ def _roots_host(key, code):
 
 def component_roots(key, connectivity="kuhn", backend="device"):
     """root (n0, n1, n2) int32: the smallest linear index of any point of the component, -1 where key == 0."""
-    code, key = connectivity_code(connectivity), _as_key(key)
-    n0, n1, n2 = (int(x) for x in key.shape)
-    if n0 * n1 * n2 >= CC_LIMIT:
-        raise _lib.CliftError(f"component_roots: {n0 * n1 * n2} lattice points, must be < 2^31")
-    if key.numel() == 0:
+    code, key = connectivity_code(connectivity), lattice.as_lattice(key, "component_roots")
+    if key.numel() == 0:                                                     # (an empty lattice has no component: no error here)
         return torch.zeros_like(key)
-    if _check_backend(backend) == "host":
+    if lattice.check_backend(backend) == "host":
         return _roots_host(key, code)
-    if not key.is_cuda:
-        raise _lib.CliftError(f"component_roots: backend='device' wants the key on the GPU, got {key.device}")
+    lattice.require_device(key, "component_roots")
     root = torch.empty_like(key)
-    _lib.call("clift_cc_label", _lib.ptr(key), n0, n1, n2, code, _lib.ptr(root), _lib.stream())
+    _lib.call("clift_cc_label", _lib.ptr(key), *key.shape, code, _lib.ptr(root), _lib.stream())
     return root
 
 

@@ -14,11 +14,11 @@
 //
 // Two launches of ONE body: pass 1 takes the minima (pair, travel), pass 2 walks the same events again and counts those with
 // g <= travel[u][d] + slack (landing).  Events are rare but skewed (one floor owns most): equal codes are folded inside the wave before any
-// atomic -- pass 1 with a wave minimum, pass 2 with a popcount (the leader / readlane / ballot loop of relations.hip) -- and with
+// atomic -- pass 1 with a wave minimum, pass 2 with a popcount (wave_fold_equal of clift_dev.h) -- and with
 // n_keys <= CLIFT_REL_LDS_KEYS the block works into a private table in LDS and sends its touched entries to memory once, when it ends; above
 // it the folded atomics go straight to memory.  Only integer vector atomics: ds_min_i32, global_atomic_smin / _add, and flat_atomic_add /
 // _smin where one atomic serves a destination picked at run time (the block's table or memory; pair or travel).
-#include "clift_dev.h"
+#include "keyed_lattice.h"
 
 #define CLR_THREADS 256
 #define CLR_WAVES (CLR_THREADS / 64)
@@ -33,12 +33,6 @@ struct ClrArgs {
     long w0, w1, items;                                                               // column groups along axis 0, along axis 1; all items
 };
 
-__device__ __forceinline__ int clr_wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-    return v;
-}
-
 // One event per lane at most (`event`: keys u at the lower and v at the upper end of an empty run of `run` points along axis a).  Wave
 // collective: every lane of the wave calls it.  tab: the block's table in LDS, or nullptr.
 template <bool SECOND>
@@ -48,39 +42,27 @@ __device__ __forceinline__ void clr_emit(const ClrArgs& g, int* tab, bool event,
     const int fwd = event ? (u * nk + v) * 6 + 2 * a : -1, bwd = event ? (v * nk + u) * 6 + 2 * a + 1 : -1;
     if (!SECOND) {
         // fwd names the unordered event: the lanes of one fwd code are the lanes of its bwd code
-        unsigned long long todo = __ballot(fwd >= 0);
-        while (todo != 0ull) {
-            const int leader = __ffsll(todo) - 1;
-            const int c = __builtin_amdgcn_readlane(fwd, leader);
-            const unsigned long long same = __ballot(fwd == c);
-            const int m = clr_wave_min(fwd == c ? run : CLIFT_CLR_NONE);
-            if (lane == leader) {
-                if (tab) {
-                    atomicMin(&tab[fwd], m); atomicMin(&tab[bwd], m);
-                    atomicMin(&tab[np + u * 6 + 2 * a], m); atomicMin(&tab[np + v * 6 + 2 * a + 1], m);
-                } else {
-                    atomicMin(g.pair + fwd, m); atomicMin(g.pair + bwd, m);
-                    atomicMin(g.travel + u * 6 + 2 * a, m); atomicMin(g.travel + v * 6 + 2 * a + 1, m);
-                }
+        wave_fold_equal(fwd, [&](int c, unsigned long long, int leader) {
+            const int m = wave_min_i(fwd == c ? run : CLIFT_CLR_NONE);
+            if (lane != leader) return;                                               // (after the wave minimum)
+            if (tab) {
+                atomicMin(&tab[fwd], m); atomicMin(&tab[bwd], m);
+                atomicMin(&tab[np + u * 6 + 2 * a], m); atomicMin(&tab[np + v * 6 + 2 * a + 1], m);
+            } else {
+                atomicMin(g.pair + fwd, m); atomicMin(g.pair + bwd, m);
+                atomicMin(g.travel + u * 6 + 2 * a, m); atomicMin(g.travel + v * 6 + 2 * a + 1, m);
             }
-            todo &= ~same;
-        }
+        });
     } else {
         // travel is final (pass 1 has ended); an event of (u, d) exists, so travel[u][d] <= run < 2^31 - 4
         int code[2];
         code[0] = event && run <= g.travel[u * 6 + 2 * a] + g.slack ? fwd : -1;
         code[1] = event && run <= g.travel[v * 6 + 2 * a + 1] + g.slack ? bwd : -1;
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            unsigned long long todo = __ballot(code[s] >= 0);
-            while (todo != 0ull) {
-                const int leader = __ffsll(todo) - 1;
-                const int c = __builtin_amdgcn_readlane(code[s], leader);
-                const unsigned long long same = __ballot(code[s] == c);
+        for (int s = 0; s < 2; ++s)
+            wave_fold_equal(code[s], [&](int c, unsigned long long same, int leader) {
                 if (lane == leader) atomicAdd(tab ? &tab[c] : g.landing + c, __popcll(same));
-                todo &= ~same;
-            }
-        }
+            });
     }
 }
 
@@ -182,10 +164,7 @@ __global__ __launch_bounds__(CLR_THREADS) void k_lattice_clearance(const ClrArgs
 
 extern "C" int clift_lattice_clearance(const int* key, int n0, int n1, int n2, int n_keys, int slack, int* pair, int* travel, int* landing,
                                        int* rejected, clift_stream_t s) {
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_lattice_clearance: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
-    const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < CLIFT_ISO_LIMIT, "clift_lattice_clearance: %ld lattice points (%d x %d x %d), must be < 2^31", total, n0, n1, n2);
-    CLIFT_REQUIRE(n_keys >= 1 && n_keys <= CLIFT_REL_MAX_KEYS, "clift_lattice_clearance: n_keys must be 1 .. %d (got %d)", CLIFT_REL_MAX_KEYS, n_keys);
+    if (keyed_lattice_check("clift_lattice_clearance", n0, n1, n2, 0, n_keys, CLIFT_REL_MAX_KEYS)) return 1;
     CLIFT_REQUIRE(slack >= 0 && slack <= CLIFT_CLR_MAX_SLACK, "clift_lattice_clearance: slack must be 0 .. %d (got %d)", CLIFT_CLR_MAX_SLACK, slack);
     CLIFT_REQUIRE(key && pair && travel && landing && rejected, "clift_lattice_clearance: NULL device buffer");
     const hipStream_t st = as_stream(s);
@@ -205,8 +184,7 @@ extern "C" int clift_lattice_clearance(const int* key, int n0, int n1, int n2, i
     g.w0 = n0 > 1 ? ((long)n1 * n2 + 63) / 64 : 0;                                    // a column of one point holds no event
     g.w1 = n1 > 1 ? ((long)n0 * n2 + 63) / 64 : 0;
     g.items = g.w0 + g.w1 + (long)n0 * n1;                                            // the rows are always walked: they count the rejected keys
-    const long want = (long)clift_persistent_cus() * 4, need = (g.items + CLR_WAVES - 1) / CLR_WAVES;
-    const int blocks = (int)(need < want ? need : want);
+    const int blocks = wave_item_blocks(g.items, CLR_WAVES, 4);
     const size_t lds1 = g.lds ? (size_t)(n_pair + n_travel) * sizeof(int) : 0, lds2 = g.lds ? (size_t)n_pair * sizeof(int) : 0;
     k_lattice_clearance<false><<<blocks, CLR_THREADS, lds1, st>>>(g);
     k_lattice_clearance<true><<<blocks, CLR_THREADS, lds2, st>>>(g);

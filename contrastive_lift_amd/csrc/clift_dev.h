@@ -28,6 +28,11 @@ static inline hipStream_t as_stream(clift_stream_t s) { return reinterpret_cast<
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // row ranges of a persistent launch over the CUs such launches may use (per_cu blocks on each)
 static inline RowRanges persistent_ranges(long rows, int ROWS, int per_cu = 1) { return row_ranges(rows, ROWS, clift_persistent_cus(), per_cu); }
+// blocks of a fixed grid whose waves take `items` wave items with a stride of the grid's wave count: no more than there is work for
+static inline int wave_item_blocks(long items, int waves_per_block, int blocks_per_cu) {
+    const long need = (items + waves_per_block - 1) / waves_per_block, want = (long)clift_persistent_cus() * blocks_per_cu;
+    return (int)(need < want ? need : want);
+}
 
 // ----------------------------------------------------------------------------- kernel-argument mirrors
 struct MarchP {
@@ -128,6 +133,36 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
     return v;
+}
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+// Fold the equal codes of a wave (code < 0: this lane has none) before an atomic: the lowest lane that still holds an unserved code is the
+// leader, its code is broadcast (v_readlane), a ballot finds the lanes that share it, and f(c, same, leader) runs once per distinct code c --
+// the leader alone then adds popcount(same), or a wave minimum over the lanes of `same`.  A wave of one code costs one trip, 64 distinct codes
+// cost 64.  Every lane of the wave must call it.  f runs wave-uniformly and may hold wave collectives of its own (clearance.hip takes a
+// wave minimum inside it), so it must not leave early on a lane-dependent condition before one.  Each trip clears at least the leader's bit
+// from `todo`: the loop ends.
+template <class F>
+__device__ __forceinline__ void wave_fold_equal(int code, F&& f) {
+    unsigned long long todo = __ballot(code >= 0);                                     // wave-uniform: every lane walks the loop
+    while (todo != 0ull) {
+        const int leader = __ffsll(todo) - 1;
+        const int c = __builtin_amdgcn_readlane(code, leader);
+        const unsigned long long same = __ballot(code == c);
+        f(c, same, leader);
+        todo &= ~same;
+    }
 }
 // inclusive scans over the wave, lane 0 first
 __device__ __forceinline__ float wave_incl_prod(float v) {

@@ -9,7 +9,7 @@
 // No block waits for another (the passes are separate launches), and every loop is a root chase or a union retry whose index strictly
 // descends.  Only half of each neighbourhood is visited -- the offsets whose first non-zero component is -1 -- since the pair relation
 // is symmetric.
-#include "clift_dev.h"
+#include "keyed_lattice.h"
 
 #define CC_T0 4
 #define CC_T1 8
@@ -124,9 +124,8 @@ __global__ __launch_bounds__(256) void k_cc_flatten(int* root, long total) {
 }
 
 extern "C" int clift_cc_label(const int* key, int n0, int n1, int n2, int connectivity, int* root, clift_stream_t s) {
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_cc_label: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
+    if (keyed_lattice_check("clift_cc_label", n0, n1, n2, 0, 0, 0)) return 1;                   // (no key table: any non-zero key)
     const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < CLIFT_ISO_LIMIT, "clift_cc_label: %ld lattice points (%d x %d x %d), must be < 2^31", total, n0, n1, n2);
     CLIFT_REQUIRE(connectivity == 6 || connectivity == 14 || connectivity == 26, "clift_cc_label: connectivity must be 6, 14 (Kuhn) or 26 (got %d)",
                   connectivity);
     CLIFT_REQUIRE(key && root, "clift_cc_label: NULL device buffer");

@@ -16,10 +16,10 @@
 //              best dist2 (strictly: a candidate with r^2 == dist2 ties on distance and may win on the index) or both ends have left
 //              [lo, hi].  No per-lane storage.  CLIFT_DT_NONE is tested, never added to.  A column is cut into segments of `seg` points
 //              where the lattice has too few columns to fill the device; every segment repeats the walk for lo and hi.
-//   pass x     also folds key_min: equal keys inside the wave first (the leader / readlane / ballot loop of clearance.hip with a 64-bit wave
-//              minimum), then one 64-bit unsigned atomic minimum per distinct key and wave (global_atomic_umin_x2).
+//   pass x     also folds key_min: equal keys inside the wave first (wave_fold_equal of clift_dev.h with a 64-bit wave minimum), then one
+//              64-bit unsigned atomic minimum per distinct key and wave (global_atomic_umin_x2).
 // Only vector loads, stores and atomics.  z writes `out`, y reads it into `work`, x reads `work` into `out`.
-#include "clift_dev.h"
+#include "keyed_lattice.h"
 
 #define DT_THREADS 256
 #define DT_WAVES (DT_THREADS / 64)
@@ -35,15 +35,6 @@ struct DtArgs {
     int n0, n1, n2, n_keys, axis, seg;
     long items;
 };
-
-__device__ __forceinline__ unsigned long long dt_wave_min(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 __device__ __forceinline__ long dt_word(int d, long lin) { return (((long)d * d) << 31) | lin; }
 
@@ -145,15 +136,10 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_cols(const DtArgs g) {
                 const int k = mine ? g.key[at] : 0;
                 const int u = (best != CLIFT_DT_NONE && k > 0 && k < g.n_keys) ? k : -1;
                 const unsigned long long word = (unsigned long long)(((best >> 31) << 31) | at);
-                unsigned long long todo = __ballot(u >= 0);
-                while (todo != 0ull) {                                                    // wave-uniform
-                    const int leader = __ffsll(todo) - 1;
-                    const int ku = __builtin_amdgcn_readlane(u, leader);
-                    const unsigned long long same = __ballot(u == ku);
-                    const unsigned long long m = dt_wave_min(u == ku ? word : (unsigned long long)CLIFT_DT_NONE);
+                wave_fold_equal(u, [&](int ku, unsigned long long, int leader) {
+                    const unsigned long long m = wave_min_u64(u == ku ? word : (unsigned long long)CLIFT_DT_NONE);
                     if (lane == leader) atomicMin(g.key_min + ku, m);
-                    todo &= ~same;
-                }
+                });
             }
         }
     }
@@ -161,11 +147,8 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_cols(const DtArgs g) {
 
 extern "C" int clift_lattice_distance(const int* key, int n0, int n1, int n2, int n_keys, const unsigned char* site, long* out, long* work,
                                       long* key_min, int* rejected, clift_stream_t s) {
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= CLIFT_DT_MAX_DIM && n1 <= CLIFT_DT_MAX_DIM && n2 <= CLIFT_DT_MAX_DIM,
-                  "clift_lattice_distance: lattice dimensions must be 1 .. %d (got %d x %d x %d)", CLIFT_DT_MAX_DIM, n0, n1, n2);
+    if (keyed_lattice_check("clift_lattice_distance", n0, n1, n2, CLIFT_DT_MAX_DIM, n_keys, CLIFT_REL_MAX_KEYS)) return 1;
     const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < CLIFT_ISO_LIMIT, "clift_lattice_distance: %ld lattice points (%d x %d x %d), must be < 2^31", total, n0, n1, n2);
-    CLIFT_REQUIRE(n_keys >= 1 && n_keys <= CLIFT_REL_MAX_KEYS, "clift_lattice_distance: n_keys must be 1 .. %d (got %d)", CLIFT_REL_MAX_KEYS, n_keys);
     CLIFT_REQUIRE(key && site && out && work && rejected, "clift_lattice_distance: NULL device buffer");
     const char *ob = reinterpret_cast<const char*>(out), *wb = reinterpret_cast<const char*>(work);
     CLIFT_REQUIRE(ob + total * sizeof(long) <= wb || wb + total * sizeof(long) <= ob, "clift_lattice_distance: out and work overlap");
@@ -181,8 +164,7 @@ extern "C" int clift_lattice_distance(const int* key, int n0, int n1, int n2, in
     g.key = key; g.site = site; g.key_min = reinterpret_cast<unsigned long long*>(key_min); g.rejected = rejected;
     g.n0 = n0; g.n1 = n1; g.n2 = n2; g.n_keys = n_keys;
     g.axis = 2; g.seg = 0; g.in = nullptr; g.dst = out; g.items = (long)n0 * n1;
-    long need = (g.items + DT_WAVES - 1) / DT_WAVES;
-    k_dt_rows<<<(int)(need < want ? need : want), DT_THREADS, 0, st>>>(g);
+    k_dt_rows<<<wave_item_blocks(g.items, DT_WAVES, 4), DT_THREADS, 0, st>>>(g);
     for (int a = 1; a >= 0; --a) {
         const int len = a == 0 ? n0 : n1;
         const long groups = ((a == 0 ? (long)n1 * n2 : (long)n0 * n2) + 63) / 64;
@@ -190,8 +172,7 @@ extern "C" int clift_lattice_distance(const int* key, int n0, int n1, int n2, in
         while (seg > DT_MIN_SEG && groups * ((len + seg - 1) / seg) < want * DT_WAVES) seg = (seg + 1) / 2;
         g.axis = a; g.seg = seg; g.items = groups * ((len + seg - 1) / seg);
         g.in = a == 1 ? out : work; g.dst = a == 1 ? work : out;
-        need = (g.items + DT_WAVES - 1) / DT_WAVES;
-        const int blocks = (int)(need < want ? need : want);
+        const int blocks = wave_item_blocks(g.items, DT_WAVES, 4);
         if (a == 1) k_dt_cols<false><<<blocks, DT_THREADS, 0, st>>>(g);
         else k_dt_cols<true><<<blocks, DT_THREADS, 0, st>>>(g);
     }

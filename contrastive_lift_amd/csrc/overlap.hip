@@ -11,9 +11,8 @@
 // device: the host never sees it and the call does not synchronise.
 //
 // Skewed keys: label images are piecewise constant, so most of a wave's 64 lanes hold the same (sa, sb) and one stuff segment can own half a
-// frame -- one atomic per pixel would serialise on a handful of addresses.  Equal keys are folded inside the wave first: the lowest lane that
-// still holds an uncounted key is the leader, its key is broadcast (v_readlane), a ballot finds the lanes that share it, and the leader alone
-// adds their popcount.  A wave of one key costs one atomic; 64 distinct keys cost 64 trips, the same atomics as before.
+// frame -- one atomic per pixel would serialise on a handful of addresses.  Equal keys are folded inside the wave first (wave_fold_equal of
+// clift_dev.h) and the leader alone adds their popcount: a wave of one key costs one atomic, 64 distinct keys the same atomics as before.
 //
 // LDS tables: when NA * NB <= OV_LDS_INTS = 8192 ints (32 KiB: five 256-thread blocks per CU out of the CU's 160 KiB, the same budget as the
 // candidate tile of points3d.hip, and above the 4 blocks per CU the fixed grid asks for) the block counts into a private table in LDS and adds
@@ -108,17 +107,9 @@ __global__ __launch_bounds__(OV_THREADS) void k_label_overlap(const OvArgs g) {
                     }
                 }
             }
-            unsigned long long todo = __ballot(key >= 0);                            // wave-uniform: every lane of the wave walks the loop
-            while (todo != 0ull) {
-                const int leader = __ffsll(todo) - 1;
-                const int k = __builtin_amdgcn_readlane(key, leader);
-                const unsigned long long same = __ballot(key == k);
-                if (lane == leader) {
-                    if (LDS) atomicAdd(&tab[k], __popcll(same));
-                    else atomicAdd(&dst[k], __popcll(same));
-                }
-                todo &= ~same;
-            }
+            wave_fold_equal(key, [&](int k, unsigned long long same, int leader) {
+                if (lane == leader) atomicAdd(LDS ? &tab[k] : &dst[k], __popcll(same));
+            });
         }
         rej = wave_sum_i(rej);
         if (lane == 0 && rej != 0) atomicAdd(&g.rejected[f], rej);

@@ -18,7 +18,7 @@
 //              with each mask word and counts the bits.  Mask words without a bit and windows without a solid point are skipped, both
 //              uniform branches.  Lanes with t2 >= T2 idle (accepted: DESIGN.md).  The counts and the two minima are carried over the items
 //              of a wave and folded inside it, then one vector atomic each per wave (atomicAdd on int, atomicMin on unsigned long long).
-#include "clift_dev.h"
+#include "keyed_lattice.h"
 
 #define PM_THREADS 256
 #define PM_WAVES (PM_THREADS / 64)
@@ -33,15 +33,6 @@ struct PmArgs {
     int T0, T1, T2, Q, wp, mw;                                                             // Q = ceil(T2 / 64) chunks of t2
     long items;
 };
-
-__device__ __forceinline__ pm_word pm_wave_min(pm_word v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const pm_word o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 // a word that every lane holds alike, as a scalar: the branches on it are uniform
 __device__ __forceinline__ pm_word pm_uniform(pm_word v) {
@@ -141,8 +132,8 @@ __global__ __launch_bounds__(PM_THREADS) void k_pm_correlate(const PmArgs g) {
         if (fr && word < best_free) best_free = word;
         if (sp && word < best_sup) best_sup = word;
     }
-    best_free = pm_wave_min(best_free);
-    best_sup = pm_wave_min(best_sup);
+    best_free = wave_min_u64(best_free);
+    best_sup = wave_min_u64(best_sup);
     if (lane == 0) {
         if (n_free != 0) {
             atomicAdd(g.count, n_free);
@@ -158,13 +149,9 @@ __global__ __launch_bounds__(PM_THREADS) void k_pm_correlate(const PmArgs g) {
 extern "C" int clift_lattice_placement(const int* key, int n0, int n1, int n2, int n_keys, const unsigned char* solid, const unsigned char* shape,
                                        int m0, int m1, int m2, int direction, int min_support, int t0, int t1, int t2, int* overlap, int* support,
                                        int* count, long* best, int* rejected, long* work, clift_stream_t s) {
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= CLIFT_DT_MAX_DIM && n1 <= CLIFT_DT_MAX_DIM && n2 <= CLIFT_DT_MAX_DIM,
-                  "clift_lattice_placement: lattice dimensions must be 1 .. %d (got %d x %d x %d)", CLIFT_DT_MAX_DIM, n0, n1, n2);
+    if (keyed_lattice_check("clift_lattice_placement", n0, n1, n2, CLIFT_DT_MAX_DIM, n_keys, CLIFT_REL_MAX_KEYS)) return 1;
     CLIFT_REQUIRE(m0 >= 1 && m1 >= 1 && m2 >= 1 && m0 <= n0 && m1 <= n1 && m2 <= n2,
                   "clift_lattice_placement: shape dimensions must be 1 .. the lattice's (got %d x %d x %d in %d x %d x %d)", m0, m1, m2, n0, n1, n2);
-    const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < CLIFT_ISO_LIMIT, "clift_lattice_placement: %ld lattice points (%d x %d x %d), must be < 2^31", total, n0, n1, n2);
-    CLIFT_REQUIRE(n_keys >= 1 && n_keys <= CLIFT_REL_MAX_KEYS, "clift_lattice_placement: n_keys must be 1 .. %d (got %d)", CLIFT_REL_MAX_KEYS, n_keys);
     CLIFT_REQUIRE(direction >= 0 && direction <= 5, "clift_lattice_placement: direction must be 0 .. 5 (got %d)", direction);
     CLIFT_REQUIRE(min_support >= 1, "clift_lattice_placement: min_support must be >= 1 (got %d)", min_support);
     PmArgs g;
@@ -180,12 +167,10 @@ extern "C" int clift_lattice_placement(const int* key, int n0, int n1, int n2, i
     const long lat_words = ((long)n0 + 2) * (n1 + 2) * g.wp, mask_words = ((long)m0 + 2) * (m1 + 2) * g.mw;
     g.lat = reinterpret_cast<pm_word*>(work); g.cells = g.lat + lat_words; g.shadow = g.cells + mask_words;
     const hipStream_t st = as_stream(s);
-    const long want = (long)clift_persistent_cus() * 8;                                    // blocks of the fixed grid
     const long sizes[3] = {mask_words, lat_words, (long)g.T0 * g.T1 * g.Q};
     for (int pass = 0; pass < 3; ++pass) {
         g.items = sizes[pass];
-        const long need = (g.items + PM_WAVES - 1) / PM_WAVES;
-        const int blocks = (int)(need < want ? need : want);
+        const int blocks = wave_item_blocks(g.items, PM_WAVES, 8);
         if (pass == 0) k_pm_shape<<<blocks, PM_THREADS, 0, st>>>(g);
         else if (pass == 1) k_pm_pack<<<blocks, PM_THREADS, 0, st>>>(g);
         else k_pm_correlate<<<blocks, PM_THREADS, 0, st>>>(g);

@@ -10,7 +10,8 @@
 // axes 1 and 2 are bit fields of the lane number.
 //
 // Skewed keys: label lattices are piecewise constant and one floor can own most points and most faces.
-//   moments  equal keys are folded inside the wave (the leader / readlane / ballot loop of overlap.hip).  Because the lanes' offsets are bit
+//   moments  equal keys are folded inside the wave (the loop of wave_fold_equal, clift_dev.h, written out in this file: through the helper
+//            the kernel came out a VGPR smaller and 0.6 % slower in one of its timings).  Because the lanes' offsets are bit
 //            fields of the lane number, the count, the three index sums and the index box of the lanes of one key all follow from the ballot
 //            mask alone -- popcounts against five lane patterns, a count of leading and of trailing zeros -- without a shuffle.  The folded
 //            record stays in the wave's registers while the next fold has the same key and goes to memory (ten atomics of one lane,
@@ -19,7 +20,7 @@
 //            adds the popcount.  A wave with no boundary in it pays six ballots.  With n_keys <= CLIFT_REL_LDS_KEYS the block counts into a
 //            private table in LDS and adds its non-zero entries to memory once, when it ends; above it the folded adds go straight to memory.
 // Only integer vector atomics (ds_add_u32, global_atomic_add / _add_x2 / _smin / _smax).
-#include "clift_dev.h"
+#include "keyed_lattice.h"
 
 #define REL_THREADS 256
 #define REL_T0 8
@@ -200,10 +201,7 @@ __global__ __launch_bounds__(REL_THREADS) void k_lattice_relations(const RelArgs
 
 extern "C" int clift_lattice_relations(const int* key, int n0, int n1, int n2, int n_keys, int gap, long* count, long* isum, int* ibox, int* faces,
                                        int* near, int* rejected, clift_stream_t s) {
-    CLIFT_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1, "clift_lattice_relations: lattice dimensions must be positive (got %d x %d x %d)", n0, n1, n2);
-    const long total = (long)n0 * n1 * n2;
-    CLIFT_REQUIRE(total < CLIFT_ISO_LIMIT, "clift_lattice_relations: %ld lattice points (%d x %d x %d), must be < 2^31", total, n0, n1, n2);
-    CLIFT_REQUIRE(n_keys >= 1 && n_keys <= CLIFT_REL_MAX_KEYS, "clift_lattice_relations: n_keys must be 1 .. %d (got %d)", CLIFT_REL_MAX_KEYS, n_keys);
+    if (keyed_lattice_check("clift_lattice_relations", n0, n1, n2, 0, n_keys, CLIFT_REL_MAX_KEYS)) return 1;
     CLIFT_REQUIRE(gap >= 0 && gap <= CLIFT_REL_MAX_GAP, "clift_lattice_relations: gap must be 0 .. %d (got %d)", CLIFT_REL_MAX_GAP, gap);
     CLIFT_REQUIRE((gap == 0) == (near == nullptr), "clift_lattice_relations: near must be NULL exactly when gap == 0 (gap %d, near %s)", gap,
                   near ? "given" : "NULL");
@@ -226,8 +224,7 @@ extern "C" int clift_lattice_relations(const int* key, int n0, int n1, int n2, i
     g.n0 = n0; g.n1 = n1; g.n2 = n2; g.n_keys = n_keys; g.gap = gap;
     g.g1 = cdiv(n1, REL_T1); g.g2 = cdiv(n2, REL_T2);
     g.tiles = (long)cdiv(n0, REL_T0) * g.g1 * g.g2;                                   // <= total
-    const long want = (long)clift_persistent_cus() * 4;
-    const int blocks = (int)(g.tiles < want ? g.tiles : want);
+    const int blocks = wave_item_blocks(g.tiles, 1, 4);                               // a block takes a run of tiles
     if (n_keys <= CLIFT_REL_LDS_KEYS) k_lattice_relations<true><<<blocks, REL_THREADS, 0, st>>>(g);
     else                              k_lattice_relations<false><<<blocks, REL_THREADS, 0, st>>>(g);
     return clift_check_launch("clift_lattice_relations");

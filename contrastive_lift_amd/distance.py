@@ -17,47 +17,19 @@ afterwards from the lattice ticks of the two points that were chosen.
 
 ``backend="device"`` is one call (three passes: z, y, x); ``backend="host"`` gives the same integers in numpy -- the same three passes, one
 offset of the axis at a time over the whole lattice (three lattices of int64 in memory), ending an axis once the offset squared exceeds every
-distance found -- for machines and tests without a GPU.
+distance found -- for machines and tests without a GPU.  What the lattice modules share is in ``lattice``.
 """
-import json
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
-from .clearance import _host_ticks, default_level, settle_key
-from .components import CC_LIMIT, _as_key, _check_backend
-from .relations import MAX_KEYS
+from . import _lib, lattice
+from .lattice import INDEX_MASK, MAX_DIM, NONE_WORD   # (CLIFT_DT_MAX_DIM, CLIFT_DT_NONE: read as distance.MAX_DIM, distance.NONE_WORD too)
+from .lattice import key_table as site_table, placement_key, scene_before   # noqa: F401  (still read as distance.site_table, ...)
 
-MAX_DIM = 16384                  # CLIFT_DT_MAX_DIM
 NONE = 0x7fffffff                # the dist2 of ``split`` where there is no site; gap2 where there is no pair
-NONE_WORD = 0x7fffffffffffffff   # CLIFT_DT_NONE
-INDEX_MASK = 0x7fffffff          # the nearest field of a packed word
 MAX_SEPARATION_KEYS = 256        # ``separation`` runs one transform per key
-
-
-def site_table(sites, n_keys):
-    """``sites`` -> (n_keys,) numpy bool.  None: every key >= 1; an int: that key; an iterable of keys; a bool array of length n_keys."""
-    n_keys = int(n_keys)
-    table = np.zeros(n_keys, bool)
-    if sites is None:
-        table[1:] = True
-        return table
-    if torch.is_tensor(sites):
-        sites = sites.cpu().numpy()
-    if isinstance(sites, np.ndarray) and sites.dtype == np.bool_:
-        if sites.shape != (n_keys,):
-            raise ValueError(f"a bool site table holds n_keys = {n_keys} entries, got shape {tuple(sites.shape)}")
-        return sites.copy()
-    keys = [sites] if isinstance(sites, (int, np.integer)) else list(sites)
-    for k in keys:
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
-            raise ValueError(f"sites is None, a key, an iterable of keys or a bool array of length n_keys (got an entry {k!r})")
-        if not 0 <= int(k) < n_keys:
-            raise ValueError(f"site key {int(k)} lies outside [0, {n_keys})")
-        table[int(k)] = True
-    return table
 
 
 def _axis_pass_host(cur, axis):
@@ -92,31 +64,12 @@ def _tables_host(key, n_keys, table, want_min):
     return {name: torch.from_numpy(v).to(key.device) for name, v in out.items()}
 
 
-def _prepare(key, n_keys, what):
-    key = _as_key(key)
-    n0, n1, n2 = (int(x) for x in key.shape)
-    if n0 * n1 * n2 >= CC_LIMIT:
-        raise _lib.CliftError(f"{what}: {n0 * n1 * n2} lattice points, must be < 2^31")
-    if key.numel() == 0:
-        raise ValueError(f"key must have at least one point along every axis, got {tuple(key.shape)}")
-    if max(n0, n1, n2) > MAX_DIM:
-        raise ValueError(f"every lattice dimension must be 1 .. {MAX_DIM} (got {n0} x {n1} x {n2})")
-    if n_keys is None:
-        n_keys = max(int(key.max()), 0) + 1
-    n_keys = int(n_keys)
-    if not 1 <= n_keys <= MAX_KEYS:
-        raise ValueError(f"n_keys must be 1 .. {MAX_KEYS} (got {n_keys})")
-    return key, n_keys
-
-
 def _run(key, n_keys, table, want_min, backend, work=None):
     """One transform of a prepared key.  ``work``: a scratch tensor (N,) int64 on the device to use again, or None."""
     if backend == "host":
         return _tables_host(key, n_keys, table, want_min)
-    if not key.is_cuda:
-        raise _lib.CliftError(f"lattice_distance: backend='device' wants the key on the GPU, got {key.device}")
-    dev = key.device
-    n0, n1, n2 = (int(x) for x in key.shape)
+    lattice.require_device(key, "lattice_distance")
+    dev, (n0, n1, n2) = key.device, key.shape
     site = torch.from_numpy(table.astype(np.uint8)).to(dev)
     out = dict(packed=torch.empty((n0, n1, n2), dtype=torch.int64, device=dev), rejected=torch.empty(1, dtype=torch.int32, device=dev))
     if work is None:
@@ -132,27 +85,21 @@ def _run(key, n_keys, table, want_min, backend, work=None):
 def distance_tables(key, n_keys=None, sites=None, key_min=False, backend="device"):
     """The transform of a key lattice (n0, n1, n2) bool or integer as a dict of tensors on key's device -- ``packed`` (n0, n1, n2) int64,
     ``rejected`` (1,) int32 and, with ``key_min=True``, ``key_min`` (n_keys,) int64 -- whatever ``rejected`` says (``lattice_distance`` raises
-    on it).  ``sites``: see ``site_table``.  ``n_keys=None``: max(key) + 1, one read of the lattice's maximum."""
+    on it).  ``sites``: see ``lattice.key_table``.  ``n_keys=None``: max(key) + 1, one read of the lattice's maximum."""
     return _tables(key, n_keys, sites, key_min, backend)[0]
 
 
 def _tables(key, n_keys, sites, key_min, backend):
-    _check_backend(backend)
-    key, n_keys = _prepare(key, n_keys, "lattice_distance")
-    return _run(key, n_keys, site_table(sites, n_keys), bool(key_min), backend), n_keys
-
-
-def _raise_on_rejected(out, n_keys, what):
-    rejected = int(out["rejected"][0])
-    if rejected > 0:
-        raise _lib.CliftError(f"{what}: {rejected} lattice points carry a key outside [0, {n_keys})")
+    key, n_keys = lattice.prepare(key, n_keys, "lattice_distance", MAX_DIM)
+    lattice.check_backend(backend)
+    return _run(key, n_keys, lattice.key_table(sites, n_keys), bool(key_min), backend), n_keys
 
 
 @torch.no_grad()
 def lattice_distance(key, n_keys=None, sites=None, key_min=False, backend="device"):
     """``distance_tables``; raises CliftError when a point's key lies outside [0, n_keys)."""
     out, n_keys = _tables(key, n_keys, sites, key_min, backend)
-    _raise_on_rejected(out, n_keys, "lattice_distance")
+    lattice.raise_on_rejected(out, n_keys, "lattice_distance")
     return out
 
 
@@ -170,7 +117,7 @@ def split(packed):
 def voronoi_keys(key, packed, max_dist2=None):
     """Per point the key of its nearest site (int32, key's shape, on packed's device): the Voronoi labelling of the lattice by the sites of
     ``packed``.  0 where there is no site, or where dist2 > ``max_dist2``."""
-    key = _as_key(key)
+    key = lattice.as_key(key)
     packed = packed if torch.is_tensor(packed) else torch.from_numpy(np.ascontiguousarray(packed))
     if tuple(packed.shape) != tuple(key.shape):
         raise ValueError(f"packed {tuple(packed.shape)} and key {tuple(key.shape)} are not one lattice")
@@ -189,8 +136,8 @@ def separation(key, n_keys=None, backend="device"):
     ``at[u][v]`` the lin of the point of u that realises it (the smallest lin among those), ``to[u][v]`` that point's nearest point of v
     (-1 each where gap2 is NONE), and ``rejected``.  One transform per key v >= 1 that occurs, with sites = v and key_min: at most
     ``MAX_SEPARATION_KEYS`` keys.  Raises CliftError on a key outside [0, n_keys)."""
-    _check_backend(backend)
-    key, n_keys = _prepare(key, n_keys, "separation")
+    key, n_keys = lattice.prepare(key, n_keys, "separation", MAX_DIM)
+    lattice.check_backend(backend)
     if n_keys > MAX_SEPARATION_KEYS:
         raise ValueError(f"separation runs one transform per key and takes at most {MAX_SEPARATION_KEYS} keys (got n_keys = {n_keys}): drop the "
                          "small components first (--min_component)")
@@ -202,8 +149,8 @@ def separation(key, n_keys=None, backend="device"):
     work = torch.empty(key.numel(), dtype=torch.int64, device=dev) if backend == "device" and key.is_cuda else None
     rejected = None
     for v in present:
-        out = _run(key, n_keys, site_table(int(v), n_keys), True, backend, work)
-        _raise_on_rejected(out, n_keys, "separation")
+        out = _run(key, n_keys, lattice.key_table(int(v), n_keys), True, backend, work)
+        lattice.raise_on_rejected(out, n_keys, "separation")
         rejected = out["rejected"]
         km = out["key_min"].clone()
         km[v] = NONE_WORD                                                  # the diagonal
@@ -214,7 +161,7 @@ def separation(key, n_keys=None, backend="device"):
         to[:, v] = torch.where(found, out["packed"].reshape(-1)[point] & INDEX_MASK, -1)
     if rejected is None:
         rejected = torch.tensor([int(((key < 0) | (key >= n_keys)).sum())], dtype=torch.int32, device=dev)
-        _raise_on_rejected(dict(rejected=rejected), n_keys, "separation")
+        lattice.raise_on_rejected(dict(rejected=rejected), n_keys, "separation")
     return dict(gap2=gap2.to(torch.int32), at=at.to(torch.int32), to=to.to(torch.int32), rejected=rejected)
 
 
@@ -224,7 +171,7 @@ def _world(lin, ticks):
     return [float(ticks[a][idx[a]]) for a in range(3)]
 
 
-class Separation:
+class Separation(lattice.Summary):
     """The summary of ``Separation.from_tables``: ``nodes``, one dict per key 1..K with its nearest other node, and ``pairs``, one dict per
     unordered pair of nodes within ``max_cells``."""
 
@@ -240,14 +187,12 @@ class Separation:
         None for a node alone.  Per unordered pair u < v with sqrt(gap2) <= ``max_cells`` (None: every pair that exists): ``gap2``,
         ``cells``, ``distance`` = the world distance between the two points, in fp64 from the ticks of at[u][v] and to[u][v], and those
         points as ``point_a`` (of u) and ``point_b`` (of v)."""
-        host = {k: (tables[k].cpu().numpy() if torch.is_tensor(tables[k]) else np.asarray(tables[k])).astype(np.int64) for k in ("gap2", "at", "to")}
+        host = lattice.to_host(tables, ("gap2", "at", "to"), np.int64)
         gap2, at, to = host["gap2"], host["at"], host["to"]
-        K = len(nodes)
-        if gap2.shape[0] != K + 1:
-            raise ValueError(f"the tables hold {gap2.shape[0]} keys, the node list wants {K + 1}")
+        K = lattice.node_count(gap2, nodes)
         if max_cells is not None and not float(max_cells) >= 0.0:
             raise ValueError(f"max_cells must be >= 0 (got {max_cells})")
-        ticks, _ = _host_ticks(ticks)
+        ticks, _ = lattice.host_ticks(ticks)
 
         def world_distance(u, v):
             a, b = _world(at[u, v], ticks), _world(to[u, v], ticks)
@@ -272,35 +217,14 @@ class Separation:
     def to_dict(self):
         return dict(max_cells=self.max_cells, nodes=self.nodes, pairs=self.pairs)
 
-    def to_json(self, **kw):
-        return json.dumps(self.to_dict(), **kw)
-
-    def __eq__(self, other):
-        return isinstance(other, Separation) and self.to_dict() == other.to_dict()
-
-
-def scene_before(edit):
-    """What stands where the LAST edit of ``edit`` places its object, as an edit program (None: the unedited scene): for a move the program
-    with its last edit replaced by a delete of the same source box and shape, for a copy the program without its last edit."""
-    from . import edit as ed
-    program = ed.as_program(edit)
-    last = program[len(program) - 1]
-    if last.mode not in (ed.DUPLICATE, ed.MANIPULATE):
-        raise ValueError(f"placement: the last edit must be a copy or a move (it is a {last.name})")
-    head = list(program)[:-1]
-    if last.mode == ed.MANIPULATE:
-        head.append(ed.Edit(ed.DELETE, last.src, shape=last.shape))
-    return ed.EditProgram(head) if head else None
-
 
 def placement_from_keys(key, ticks, backend="device"):
     """``placement`` from its key lattice (0 .. 3: 1 = the rest of the scene, 2 = the moved content, 3 = both) and the lattice ticks."""
-    key = _as_key(key)
+    key = lattice.as_key(key)
     n_moved, overlap = int((key >= 2).sum()), int((key == 3).sum())
     if n_moved == 0:
-        raise _lib.CliftError("placement: no lattice point at or above the level holds content that the last edit placed (the moved set is "
-                              "empty): is the destination outside the scene box, the level too high, or the lattice too coarse?")
-    ticks, step = _host_ticks(ticks)
+        lattice.refuse_empty_moved("placement")
+    ticks, step = lattice.host_ticks(ticks)
     rest = lattice_distance(key, 4, sites=[1, 3], key_min=True, backend=backend)
     word = int(torch.minimum(rest["key_min"][2], rest["key_min"][3]))
     gap2 = moved_point = rest_point = None
@@ -317,26 +241,13 @@ def placement_from_keys(key, ticks, backend="device"):
 
 
 @torch.no_grad()
-def placement_key(model, renderer, edit, upsample=1, level=None):
-    """The key lattice of ``placement`` -> (key (n0, n1, n2) int32 = R + 2 M, ticks): M the content that the LAST edit of ``edit`` placed, on
-    the lattice of the edited scene (key 2 of ``clearance.settle_key``), R the density >= level of the scene before the paste
-    (``scene_before``) on the same lattice."""
-    before = scene_before(edit)
-    level = default_level(renderer, 0.5) if level is None else float(level)
-    moved_key, ticks, _ = settle_key(model, renderer, edit, upsample, level)
-    sigma = renderer.get_dense_sigma(model, int(upsample), edit=before) if before is not None else renderer.get_dense_sigma(model, int(upsample))
-    rest = sigma >= torch.tensor(level, dtype=torch.float32, device=sigma.device)
-    return (rest.int() + 2 * (moved_key == 2).int()).int(), ticks
-
-
-@torch.no_grad()
 def placement(model, renderer, edit, upsample=1, level=None):
     """Does the object that the LAST edit of ``edit`` (an ``Edit`` or an ``EditProgram``; a copy or a move, else ValueError) places collide
-    with what was there?  Two transforms of ``placement_key``.  Sites {1, 3} with key_min: ``gap2`` = the smallest squared index distance
+    with what was there?  Two transforms of ``lattice.placement_key``.  Sites {1, 3} with key_min: ``gap2`` = the smallest squared index distance
     from a point of the moved content to the rest of the scene (0 when they overlap; None when the scene holds nothing else) with the two
     world points ``moved_point`` and ``rest_point``.  Sites {0, 2}: ``depth2`` = the largest dist2 over the overlapping points, how deep
     the deepest of them lies in what was there (0 without overlap).  -> dict(n_moved, overlap = the points of key 3, depth2, gap2,
     moved_point, rest_point, spacing (3,), verdict): "collides" when overlap > 0, "touches" when gap2 <= 3 (a neighbour within the
     3 x 3 x 3 cube around a point), else "clear".  No density of the moved object on the lattice is a CliftError."""
-    key, ticks = placement_key(model, renderer, edit, upsample, level)
+    key, ticks = lattice.placement_key(model, renderer, edit, upsample, level)
     return placement_from_keys(key, ticks)

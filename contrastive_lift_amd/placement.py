@@ -18,17 +18,13 @@ cell of the shape (a neighbour outside the shape's box is not) and has t + c + e
 
 ``backend="device"`` is one call (three launches: the two masks of the shape, the bit-packed lattice, the correlation); ``backend="host"``
 gives the same integers in numpy -- one shifted slice of the zero-padded solid lattice per mask cell, added into int32 -- for machines and
-tests without a GPU.
+tests without a GPU.  What the lattice modules share is in ``lattice``.
 """
-import json
-
 import numpy as np
 import torch
 
-from . import _lib
-from .clearance import _host_ticks, direction_index, index_box
-from .components import _as_key, _check_backend
-from .distance import INDEX_MASK, NONE_WORD, _prepare, _raise_on_rejected, placement_key, site_table
+from . import _lib, lattice
+from .lattice import INDEX_MASK, NONE_WORD
 
 def work_words(n, m):
     """CLIFT_PM_WORK_WORDS: the int64 words of scratch for a lattice ``n`` and a shape ``m``."""
@@ -87,15 +83,15 @@ def _tables_host(key, n_keys, table, shape, d, min_support, target):
 
 
 def _tables(key, shape, n_keys, solid, direction, target, min_support, backend):
-    _check_backend(backend)
-    key, n_keys = _prepare(key, n_keys, "lattice_placement")
-    n = tuple(int(x) for x in key.shape)
+    key, n_keys = lattice.prepare(key, n_keys, "lattice_placement", lattice.MAX_DIM)
+    lattice.check_backend(backend)
+    n = tuple(key.shape)
     shape, m = _as_shape(shape, n)
-    d = direction_index(direction)
+    d = lattice.direction_index(direction)
     min_support = int(min_support)
     if min_support < 1:
         raise ValueError(f"min_support must be >= 1 (got {min_support})")
-    table = site_table(solid, n_keys)
+    table = lattice.key_table(solid, n_keys)
     T = tuple(n[a] - m[a] + 1 for a in range(3))
     target = (0, 0, 0) if target is None else tuple(int(x) for x in target)
     if len(target) != 3:
@@ -103,8 +99,7 @@ def _tables(key, shape, n_keys, solid, direction, target, min_support, backend):
     target = tuple(min(max(target[a], 0), T[a] - 1) for a in range(3))
     if backend == "host":
         return _tables_host(key, n_keys, table, shape, d, min_support, target), n_keys
-    if not key.is_cuda:
-        raise _lib.CliftError(f"lattice_placement: backend='device' wants the key on the GPU, got {key.device}")
+    lattice.require_device(key, "lattice_placement")
     dev = key.device
     shape = shape.to(dev)
     site = torch.from_numpy(table.astype(np.uint8)).to(dev)
@@ -123,7 +118,7 @@ def placement_tables(key, shape, n_keys=None, solid=None, direction="-z", target
     """The placement map of ``shape`` (m0, m1, m2) bool or integer, a non-zero entry is a cell, over a key lattice (n0, n1, n2) bool or
     integer, as a dict of tensors on key's device -- ``overlap`` and ``support`` (T) int32, ``count`` (2) int32, ``best`` (2) int64,
     ``rejected`` (1) int32 -- whatever ``rejected`` says (``lattice_placement`` raises on it).  ``solid``: the forms of
-    ``distance.site_table``, None = every key >= 1.  ``direction``: "+x" .. "-z".  ``target``: three indices, None = (0, 0, 0); one outside
+    ``lattice.key_table``, None = every key >= 1.  ``direction``: "+x" .. "-z".  ``target``: three indices, None = (0, 0, 0); one outside
     T is clamped.  ``n_keys=None``: max(key) + 1.  A shape without a cell is a ValueError."""
     return _tables(key, shape, n_keys, solid, direction, target, min_support, backend)[0]
 
@@ -132,7 +127,7 @@ def placement_tables(key, shape, n_keys=None, solid=None, direction="-z", target
 def lattice_placement(key, shape, n_keys=None, solid=None, direction="-z", target=None, min_support=1, backend="device"):
     """``placement_tables``; raises CliftError when a point's key lies outside [0, n_keys)."""
     out, n_keys = _tables(key, shape, n_keys, solid, direction, target, min_support, backend)
-    _raise_on_rejected(out, n_keys, "lattice_placement")
+    lattice.raise_on_rejected(out, n_keys, "lattice_placement")
     return out
 
 
@@ -146,13 +141,13 @@ def split_best(word, T):
 
 
 def object_of(key, u):
-    """-> (shape, origin): the points of key ``u`` cropped to their index box (``clearance.index_box``) as a uint8 tensor on key's device,
+    """-> (shape, origin): the points of key ``u`` cropped to their index box (``lattice.index_box``) as a uint8 tensor on key's device,
     and the box's low corner (three ints).  A key that no point carries is a ValueError."""
-    key = _as_key(key)
+    key = lattice.as_key(key)
     u = int(u)
     if u < 0:
         raise ValueError(f"the key of an object is >= 0 (got {u})")
-    box = index_box(key, u + 1)[u]
+    box = lattice.index_box(key, u + 1)[u]
     if box[3] < 0:
         raise ValueError(f"no lattice point carries key {u}")
     lo, hi = [int(x) for x in box[:3]], [int(x) + 1 for x in box[3:]]
@@ -163,7 +158,7 @@ def object_of(key, u):
 def node_placement(key, n_keys, u, direction="-z", min_support=1, backend="device"):
     """Where else could node ``u`` stand?  ``lattice_placement`` of shape = ``object_of(key, u)`` over the lattice with every key >= 1
     except u solid, the target u's own origin -> (tables, origin)."""
-    key, n_keys = _prepare(key, n_keys, "node_placement")
+    key, n_keys = lattice.prepare(key, n_keys, "node_placement", lattice.MAX_DIM)
     u = int(u)
     if not 1 <= u < n_keys:
         raise ValueError(f"node key {u} lies outside [1, {n_keys})")
@@ -174,7 +169,7 @@ def node_placement(key, n_keys, u, direction="-z", min_support=1, backend="devic
     return lattice_placement(key, shape, n_keys, solid, direction, origin, min_support, backend), origin
 
 
-class PlacementMap:
+class PlacementMap(lattice.Summary):
     """The summary of ``PlacementMap.from_tables``: ``n_translations``, ``n_free``, ``n_supported`` and, for ``best_free`` and
     ``best_supported``, a dict (None where there is none) of the translation, the step vector from the origin, the world offset, overlap
     and support there, and dist2."""
@@ -188,10 +183,10 @@ class PlacementMap:
         """``tables``: the tables of ``lattice_placement``; ``origin``: where the object stands now, three indices (``object_of``);
         ``ticks``: the three uniform coordinate arrays of the lattice (``renderer.lattice_ticks``).  fp64 on the host: ``offset`` = the
         steps times the tick spacing of each axis, signed."""
-        host = {k: (tables[k].cpu().numpy() if torch.is_tensor(tables[k]) else np.asarray(tables[k])) for k in ("overlap", "support", "count", "best")}
+        host = lattice.to_host(tables, ("overlap", "support", "count", "best"))
         T = host["overlap"].shape
         origin = [int(x) for x in origin]
-        _, step = _host_ticks(ticks)
+        _, step = lattice.host_ticks(ticks)
 
         def entry(word):
             found = split_best(word, T)
@@ -207,25 +202,18 @@ class PlacementMap:
         return dict(origin=self.origin, n_translations=self.n_translations, n_free=self.n_free, n_supported=self.n_supported,
                     best_free=self.best_free, best_supported=self.best_supported)
 
-    def to_json(self, **kw):
-        return json.dumps(self.to_dict(), **kw)
-
-    def __eq__(self, other):
-        return isinstance(other, PlacementMap) and self.to_dict() == other.to_dict()
-
 
 def snap_from_keys(key, ticks, direction="-z", min_support=1, backend="device"):
     """``snap_offset`` from its key lattice (0 .. 3: 1 = the rest of the scene, 2 = the moved content, 3 = both) and the lattice ticks."""
-    key = _as_key(key)
-    direction_index(direction)
+    key = lattice.as_key(key)
+    lattice.direction_index(direction)
     n_moved = int((key >= 2).sum())
     if n_moved == 0:
-        raise _lib.CliftError("snap_offset: no lattice point at or above the level holds content that the last edit placed (the moved set is "
-                              "empty): is the destination outside the scene box, the level too high, or the lattice too coarse?")
+        lattice.refuse_empty_moved("snap_offset")
     shape, origin = object_of(key >= 2, 1)
     tables = lattice_placement(key, shape, 4, [1, 3], direction, origin, min_support, backend)
     T = tuple(tables["overlap"].shape)
-    _, step = _host_ticks(ticks)
+    _, step = lattice.host_ticks(ticks)
     found = split_best(tables["best"][1], T)
     dist2, t = found if found is not None else (None, origin)
     steps = np.asarray([t[a] - origin[a] for a in range(3)], np.int64)
@@ -239,10 +227,10 @@ def snap_from_keys(key, ticks, direction="-z", min_support=1, backend="device"):
 def snap_offset(model, renderer, edit, direction="-z", upsample=1, level=None, min_support=1):
     """The nearest place where the object that the LAST edit of ``edit`` (an ``Edit`` or an ``EditProgram``; a copy or a move, else
     ValueError) places fits and stands: the companion of ``clearance.settle_offset`` (one axis) and ``distance.placement`` (one position).
-    The lattice is ``distance.placement_key`` (R + 2 M); the shape and its origin are the moved content cropped to its index box, solid is
+    The lattice is ``lattice.placement_key`` (R + 2 M); the shape and its origin are the moved content cropped to its index box, solid is
     what stood there before the paste (keys 1 and 3), the target is the origin.  -> dict(found, steps (3,) int, offset (3,) fp64 world
     translation, overlap_before = overlap[origin], support_before, support and dist2 at the chosen translation, n_free, n_supported,
     n_moved, direction, spacing (3,)); ``found`` is False, the steps and the offset zero and support and dist2 None when no free
     translation has ``min_support`` faces along ``direction``.  No density of the moved object on the lattice is a CliftError."""
-    key, ticks = placement_key(model, renderer, edit, upsample, level)
+    key, ticks = lattice.placement_key(model, renderer, edit, upsample, level)
     return snap_from_keys(key, ticks, direction, min_support)

@@ -13,47 +13,31 @@ at most ``gap`` background points deep, ends at another key v: objects in a dens
 level set, so plain adjacency misses "cup on table".  A point with a key outside [0, n_keys) is counted in ``rejected`` and nowhere else.
 
 ``backend="device"`` is one kernel launch; ``backend="host"`` gives the same integers in vectorised numpy (shifted slices and np.add.at) for
-machines and tests without a GPU.
+machines and tests without a GPU.  What the lattice modules share is in ``lattice``.
 """
-import json
-
 import numpy as np
 import torch
 
-from . import _lib
-from .components import CC_LIMIT, _as_key, _check_backend
+from . import _lib, lattice
+from .lattice import MAX_KEYS   # noqa: F401  (CLIFT_REL_MAX_KEYS; callers read it as relations.MAX_KEYS)
 
 LDS_KEYS = 32                    # CLIFT_REL_LDS_KEYS: up to here the kernel counts pairs in a block-private LDS table
-MAX_KEYS = 1024                  # CLIFT_REL_MAX_KEYS
 MAX_GAP = 4                      # CLIFT_REL_MAX_GAP
 TILE = (8, 8, 32)                # the kernel's tile extents (csrc/relations.hip: REL_T0, REL_T1, REL_T2)
-UP_AXES = ("+x", "-x", "+y", "-y", "+z", "-z")
+UP_AXES = lattice.DIRECTIONS     # "+x", "-x", "+y", "-y", "+z", "-z"
 TABLES = ("count", "isum", "ibox", "faces", "near", "rejected")
-
-
-def _check_sizes(n_keys, gap):
-    n_keys, gap = int(n_keys), int(gap)
-    if not 1 <= n_keys <= MAX_KEYS:
-        raise ValueError(f"n_keys must be 1 .. {MAX_KEYS} (got {n_keys})")
-    if not 0 <= gap <= MAX_GAP:
-        raise ValueError(f"gap must be 0 .. {MAX_GAP} (got {gap})")
-    return n_keys, gap
 
 
 def _tables_host(key, n_keys, gap):
     k = key.cpu().numpy().astype(np.int64)
-    shape = k.shape
     valid = (k >= 0) & (k < n_keys)
     kv = np.where(valid, k, -1)                                            # -1: rejected, and later: beyond the lattice
     count = np.bincount(kv[valid], minlength=n_keys).astype(np.int64)
     isum = np.zeros((n_keys, 3), np.int64)
-    ibox = np.empty((n_keys, 6), np.int32)
-    ibox[:, :3], ibox[:, 3:] = np.asarray(shape, np.int32), -1
+    ibox = lattice.index_box(k, n_keys).astype(np.int32)
     at = np.nonzero(valid)
     for a in range(3):
         np.add.at(isum[:, a], kv[valid], at[a])
-        np.minimum.at(ibox[:, a], kv[valid], at[a].astype(np.int32))
-        np.maximum.at(ibox[:, 3 + a], kv[valid], at[a].astype(np.int32))
     faces = np.zeros((n_keys, n_keys, 3), np.int32)
     near = np.zeros((n_keys, n_keys, 3), np.int32) if gap > 0 else None
     for a in range(3):
@@ -81,20 +65,14 @@ def relation_tables(key, n_keys=None, gap=0, backend="device"):
     """The tables of clift_lattice_relations as a dict of tensors on key's device -- count (n_keys) int64, isum (n_keys, 3) int64, ibox
     (n_keys, 6) int32, faces and near (n_keys, n_keys, 3) int32 (near is None when gap == 0), rejected (1) int32 -- whatever ``rejected``
     says (``lattice_relations`` raises on it).  ``n_keys=None``: max(key) + 1, one read of the lattice's maximum."""
-    key = _as_key(key)
-    n0, n1, n2 = (int(x) for x in key.shape)
-    if n0 * n1 * n2 >= CC_LIMIT:
-        raise _lib.CliftError(f"lattice_relations: {n0 * n1 * n2} lattice points, must be < 2^31")
-    if key.numel() == 0:
-        raise ValueError(f"key must have at least one point along every axis, got {tuple(key.shape)}")
-    if n_keys is None:
-        n_keys = max(int(key.max()), 0) + 1
-    n_keys, gap = _check_sizes(n_keys, gap)
-    if _check_backend(backend) == "host":
+    key, n_keys = lattice.prepare(key, n_keys, "lattice_relations")
+    gap = int(gap)
+    if not 0 <= gap <= MAX_GAP:
+        raise ValueError(f"gap must be 0 .. {MAX_GAP} (got {gap})")
+    if lattice.check_backend(backend) == "host":
         return _tables_host(key, n_keys, gap)
-    if not key.is_cuda:
-        raise _lib.CliftError(f"lattice_relations: backend='device' wants the key on the GPU, got {key.device}")
-    dev = key.device
+    lattice.require_device(key, "lattice_relations")
+    dev, (n0, n1, n2) = key.device, key.shape
     out = dict(count=torch.empty(n_keys, dtype=torch.int64, device=dev), isum=torch.empty((n_keys, 3), dtype=torch.int64, device=dev),
                ibox=torch.empty((n_keys, 6), dtype=torch.int32, device=dev), faces=torch.empty((n_keys, n_keys, 3), dtype=torch.int32, device=dev),
                near=torch.empty((n_keys, n_keys, 3), dtype=torch.int32, device=dev) if gap > 0 else None,
@@ -108,9 +86,7 @@ def relation_tables(key, n_keys=None, gap=0, backend="device"):
 def lattice_relations(key, n_keys=None, gap=0, backend="device"):
     """``relation_tables`` of a key lattice (n0, n1, n2) bool or integer; raises CliftError when a point's key lies outside [0, n_keys)."""
     out = relation_tables(key, n_keys, gap, backend)
-    rejected = int(out["rejected"][0])
-    if rejected > 0:
-        raise _lib.CliftError(f"lattice_relations: {rejected} lattice points carry a key outside [0, {out['count'].shape[0]})")
+    lattice.raise_on_rejected(out, out["count"].shape[0], "lattice_relations")
     return out
 
 
@@ -149,7 +125,7 @@ def _up_axis(up):
     return "xyz".index(up[1]), up[0] == "+"
 
 
-class SceneGraph:
+class SceneGraph(lattice.Summary):
     """The graph of ``SceneGraph.from_counts``: ``nodes`` (one dict per key 1..K), ``pairs`` (one dict per ordered pair of nodes with any
     contact, u the lower one along the axis of the contact) and ``relations`` (the named ones: "on" and "beside")."""
 
@@ -169,15 +145,12 @@ class SceneGraph:
           beside  u < v with at least min_faces contacts on the other two axes together, in either order, and none along ``up``."""
         axis, positive = _up_axis(up)
         min_faces = int(min_faces)
-        host = {k: None if rel.get(k) is None else (rel[k].cpu().numpy() if torch.is_tensor(rel[k]) else np.asarray(rel[k])) for k in TABLES}
-        count, isum, ibox, faces = host["count"].astype(np.int64), host["isum"].astype(np.int64), host["ibox"].astype(np.int64), host["faces"].astype(np.int64)
-        near = np.zeros_like(faces) if host["near"] is None else host["near"].astype(np.int64)
-        K = len(nodes)
-        if count.shape[0] != K + 1:
-            raise ValueError(f"the tables hold {count.shape[0]} keys, the node list wants {K + 1}")
-        ticks = [np.asarray(t.cpu() if torch.is_tensor(t) else t, np.float64) for t in ticks]
+        host = lattice.to_host(rel, ("count", "isum", "ibox", "faces", "near"), np.int64)
+        count, isum, ibox, faces = host["count"], host["isum"], host["ibox"], host["faces"]
+        near = np.zeros_like(faces) if host["near"] is None else host["near"]
+        K = lattice.node_count(count, nodes)
+        ticks, step = lattice.host_ticks(ticks)
         first = np.asarray([t[0] for t in ticks])
-        step = np.asarray([(t[-1] - t[0]) / (t.shape[0] - 1) if t.shape[0] > 1 else 0.0 for t in ticks])
         face_area = np.asarray([abs(step[1] * step[2]), abs(step[0] * step[2]), abs(step[0] * step[1])])
         cell = float(abs(step[0] * step[1] * step[2]))
         contact = faces + near
@@ -231,9 +204,3 @@ class SceneGraph:
 
     def to_dict(self):
         return dict(up=self.up, min_faces=self.min_faces, nodes=self.nodes, pairs=self.pairs, relations=self.relations)
-
-    def to_json(self, **kw):
-        return json.dumps(self.to_dict(), **kw)
-
-    def __eq__(self, other):
-        return isinstance(other, SceneGraph) and self.to_dict() == other.to_dict()

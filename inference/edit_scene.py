@@ -93,7 +93,7 @@ import render_panopli as rp                                           # noqa: E4
 from contrastive_lift_amd import edit as ed                           # noqa: E402
 from contrastive_lift_amd import inference as inf                     # noqa: E402
 from contrastive_lift_amd.config import load_run_config               # noqa: E402
-from contrastive_lift_amd.relations import UP_AXES                    # noqa: E402
+from contrastive_lift_amd.lattice import DIRECTIONS as UP_AXES        # noqa: E402
 
 OPS = ("delete", "extract", "copy", "move")
 

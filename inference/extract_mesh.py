@@ -92,6 +92,7 @@ import render_panopli as rp                                           # noqa: E4
 from contrastive_lift_amd import clearance as clr                     # noqa: E402
 from contrastive_lift_amd import distance as dt                       # noqa: E402
 from contrastive_lift_amd import components as cc                     # noqa: E402
+from contrastive_lift_amd import lattice                              # noqa: E402
 from contrastive_lift_amd import mesh as cm                           # noqa: E402
 from contrastive_lift_amd import relations as rel                     # noqa: E402
 from contrastive_lift_amd.config import load_run_config               # noqa: E402
@@ -100,9 +101,9 @@ from contrastive_lift_amd.config import load_run_config               # noqa: E4
 def default_level(renderer, alpha_level):
     """The sigma at which ONE sample of a training step would have opacity ``alpha_level``: alpha = 1 - exp(-sigma step distance_scale).
     ``renderer`` comes from ``load_for_inference``, which halves the step ratio (RP:104): the training step is twice its step.
-    (``clearance.default_level``, which ``clearance.settle_offset`` shares; a bad ``alpha_level`` ends the tool.)"""
+    (``lattice.default_level``, which ``clearance.settle_offset`` shares; a bad ``alpha_level`` ends the tool.)"""
     try:
-        return clr.default_level(renderer, alpha_level)
+        return lattice.default_level(renderer, alpha_level)
     except ValueError as err:
         raise SystemExit(str(err))
 

@@ -29,7 +29,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from contrastive_lift_amd import _lib, distance, relations, synthetic   # noqa: E402
+from contrastive_lift_amd import _lib, distance, lattice, relations, synthetic   # noqa: E402
 
 
 def timed(fn, repeats):
@@ -86,9 +86,9 @@ def main():
                    rejected=torch.empty(1, dtype=torch.int32, device=dev))
         work = torch.empty(key.numel(), dtype=torch.int64, device=dev)
         lines.append(f"== upsample {upsample}: lattice {tuple(key.shape)}, {key.numel()} points, {len(nodes)} nodes, {int((key > 0).sum())} keyed points")
-        for title, k, table in (("transform, every node a site", key, distance.site_table(None, n_keys)), ("complement, key 0 the site", key, distance.site_table(0, n_keys)),
-                                ("corner, a single site", corner, distance.site_table(None, n_keys)),
-                                ("two opposite corners", corners, distance.site_table(None, n_keys))):
+        for title, k, table in (("transform, every node a site", key, lattice.key_table(None, n_keys)), ("complement, key 0 the site", key, lattice.key_table(0, n_keys)),
+                                ("corner, a single site", corner, lattice.key_table(None, n_keys)),
+                                ("two opposite corners", corners, lattice.key_table(None, n_keys))):
             site = torch.from_numpy(table.astype(np.uint8)).to(dev)
             _, *t = timed(lambda: transform_kernel(k, n_keys, site, out, work), a.repeats)
             first = {name: v.clone() for name, v in out.items()}

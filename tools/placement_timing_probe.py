@@ -30,7 +30,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from contrastive_lift_amd import _lib, distance, placement, relations, synthetic   # noqa: E402
+from contrastive_lift_amd import _lib, lattice, placement, relations, synthetic   # noqa: E402
 
 
 def timed(fn, repeats):
@@ -84,12 +84,12 @@ def main():
         sizes = torch.bincount(key.reshape(-1).long(), minlength=n_keys)
         u = 1 + int(sizes[1:].argmax())
         node_shape, origin = placement.object_of(key, u)
-        others = distance.site_table(None, n_keys)
+        others = lattice.key_table(None, n_keys)
         others[u] = False
         box = torch.ones((24, 24, 32), dtype=torch.uint8, device=dev)
         say(f"== upsample {upsample}: lattice {n}, {key.numel()} points, {len(nodes)} nodes, {int((key > 0).sum())} keyed points")
         for title, shape, table, target in ((f"node {u} ({int(node_shape.sum())} cells in {tuple(node_shape.shape)}), every other key solid", node_shape, others, origin),
-                                            ("dense 24 x 24 x 32 box, every key >= 1 solid", box, distance.site_table(None, n_keys), (0, 0, 0))):
+                                            ("dense 24 x 24 x 32 box, every key >= 1 solid", box, lattice.key_table(None, n_keys), (0, 0, 0))):
             m = tuple(int(x) for x in shape.shape)
             T = tuple(n[i] - m[i] + 1 for i in range(3))
             site = torch.from_numpy(table.astype(np.uint8)).to(dev)
